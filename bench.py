@@ -20,9 +20,9 @@ the costs, and every rank computes the same cost-balanced deal
 (shard.cost_deal) for the warm-up and timed steps -- as a renderer deals frame
 n+1 by frame n's costs (measured no better than the interleave, DESIGN.md
 section 6).
-value = the frame's rays / max-over-ranks step time.  The same run then also
-times weak scaling (key "weak"; --weak-extra 0 skips it): a step is a batch of
-N frames (seeds 42 .. 42+N-1; the reference re-seeds every frame,
+value = the frame's rays / max-over-ranks step time.  With --full the same run
+then also times weak scaling (key "weak"; --weak-extra 0 skips it): a step is
+a batch of N frames (seeds 42 .. 42+N-1; the reference re-seeds every frame,
 path_tracer.cu:493,513), each frame banded across all N GPUs, one all-to-all
 leaving frame f on rank f.  --scaling weak makes that the headline instead.
 
@@ -40,6 +40,14 @@ resident, so its algorithmic bytes are set against the guide's L2-resident
 gather rate, and the binding resource is read from the rocprofv3 PMC summary
 of the same workload committed under profiles/ (VALU issue, lane
 utilisation, HBM bytes).
+
+A plain run sets up, warms up, times --steps steps and prints the result line
+(ms_per_step = the timed region / --steps).  --full adds the measurements that
+take runs of their own: the CPU baseline (key "cpu_baseline"), the tolerance
+mode (key "tolerance_mode") and, with several ranks, weak scaling.
+--dump-outputs DIR writes the frame the last timed step returned
+(DIR/radiance.npy, float32); the inputs are fixed by the arguments, so two
+builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -79,6 +87,14 @@ def parse():
                          "(torch.distributed.run); default: WORLD_SIZE, else 1")
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also run the measurements that take runs of their own: the CPU "
+                         "baseline (--cpu-baseline), the tolerance mode (--fast-extra) and, with several ranks, "
+                         "weak scaling (--weak-extra); a plain run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the radiance frame the last timed step returned as "
+                         "DIR/radiance.npy (float32; rank r > 0 of a weak-scaling run: radiance_rank<r>.npy); a "
+                         "frame above the size budget is written as a fixed, seeded sample of its pixels")
     ap.add_argument("--config", choices=sorted(PRESETS), default=None,
                     help="SURVEY 8(d) preset; explicit flags after it still override")
     ap.add_argument("--scene", default="box")
@@ -98,9 +114,9 @@ def parse():
                          "bands dispatched first (interleaved-heavy-first: the interleave's); *-sets = that deal's bands ordered so the launch pipeline's three "
                          "band sets carry equal probe costs (shard.set_balanced_order)")
     ap.add_argument("--weak-extra", type=int, default=1,
-                    help="N>1 with --scaling strong: also time weak scaling (key 'weak')")
+                    help="--full, N>1 with --scaling strong: also time weak scaling (key 'weak')")
     ap.add_argument("--fast-extra", type=int, default=1,
-                    help="1 GPU: also time the tolerance mode (TPT_FLAG_FAST: FMA contraction, hardware "
+                    help="--full, 1 GPU: also time the tolerance mode (TPT_FLAG_FAST: FMA contraction, hardware "
                          "rcp/sqrt/sin/cos, no culling guards; not bit-exact: within SURVEY 8(d)'s tolerance at C2-C4, "
                          "C5's full-spp band meets the mean only) and report it under the key 'tolerance_mode' "
                          "beside the exact headline")
@@ -147,7 +163,7 @@ def parse():
     ap.add_argument("--extra-streams", type=int, default=0,
                     help="diagnostic: create this many busy-once HIP streams before the scene (as a process "
                          "group's communicator streams would), to check the launch pipeline's queue use")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="1: time the CPU port on rank 0 at N=1")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full: 1: time the CPU port on rank 0 at N=1")
     ap.add_argument("--cpu-spp", type=int, default=16)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every usable host core")
     ap.add_argument("--pmc-dir", default=os.path.join(ROOT, "profiles"),
@@ -176,13 +192,13 @@ def scene_file(name):
     if name == "c5":   # synthesized from the shipped scenes (tinypathtracer_amd.synth)
         import tempfile
         from tinypathtracer_amd import synth
-        out = os.path.join(tempfile.gettempdir(), "tpt_scenes", "c5.gltf")
+        out = os.path.join(tempfile.gettempdir(), f"tpt_scenes_{os.getuid()}", "c5.gltf")
         synth.write_c5(out, SCENE_DIR)
         return out
     if name.startswith("x1s") or name in ("x2", "x3"):   # the exactness scenes (synth.exactness_scene)
         import tempfile
         from tinypathtracer_amd import synth
-        out = os.path.join(tempfile.gettempdir(), "tpt_scenes", f"{name}.gltf")
+        out = os.path.join(tempfile.gettempdir(), f"tpt_scenes_{os.getuid()}", f"{name}.gltf")
         synth.write_scene(synth.exactness_scene(name, SCENE_DIR), out)
         return out
     p = os.path.join(SCENE_DIR, f"{name}.gltf")
@@ -366,6 +382,28 @@ def roofline(args, world, config, bytes_step, step_s, launches_per_step, avg_lau
             "avg_launch_ms": round(avg_launch_ms, 3), "limits": limits, "pmc_source": source,
             # the PMC summary's library == the one this bench ran (code-object hash)
             "pmc_same_build": same_build, "pmc_build": pmc_build}
+
+
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: every rank's file together
+
+
+def dump_outputs(out_dir, frame, rank, writers):
+    """--dump-outputs: the frame the last timed step returned (what a caller of
+    doTraceFrames + the rank exchange receives), float32 [H, W, 3], as
+    DIR/radiance.npy (rank r > 0 holding a frame: radiance_rank<r>.npy).  A
+    frame above this rank's share of the budget is written as [K, 3]: K pixels
+    drawn without replacement by a fixed seed, in ascending pixel order."""
+    if frame is None:   # a strong-scaling rank other than 0: rank 0 holds the frame
+        return
+    a = np.ascontiguousarray(frame.detach().cpu().numpy(), dtype=np.float32)
+    budget = DUMP_BUDGET_BYTES // max(writers, 1) - 4096   # (room for the .npy headers)
+    if a.nbytes > budget:
+        px = a.reshape(-1, a.shape[-1])
+        keep = budget // (px.shape[1] * px.itemsize)
+        idx = np.sort(np.random.default_rng(20240229).choice(px.shape[0], size=keep, replace=False))
+        a = np.ascontiguousarray(px[idx])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "radiance.npy" if rank == 0 else f"radiance_rank{rank}.npy"), a)
 
 
 KEYS = ["traversals", "internal_visits", "wide_visits", "leaf_tests", "shade_hits", "pixels", "samples", "trace_ms",
@@ -571,6 +609,8 @@ def main():
         return e, tot, mine, bms, frame, nfr, seeds, [round(p[0] / args.steps * 1e3, 3) for p in per], run_ms
 
     elapsed, tot, local_tot, build_ms, frame, n_frames, seeds, per_rank_ms, run_ms = measure_all(args.scaling)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame, rank, world if args.scaling == "weak" else 1)
 
     def verify(frame):
         """This rank's assembled frame (weak: frame `rank`, seed + rank; strong:
@@ -590,7 +630,7 @@ def main():
         verified = bool(okt.item() == 1.0)
 
     weak = None
-    if ranks > 1 and args.scaling == "strong" and args.weak_extra:
+    if args.full and ranks > 1 and args.scaling == "strong" and args.weak_extra:
         we, wt, _, _, _, wnf, _, wper, _ = measure_all("weak")
         weak = {"value": round(wt["traversals"] / we / 1e6, 2), "unit": "Mrays/s",
                 "ms_per_step": round(we / args.steps * 1e3, 3), "frames_per_step": wnf,
@@ -601,7 +641,7 @@ def main():
             weak["per_rank_ms"] = wper
 
     tolerance = None
-    if world == 1 and not emulate and args.fast_extra and not args.wavefront:
+    if args.full and world == 1 and not emulate and args.fast_extra and not args.wavefront:
         fe, ft, _, _, _, _, _ = measure(args.scaling, 0, T._lib.FLAG_FAST)
         tolerance = {"value": round(ft["traversals"] / fe / 1e6, 2), "unit": "Mrays/s",
                      "ms_per_step": round(fe / args.steps * 1e3, 3), "flags": "TPT_FLAG_FAST",
@@ -700,7 +740,7 @@ def main():
             # the assembled frame(s) must equal one GPU rendering every row (the
             # RNG subsequence is the global pixel index, path_tracer.cu:39,320)
             out["gather_verified"] = verified
-        if world == 1 and not emulate and args.cpu_baseline:
+        if args.full and world == 1 and not emulate and args.cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -30,13 +30,13 @@ def scene_path(name):
     if name == "c5":
         import tempfile
         from tinypathtracer_amd import synth
-        out = os.path.join(tempfile.gettempdir(), "tpt_scenes", "c5.gltf")
+        out = os.path.join(tempfile.gettempdir(), f"tpt_scenes_{os.getuid()}", "c5.gltf")
         synth.write_c5(out, SCENE_DIR)
         return out
     if name.startswith("x1s") or name in ("x2", "x3"):   # exactness scenes (synth.exactness_scene)
         import tempfile
         from tinypathtracer_amd import synth
-        out = os.path.join(tempfile.gettempdir(), "tpt_scenes", f"{name}.gltf")
+        out = os.path.join(tempfile.gettempdir(), f"tpt_scenes_{os.getuid()}", f"{name}.gltf")
         synth.write_scene(synth.exactness_scene(name, SCENE_DIR), out)
         return out
     return os.path.join(SCENE_DIR, f"{name}.gltf")

@@ -14,7 +14,8 @@ for c in $CS; do bash tools/gpu_round.sh $TAG $c $(args $c) || exit 1; done
 # bench lines read the fresh summaries (copied next to the committed ones)
 cp gpurun_out/stage_profiles/*.json profiles/ 2>/dev/null
 for c in $CS; do
-  if [ $c = c2 ]; then extra="--steps 5 --warmup 1"; else extra="$(args $c) --steps 2 --warmup 1 --cpu-baseline 0"; fi
+  # --full: the round's bench lines carry the CPU baseline (C2) and the tolerance mode
+  if [ $c = c2 ]; then extra="--full --steps 5 --warmup 1"; else extra="--full $(args $c) --steps 2 --warmup 1 --cpu-baseline 0"; fi
   timeout -k 10 600 python bench.py $extra > gpurun_out/stage_profiles/${TAG}_bench_$c.json 2> gpurun_out/${TAG}_bench_$c.err || { echo "bench $c failed"; exit 1; }
   python3 -c 'import json,sys; d=json.load(open(sys.argv[1])); r=d["roofline"]; print(sys.argv[2], d["value"], "Mrays/s", d["ms_per_step"], "ms", r["bound"], r["frac"], r["pmc_source"], "same build:", r.get("pmc_same_build"))' gpurun_out/stage_profiles/${TAG}_bench_$c.json $c
 done
