@@ -287,6 +287,71 @@ tpt_status tpt_render(tpt_scene* scene, const tpt_env* env, const tpt_camera* ca
 tpt_status tpt_render_frames(tpt_scene* scene, const tpt_env* env, const tpt_camera* camera,
                              const tpt_params* params, int32_t n_frames, const uint64_t* seeds,
                              float* const* radiance_outs, uint8_t* const* bgra_outs, tpt_stats* stats);
+
+/* ---- after the render: first-hit feature buffers and the denoiser (DESIGN.md section 5 "Post-pass") ---- */
+
+/* First-hit feature buffers (AOVs).  Each pointer is nullable and may be host
+ * or device memory (detected per pointer, as tpt_render does for its outputs);
+ * device outputs follow tpt_render's stream rule. */
+typedef struct {
+    float*   albedo;    /* W*H*3: the hit material's base colour; (1, 1, 1) on a miss */
+    float*   normal;    /* W*H*3: the shading normal of the hit prelude; (0, 0, 0) on a miss */
+    float*   depth;     /* W*H:   hitDist along the unit ray; 0 on a miss */
+    int32_t* face;      /* W*H:   face id; -1 on a miss */
+    int32_t* material;  /* W*H:   material id; -1 on a miss */
+} tpt_aov;              /* all row 0 = bottom, like radiance_out */
+
+/* One deterministic ray per pixel through the pixel centre (sampleRays,
+ * path_tracer.cu:42-59, with the jitter fixed at (0.5, 0.5); no RNG is consumed)
+ * through the render's own closest-hit traversal, then the hit prelude of
+ * path_tracer.cu:364-374: the buffers describe the surface the render's primary
+ * ray finds.  Whole frame only (bands and deals do not apply; in a multi-GPU run
+ * rank 0 calls it for the gathered frame).  A pending tpt_scene_build_async is
+ * waited for first.  trace_ms: nullable, the kernel's duration (HIP events).
+ * TPT_ERR_INVALID_ARG: unbuilt scene, width or height <= 0, null camera or out,
+ * or every pointer of out null. */
+tpt_status tpt_render_aov(tpt_scene* scene, const tpt_camera* camera, int32_t width, int32_t height,
+                          const tpt_aov* out, double* trace_ms);
+
+#define TPT_DENOISE_DEMODULATE 0x1   /* filter radiance / max(albedo, 1e-3), multiply back afterwards */
+#define TPT_DENOISE_DIRECT     0x2   /* A/B: steps 1 and 2 through the direct kernel too instead of the
+                                        LDS-staged one (bit-identical output) */
+
+typedef struct {
+    int32_t iterations;      /* 0..8; 0 = copy */
+    float   sigma_color;     /* > 0 */
+    float   sigma_normal;    /* > 0 */
+    float   sigma_depth;     /* > 0, relative */
+    int32_t flags;           /* TPT_DENOISE_* */
+} tpt_denoise_params;
+
+typedef struct { double pack_ms, filter_ms, resolve_ms; } tpt_denoise_stats;
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of a radiance frame,
+ * guided by its first-hit albedo, normal and depth (guides->face / material are
+ * ignored; the three others are required).  The filter is defined in DESIGN.md
+ * section 5 "Post-pass": iteration i has step 2^i and the 5x5 B3-spline taps h = [1/16, 1/4,
+ * 3/8, 1/4, 1/16] (taps outside the frame skipped), each weighted by
+ * exp(-|dc|^2 / (sigma_color 2^-i)^2) exp(-|dn|^2 / sigma_normal^2)
+ * exp(-dz^2 / (sigma_depth^2 max(z(p)^2, 1e-12))).  iterations 0: the output is the
+ * input bit for bit.  Non-finite input radiance is the caller's problem: a NaN or
+ * infinite pixel spreads to every pixel whose taps reach it.
+ *   radiance_in / radiance_out: W*H*3 floats, row 0 = bottom; may be the same
+ *     pointer; radiance_out nullable.
+ *   bgra_out: nullable, as tpt_render's (row 0 = top, B,G,R written, alpha
+ *     untouched, truncating toUChar).
+ * Inputs and outputs may be host or device memory (tpt_render's stream rule for
+ * device memory); all work is complete when the call returns.  `scene` supplies the
+ * device, the stream and the scratch planes, which stay with it between calls
+ * (48 B per pixel, and up to 44 B more to stage host buffers); it need not be
+ * built.  Deterministic (no atomics).
+ * TPT_ERR_INVALID_ARG: null scene / radiance_in / guides / params, a missing
+ * albedo, normal or depth guide, width or height <= 0, iterations outside 0..8,
+ * a sigma that is not > 0, both outputs null. */
+tpt_status tpt_denoise(tpt_scene* scene, int32_t width, int32_t height, const float* radiance_in,
+                       const tpt_aov* guides, const tpt_denoise_params* params, float* radiance_out,
+                       uint8_t* bgra_out, tpt_denoise_stats* stats);
+
 /* Introspection for tests: copy back the built BVH in the reference node
  * layout (bvh.cuh:52-58, 36 B/node, 2F-1 nodes) and the sorted Morton keys. */
 tpt_status tpt_scene_read_bvh(tpt_scene* scene, void* nodes36, int64_t* keys);

@@ -148,6 +148,26 @@ struct Frame {
     tpt_stats stats{};
 };
 
+// First-hit feature buffers (tpt_aov) in host memory, row 0 = bottom
+struct AOV {
+    int width = 0, height = 0;
+    std::vector<float> albedo, normal;   // 3 per pixel
+    std::vector<float> depth;
+    std::vector<int32_t> face, material;
+    tpt_aov view() { return tpt_aov{albedo.data(), normal.data(), depth.data(), face.data(), material.data()}; }
+};
+
+// The hosts' denoiser defaults (DESIGN.md section 5 "Post-pass")
+inline tpt_denoise_params defaultDenoise(int iterations = 5) {
+    tpt_denoise_params p{};
+    p.iterations = iterations;
+    p.sigma_color = 4.0f;
+    p.sigma_normal = 0.3f;
+    p.sigma_depth = 0.05f;
+    p.flags = TPT_DENOISE_DEMODULATE;
+    return p;
+}
+
 class PathTracer {
 public:
     PathTracer() : PathTracer(1920, 1080) {}   // VkEngine default extent (vkEngine.h:24)
@@ -201,6 +221,42 @@ public:
         check(tpt_render_frames(scene.handle(), envLight.handle(), &camera.c, &p, (int32_t)n, seeds.data(),
                                 radiances.empty() ? nullptr : radiances.data(),
                                 framebuffers.empty() ? nullptr : framebuffers.data(), &st));
+        return st;
+    }
+
+    // First-hit feature buffers of the frame (tpt_render_aov): one ray per pixel
+    // centre through the render's traversal.  Every plane is sized and filled;
+    // row 0 = bottom, like the radiance.
+    AOV renderAOV(DeviceScene& scene, const Camera& camera, double* trace_ms = nullptr) {
+        if (!scene.built()) scene.build();
+        AOV a;
+        a.width = m_width;
+        a.height = m_height;
+        const size_t n = (size_t)m_width * m_height;
+        a.albedo.resize(3 * n);
+        a.normal.resize(3 * n);
+        a.depth.resize(n);
+        a.face.resize(n);
+        a.material.resize(n);
+        const tpt_aov out = a.view();
+        check(tpt_render_aov(scene.handle(), &camera.c, m_width, m_height, &out, trace_ms));
+        return a;
+    }
+    // The same into caller buffers (host or device pointers, each nullable).
+    void renderAOV(DeviceScene& scene, const Camera& camera, const tpt_aov& out, double* trace_ms = nullptr) {
+        if (!scene.built()) scene.build();
+        check(tpt_render_aov(scene.handle(), &camera.c, m_width, m_height, &out, trace_ms));
+    }
+
+    // Edge-avoiding a-trous filter (tpt_denoise) of a radiance frame guided by its
+    // feature buffers; radiance_out may be radiance_in, framebuffer is written as
+    // doTrace writes it (nullable).  Pointers are host or device memory.
+    tpt_denoise_stats denoise(DeviceScene& scene, const float* radiance_in, const tpt_aov& guides,
+                              float* radiance_out, uint8_t* framebuffer = nullptr,
+                              const tpt_denoise_params& params = defaultDenoise(5)) {
+        tpt_denoise_stats st{};
+        check(tpt_denoise(scene.handle(), m_width, m_height, radiance_in, &guides, &params, radiance_out, framebuffer,
+                          &st));
         return st;
     }
 

@@ -1,0 +1,153 @@
+"""tpt_render_aov: the first-hit feature buffers against the CPU oracle.
+
+The reference rays are built in numpy float32 in sampleRays' order of operations
+(tests/post_ref.py) and traced with orc_trace_ray over the oracle's BVH.  A pixel is
+comparable when the 3x3 neighbourhood of the oracle's face image around it is
+uniform (edge pixels replicated): a last-bit difference in ray generation cannot
+change what such a pixel hits, while wrong rays, flipped rows and wrong lookups
+still show."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import tinypathtracer_amd as T
+from tinypathtracer_amd import _lib
+from oracle import oracle as O
+
+from tests.conftest import scene_path
+from tests import post_ref as R
+
+pytestmark = pytest.mark.gpu
+
+W, H = 256, 144
+KEYS = ("albedo", "normal", "depth", "face", "material")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else a.dtype)
+
+
+def comparable(face):
+    p = np.pad(face, 1, mode="edge")
+    same = np.ones(face.shape, bool)
+    for dy in range(3):
+        for dx in range(3):
+            same &= p[dy:dy + face.shape[0], dx:dx + face.shape[1]] == face
+    return same
+
+
+@pytest.fixture(scope="module")
+def frames(gpu_available):
+    """Per scene: the device scene, the GPU buffers and the oracle's (computed once, read only)."""
+    out = {}
+    for name in ("box", "box2"):
+        s = T.Scene(scene_path(name))
+        d = s.copySceneToDevice(0).build()
+        pt = T.PathTracer("", W, H, 0)
+        gpu = pt.renderAOV(d, s.m_camera)
+        ref = R.oracle_aov(O.load_scene(scene_path(name)), W, H)
+        out[name] = (s, d, pt, gpu, ref)
+    yield out
+    for _, d, _, _, _ in out.values():
+        d.close()
+
+
+@pytest.mark.parametrize("name", ["box", "box2"])
+def test_aov_matches_oracle(frames, name):
+    s, d, pt, gpu, ref = frames[name]
+    ok = comparable(ref["face"])
+    hit = ok & (ref["face"] >= 0)
+    print(f"{name}: comparable {ok.mean():.3f}, comparable hits {hit.mean():.3f}")
+    assert ok.mean() >= 0.75 and hit.mean() >= 0.25
+    assert np.array_equal(gpu["face"][ok], ref["face"][ok])
+    assert np.array_equal(gpu["material"][ok], ref["material"][ok])
+    assert np.array_equal(_bits(gpu["albedo"][ok]), _bits(ref["albedo"][ok]))
+    rel = np.abs(gpu["depth"][hit].astype(np.float64) - ref["depth"][hit]) / ref["depth"][hit]
+    dn = np.abs(gpu["normal"][hit].astype(np.float64) - ref["normal"][hit])
+    print(f"{name}: max relative depth error {rel.max():.3e}, max normal error {dn.max():.3e}")
+    assert rel.max() <= 1e-4
+    assert dn.max() <= 1e-4
+
+
+@pytest.mark.parametrize("name", ["box", "box2"])
+def test_aov_miss_convention(frames, name):
+    s, d, pt, gpu, ref = frames[name]
+    miss = comparable(ref["face"]) & (ref["face"] < 0)
+    assert miss.sum() > 0
+    assert (gpu["face"][miss] == -1).all() and (gpu["material"][miss] == -1).all()
+    assert (_bits(gpu["depth"][miss]) == 0).all()
+    assert (_bits(gpu["normal"][miss]) == 0).all()
+    assert (gpu["albedo"][miss] == 1.0).all()
+
+
+def _with_sentinel(w, h):
+    """Each output with one more row past its end, filled with a sentinel."""
+    bufs = {"albedo": np.full((h + 1, w, 3), -7.0, np.float32), "normal": np.full((h + 1, w, 3), -7.0, np.float32),
+            "depth": np.full((h + 1, w), -7.0, np.float32), "face": np.full((h + 1, w), -77, np.int32),
+            "material": np.full((h + 1, w), -77, np.int32)}
+    return bufs, {k: v[:h] for k, v in bufs.items()}
+
+
+def test_aov_odd_size_writes_every_pixel_and_nothing_else(frames):
+    s, d, _, _, _ = frames["box"]
+    w, h = 50, 38                                          # not multiples of the 16 x 16 tile
+    bufs, views = _with_sentinel(w, h)
+    T.PathTracer("", w, h, 0).renderAOV(d, s.m_camera, out=views)
+    for k in KEYS:
+        assert (bufs[k][h] == (-7.0 if bufs[k].dtype == np.float32 else -77)).all(), k
+        assert not (views[k] == (-7.0 if bufs[k].dtype == np.float32 else -77)).any(), k
+    assert (views["face"] >= 0).mean() > 0.25              # the box fills the middle of the frame
+    assert ((views["face"] >= 0) == (views["depth"] > 0)).all()
+
+
+def test_aov_device_outputs_equal_host_outputs(frames):
+    import torch
+    s, d, pt, gpu, _ = frames["box"]
+    dev = torch.device("cuda", 0)
+    out = {"albedo": torch.full((H, W, 3), -7.0, device=dev), "normal": torch.full((H, W, 3), -7.0, device=dev),
+           "depth": torch.full((H, W), -7.0, device=dev),
+           "face": torch.full((H, W), -77, dtype=torch.int32, device=dev),
+           "material": torch.full((H, W), -77, dtype=torch.int32, device=dev)}
+    pt.renderAOV(d, s.m_camera, out=out)
+    for k in KEYS:
+        assert np.array_equal(_bits(out[k].cpu().numpy()), _bits(gpu[k])), k
+
+
+def test_aov_deterministic(frames):
+    s, d, pt, gpu, _ = frames["box2"]
+    st = {}
+    again = pt.renderAOV(d, s.m_camera, stats=st)
+    for k in KEYS:
+        assert np.array_equal(_bits(again[k]), _bits(gpu[k])), k
+    assert st["trace_ms"] > 0.0
+
+
+def test_aov_nullable_outputs(frames):
+    s, d, pt, gpu, _ = frames["box"]
+    depth = np.full((H, W), -7.0, np.float32)
+    out = pt.renderAOV(d, s.m_camera, out={"depth": depth})
+    assert set(out) == {"depth"}
+    assert np.array_equal(_bits(depth), _bits(gpu["depth"]))
+
+
+def test_aov_refusals(frames):
+    s, d, pt, _, _ = frames["box"]
+    L = T.lib()
+    cam = s.m_camera.to_c()
+    depth = np.zeros((H, W), np.float32)
+    a = _lib.Aov(None, None, depth.ctypes.data, None, None)
+
+    def refused(rc, word):
+        assert rc == 1                                     # TPT_ERR_INVALID_ARG
+        assert word in L.tpt_last_error(), L.tpt_last_error()
+
+    unbuilt = T.Scene(scene_path("box")).copySceneToDevice(0)
+    refused(L.tpt_render_aov(unbuilt.handle, C.byref(cam), W, H, C.byref(a), None), b"not built")
+    unbuilt.close()
+    refused(L.tpt_render_aov(d.handle, C.byref(cam), 0, H, C.byref(a), None), b"frame size")
+    refused(L.tpt_render_aov(d.handle, C.byref(cam), W, -3, C.byref(a), None), b"frame size")
+    refused(L.tpt_render_aov(d.handle, C.byref(cam), W, H, None, None), b"null")
+    none = _lib.Aov()
+    refused(L.tpt_render_aov(d.handle, C.byref(cam), W, H, C.byref(none), None), b"every pointer")
+    assert (depth == 0).all()                              # no refused call wrote anything

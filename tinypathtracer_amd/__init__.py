@@ -23,7 +23,7 @@ from . import _lib
 from ._lib import TPTError, build_identity, check, lib
 
 __all__ = ["Camera", "Scene", "DeviceScene", "BVH", "EnvLight", "PathTracer", "Frame", "TPTError",
-           "procedural_sky", "version", "device_count", "build_identity", "NODE_DTYPE"]
+           "procedural_sky", "version", "device_count", "build_identity", "NODE_DTYPE", "DENOISE_DEFAULTS"]
 
 # BVHNode (include/bvh.cuh:52-58): parent, info{left,right | fid,placeHolder}, box
 NODE_DTYPE = np.dtype([("parent", "<u4"), ("a", "<i4"), ("b", "<i4"), ("bmin", "<f4", 3), ("bmax", "<f4", 3)])
@@ -378,6 +378,30 @@ class Frame:
     stats: dict = field(default_factory=dict)
 
 
+# Denoiser defaults of the Python host and the CLI (DESIGN.md section 5 "Post-pass":
+# checked against a 2,048-spp render of box at 8 spp)
+DENOISE_DEFAULTS = {"iterations": 5, "sigma_color": 4.0, "sigma_normal": 0.3, "sigma_depth": 0.05,
+                    "demodulate": True}
+
+# buffer name -> (values per pixel, element type) of tpt_aov's planes, the radiance and the framebuffer
+AOV_LAYOUT = {"albedo": (3, "float32"), "normal": (3, "float32"), "depth": (1, "float32"),
+              "face": (1, "int32"), "material": (1, "int32")}
+_PLANES = dict(AOV_LAYOUT, radiance=(3, "float32"), framebuffer=(4, "uint8"))
+
+
+def _check_plane(name, buf, width, height):
+    """The library reads / writes width * height * channels elements behind the
+    pointer: refuse a buffer of another size or element type."""
+    ch, dt = _PLANES[name]
+    if isinstance(buf, int):   # a raw device pointer: the caller's responsibility
+        return
+    n = buf.size if isinstance(buf, np.ndarray) else buf.numel()
+    have = str(buf.dtype).replace("torch.", "")
+    if n != width * height * ch or have != dt:
+        raise ValueError(f"{name}: need {width * height * ch} {dt} values ({height} x {width} x {ch}), "
+                         f"got {n} of {have}")
+
+
 class PathTracer:
     """PathTracer (include/path_tracer.h:16-35), headless.
 
@@ -466,6 +490,73 @@ class PathTracer:
         check(lib().tpt_render_frames(d_scene.handle, env, C.byref(cam), C.byref(p), n, cs,
                                       rp[0] if rp else None, fp[0] if fp else None, C.byref(st)))
         return st.as_dict()
+
+    def renderAOV(self, d_scene: DeviceScene, camera: Camera, out=None, stats=None):
+        """First-hit feature buffers of the frame (tpt_render_aov): one ray per pixel
+        centre through the render's own traversal.  Returns a dict of `albedo`
+        [H, W, 3], `normal` [H, W, 3], `depth` [H, W] (float32), `face`, `material`
+        [H, W] (int32), row 0 = bottom like the radiance; misses hold albedo 1,
+        normal 0, depth 0, face / material -1.  out: a dict with any of those keys
+        (numpy arrays or torch CUDA tensors): only these are computed, into the
+        given buffers; None: all five, as numpy arrays.  stats: a dict that
+        receives `trace_ms`."""
+        if not d_scene.built:
+            d_scene.build()
+        W, H = self.m_width, self.m_height
+        if out is None:
+            out = {"albedo": np.zeros((H, W, 3), np.float32), "normal": np.zeros((H, W, 3), np.float32),
+                   "depth": np.zeros((H, W), np.float32), "face": np.zeros((H, W), np.int32),
+                   "material": np.zeros((H, W), np.int32)}
+        unknown = set(out) - set(AOV_LAYOUT)
+        if unknown:
+            raise ValueError(f"unknown feature buffers {sorted(unknown)}")
+        a = _lib.Aov()
+        for k, buf in out.items():
+            if buf is not None:
+                _check_plane(k, buf, W, H)
+                setattr(a, k, _addr(buf))
+        ms = C.c_double()
+        cam = camera.to_c()
+        check(lib().tpt_render_aov(d_scene.handle, C.byref(cam), W, H, C.byref(a), C.byref(ms)))
+        if stats is not None:
+            stats["trace_ms"] = ms.value
+        return out
+
+    def denoise(self, d_scene: DeviceScene, radiance, aov, iterations: int = DENOISE_DEFAULTS["iterations"],
+                sigma_color: float = DENOISE_DEFAULTS["sigma_color"],
+                sigma_normal: float = DENOISE_DEFAULTS["sigma_normal"],
+                sigma_depth: float = DENOISE_DEFAULTS["sigma_depth"],
+                demodulate: bool = DENOISE_DEFAULTS["demodulate"], out=None, framebuffer=None, flags: int = 0,
+                stats=None):
+        """Edge-avoiding a-trous filter (tpt_denoise, DESIGN.md section 5 "Post-pass")
+        of `radiance` [H, W, 3] guided by aov["albedo"], aov["normal"] and
+        aov["depth"] (renderAOV).  d_scene supplies the device and keeps the scratch
+        planes.  out: the filtered radiance's buffer (may be `radiance` itself;
+        None: a new numpy array); framebuffer: optional [H, W, 4] uint8, written as
+        doTrace writes it (row 0 = top, B, G, R; alpha untouched).  Buffers are numpy
+        arrays or torch CUDA tensors.  Returns `out`; stats: a dict that receives
+        pack_ms, filter_ms, resolve_ms."""
+        W, H = self.m_width, self.m_height
+        _check_plane("radiance", radiance, W, H)
+        g = _lib.Aov()
+        for k in ("albedo", "normal", "depth"):
+            buf = aov.get(k)
+            if buf is not None:
+                _check_plane(k, buf, W, H)
+                setattr(g, k, _addr(buf))
+        if out is None:
+            out = np.zeros((H, W, 3), np.float32)
+        _check_plane("radiance", out, W, H)
+        if framebuffer is not None:
+            _check_plane("framebuffer", framebuffer, W, H)
+        p = _lib.DenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth),
+                               int(flags) | (_lib.DENOISE_DEMODULATE if demodulate else 0))
+        st = _lib.DenoiseStats()
+        check(lib().tpt_denoise(d_scene.handle, W, H, _addr(radiance), C.byref(g), C.byref(p), _addr(out),
+                                _addr(framebuffer), C.byref(st)))
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out
 
     def render(self, meshFile: str, nSamplesPerPixel: int = 64, seed=None, max_depth: int = 8, frames: int = 1):
         scene = Scene(meshFile, "gltf")

@@ -22,6 +22,8 @@ FLAG_APPROX_CULL = 0x10
 FLAG_WAVEFRONT = 0x20
 FLAG_FAST = 0x40
 DESC_DELTALIGHT_LAYOUT = 0x1
+DENOISE_DEMODULATE = 0x1
+DENOISE_DIRECT = 0x2
 
 
 class Material(C.Structure):
@@ -78,6 +80,23 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class Aov(C.Structure):
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("face", C.c_void_p),
+                ("material", C.c_void_p)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("flags", C.c_int32)]
+
+
+class DenoiseStats(C.Structure):
+    _fields_ = [("pack_ms", C.c_double), ("filter_ms", C.c_double), ("resolve_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # (name, restype, argtypes) -- every symbol include/tpt.h declares
 SIGNATURES = [
     ("tpt_version", C.c_char_p, []),
@@ -99,6 +118,10 @@ SIGNATURES = [
     ("tpt_render_frames", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_int32,
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                     C.POINTER(Stats)]),
+    ("tpt_render_aov", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(Aov),
+                                 C.POINTER(C.c_double)]),
+    ("tpt_denoise", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Aov),
+                              C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.POINTER(DenoiseStats)]),
     ("tpt_scene_read_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_scene_read_world", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_debug_rng_init", C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),

@@ -254,6 +254,45 @@ hipError_t launch_hot_kat(int op, uint32_t n, const float* in, float* out, hipSt
 hipError_t launch_trace_rays(const TraceArgs& a, uint32_t n, const float* o, const float* d, const int32_t* ofid,
                              int mode, int32_t* hit, float* t, float* uv, hipStream_t s);
 
+// post.hip: first-hit feature buffers (tpt_render_aov) and the a-trous denoiser (tpt_denoise)
+struct AovArgs {                         // device pointers, each nullable; W*H pixels, row 0 = bottom
+    float* albedo;                       // 3 per pixel
+    float* normal;                       // 3 per pixel
+    float* depth;
+    int32_t* face;
+    int32_t* material;
+};
+// a: the scene, the camera constants, width, height, inv_w, inv_h (whole frame; bands do not apply)
+hipError_t launch_aov(const TraceArgs& a, const AovArgs& o, hipStream_t s);
+
+struct DenoiseArgs {                     // pack (inputs -> planes) and resolve (plane -> outputs)
+    const float* radiance_in;            // pack: W*H*3
+    const float* albedo;                 // W*H*3 (read when demodulate)
+    const float* normal;                 // pack: W*H*3
+    const float* depth;                  // pack: W*H
+    float4* color0;                      // pack writes it (rgb, 0); resolve reads the last iteration's plane here
+    float4* guide;                       // pack: (n.xyz, z)
+    float* radiance_out;                 // resolve: nullable, W*H*3, row 0 = bottom
+    uint8_t* bgra;                       // resolve: nullable, W*H*4, row 0 = top, alpha untouched
+    size_t npix;
+    int32_t width, height;
+    int32_t demodulate;
+};
+struct AtrousArgs {                      // one iteration: dst = filter(src) at this step
+    const float4* src;
+    const float4* guide;
+    float4* dst;
+    int32_t width, height;
+    int32_t step;                        // 2^i
+    float inv_sc2;                       // 1 / sigma_c,i^2
+    float inv_sn2;                       // 1 / sigma_n^2
+    float sz2;                           // sigma_z^2
+};
+hipError_t launch_denoise_pack(const DenoiseArgs& a, hipStream_t s);
+// use_lds: steps 1 and 2 through the LDS-staged kernel (bit-identical to the direct one)
+hipError_t launch_atrous(const AtrousArgs& a, bool use_lds, hipStream_t s);
+hipError_t launch_denoise_resolve(const DenoiseArgs& a, hipStream_t s);
+
 }  // namespace tpt
 
 // The tolerance-mode build of trace.hip (TPT_FLAG_FAST; Makefile trace_fast.hip.o):

@@ -422,6 +422,14 @@ struct tpt_scene {
     DevBuf<float4> wf_q0, wf_q1, wf_hit;
     HostPinned<uint32_t> wf_count;
     hipEvent_t wf_ev[2] = {nullptr, nullptr};
+    // post-pass (post.hip).  tpt_render_aov: device staging of host outputs.  tpt_denoise: the two
+    // colour planes and the guide plane (float4 per pixel each), device staging of host inputs /
+    // outputs.  All kept between calls, as the wavefront buffers are.
+    DevBuf<float> aov_f3[2], aov_depth;     // albedo, normal; depth
+    DevBuf<int32_t> aov_i[2];               // face, material
+    DevBuf<float4> dn_color[2], dn_guide;
+    DevBuf<float> dn_rad, dn_f3[2], dn_depth;   // radiance in / out; albedo, normal; depth
+    DevBuf<uint8_t> dn_bgra;
 
     ~tpt_scene() {
         DeviceGuard g(device);
@@ -1695,6 +1703,186 @@ tpt_status tpt_render_frames(tpt_scene* s, const tpt_env* env, const tpt_camera*
     s->acc_list = list;
     s->acc_seeds = fseeds;
     s->acc_spp = total_spp;
+    return TPT_OK;
+}
+
+// First-hit feature buffers (post.hip k_aov): the whole frame, one ray per pixel
+// centre.  Host outputs are written to the scene's staging buffers and copied back.
+tpt_status tpt_render_aov(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_t H, const tpt_aov* out,
+                          double* trace_ms) {
+    if (!s || !s->built) return fail(TPT_ERR_INVALID_ARG, "scene not built");
+    if (!cam || !out) return fail(TPT_ERR_INVALID_ARG, "null argument");
+    if (W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size");
+    if (!out->albedo && !out->normal && !out->depth && !out->face && !out->material)
+        return fail(TPT_ERR_INVALID_ARG, "no feature buffer requested: every pointer of out is null");
+    {
+        const tpt_status bs = finish_pending(s);
+        if (bs != TPT_OK) return bs;
+    }
+    DeviceGuard g(s->device);
+    hipStream_t st = s->stream;
+    const size_t npix = (size_t)W * (size_t)H;
+    tpt::TraceArgs a{};
+    fill_trace_args(s, nullptr, cam, a);
+    a.width = W;
+    a.height = H;
+    a.inv_w = 1.0f / (float)W;
+    a.inv_h = 1.0f / (float)H;
+    tpt::AovArgs o{};
+    float* const hf3[2] = {out->albedo, out->normal};
+    float** const df3[2] = {&o.albedo, &o.normal};
+    for (int k = 0; k < 2; ++k) {
+        if (!hf3[k]) continue;
+        if (is_device_ptr(hf3[k])) {
+            *df3[k] = hf3[k];
+        } else {
+            HIP_OR_FAIL(s->aov_f3[k].alloc(3 * npix));
+            *df3[k] = s->aov_f3[k].p;
+        }
+    }
+    if (out->depth) {
+        if (is_device_ptr(out->depth)) {
+            o.depth = out->depth;
+        } else {
+            HIP_OR_FAIL(s->aov_depth.alloc(npix));
+            o.depth = s->aov_depth.p;
+        }
+    }
+    int32_t* const hi[2] = {out->face, out->material};
+    int32_t** const di[2] = {&o.face, &o.material};
+    for (int k = 0; k < 2; ++k) {
+        if (!hi[k]) continue;
+        if (is_device_ptr(hi[k])) {
+            *di[k] = hi[k];
+        } else {
+            HIP_OR_FAIL(s->aov_i[k].alloc(npix));
+            *di[k] = s->aov_i[k].p;
+        }
+    }
+    HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
+    HIP_OR_FAIL(tpt::launch_aov(a, o, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
+    for (int k = 0; k < 2; ++k) {
+        if (hf3[k] && *df3[k] != hf3[k])
+            HIP_OR_FAIL(hipMemcpyAsync(hf3[k], *df3[k], 3 * npix * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (hi[k] && *di[k] != hi[k])
+            HIP_OR_FAIL(hipMemcpyAsync(hi[k], *di[k], npix * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    if (out->depth && o.depth != out->depth)
+        HIP_OR_FAIL(hipMemcpyAsync(out->depth, o.depth, npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    if (trace_ms) {
+        float ms = 0.0f;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        *trace_ms = ms;
+    }
+    return TPT_OK;
+}
+
+// The a-trous denoiser (post.hip; DESIGN.md section 5 "Post-pass"): pack, one launch
+// per iteration between the two colour planes, resolve.  Host inputs are uploaded
+// to the scene's staging buffers, host outputs copied back from them.
+tpt_status tpt_denoise(tpt_scene* s, int32_t W, int32_t H, const float* radiance_in, const tpt_aov* guides,
+                       const tpt_denoise_params* p, float* radiance_out, uint8_t* bgra_out,
+                       tpt_denoise_stats* stats) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (!radiance_in || !guides || !p) return fail(TPT_ERR_INVALID_ARG, "null argument");
+    if (!guides->albedo || !guides->normal || !guides->depth)
+        return fail(TPT_ERR_INVALID_ARG, "the denoiser needs the albedo, normal and depth guides");
+    if (W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size");
+    if (p->iterations < 0 || p->iterations > 8) return fail(TPT_ERR_INVALID_ARG, "iterations must be 0..8");
+    if (!(p->sigma_color > 0.0f) || !(p->sigma_normal > 0.0f) || !(p->sigma_depth > 0.0f))
+        return fail(TPT_ERR_INVALID_ARG, "sigma_color, sigma_normal and sigma_depth must be > 0");
+    if (p->flags & ~(TPT_DENOISE_DEMODULATE | TPT_DENOISE_DIRECT)) return fail(TPT_ERR_INVALID_ARG, "unknown denoise flags");
+    if (!radiance_out && !bgra_out) return fail(TPT_ERR_INVALID_ARG, "no output buffer");
+    DeviceGuard g(s->device);
+    hipStream_t st = s->stream;
+    const size_t npix = (size_t)W * (size_t)H;
+    // iterations 0: the input bit for bit, so no demodulation round trip
+    const bool demod = (p->flags & TPT_DENOISE_DEMODULATE) && p->iterations > 0;
+    HIP_OR_FAIL(s->dn_color[0].alloc(npix));
+    HIP_OR_FAIL(s->dn_color[1].alloc(npix));
+    HIP_OR_FAIL(s->dn_guide.alloc(npix));
+    tpt::DenoiseArgs d{};
+    d.npix = npix;
+    d.width = W;
+    d.height = H;
+    d.demodulate = demod ? 1 : 0;
+    d.color0 = s->dn_color[0].p;
+    d.guide = s->dn_guide.p;
+    const bool rin_dev = is_device_ptr(radiance_in), rout_dev = is_device_ptr(radiance_out);
+    const bool bgra_dev = is_device_ptr(bgra_out);
+    if (!rin_dev || (radiance_out && !rout_dev)) HIP_OR_FAIL(s->dn_rad.alloc(3 * npix));
+    if (rin_dev) {
+        d.radiance_in = radiance_in;
+    } else {
+        HIP_OR_FAIL(hipMemcpyAsync(s->dn_rad.p, radiance_in, 3 * npix * sizeof(float), hipMemcpyHostToDevice, st));
+        d.radiance_in = s->dn_rad.p;
+    }
+    const float* const hf3[2] = {guides->albedo, guides->normal};
+    const float** const df3[2] = {&d.albedo, &d.normal};
+    for (int k = 0; k < 2; ++k) {
+        if (is_device_ptr(hf3[k])) {
+            *df3[k] = hf3[k];
+        } else {
+            HIP_OR_FAIL(s->dn_f3[k].alloc(3 * npix));
+            HIP_OR_FAIL(hipMemcpyAsync(s->dn_f3[k].p, hf3[k], 3 * npix * sizeof(float), hipMemcpyHostToDevice, st));
+            *df3[k] = s->dn_f3[k].p;
+        }
+    }
+    if (is_device_ptr(guides->depth)) {
+        d.depth = guides->depth;
+    } else {
+        HIP_OR_FAIL(s->dn_depth.alloc(npix));
+        HIP_OR_FAIL(hipMemcpyAsync(s->dn_depth.p, guides->depth, npix * sizeof(float), hipMemcpyHostToDevice, st));
+        d.depth = s->dn_depth.p;
+    }
+    if (radiance_out) d.radiance_out = rout_dev ? radiance_out : s->dn_rad.p;   // (pack has read dn_rad by then)
+    if (bgra_out) {
+        if (bgra_dev) {
+            d.bgra = bgra_out;
+        } else {   // alpha is untouched: the caller's bytes go up first
+            HIP_OR_FAIL(s->dn_bgra.alloc(4 * npix));
+            HIP_OR_FAIL(hipMemcpyAsync(s->dn_bgra.p, bgra_out, 4 * npix, hipMemcpyHostToDevice, st));
+            d.bgra = s->dn_bgra.p;
+        }
+    }
+    HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
+    HIP_OR_FAIL(tpt::launch_denoise_pack(d, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
+    tpt::AtrousArgs f{};
+    f.guide = s->dn_guide.p;
+    f.width = W;
+    f.height = H;
+    constexpr double kFltMax = 3.402823466e+38;
+    f.inv_sn2 = (float)std::min(1.0 / ((double)p->sigma_normal * p->sigma_normal), kFltMax);
+    f.sz2 = (float)((double)p->sigma_depth * p->sigma_depth);
+    const bool use_lds = !(p->flags & TPT_DENOISE_DIRECT);
+    for (int i = 0; i < p->iterations; ++i) {
+        f.src = s->dn_color[i & 1].p;
+        f.dst = s->dn_color[(i + 1) & 1].p;
+        f.step = 1 << i;
+        const double sc = (double)p->sigma_color / (double)(1 << i);   // sigma_c,i = sigma_color 2^-i
+        f.inv_sc2 = (float)std::min(1.0 / (sc * sc), kFltMax);
+        HIP_OR_FAIL(tpt::launch_atrous(f, use_lds, st));
+    }
+    HIP_OR_FAIL(hipEventRecord(s->ev[2], st));
+    d.color0 = s->dn_color[p->iterations & 1].p;
+    HIP_OR_FAIL(tpt::launch_denoise_resolve(d, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[3], st));
+    if (radiance_out && !rout_dev)
+        HIP_OR_FAIL(hipMemcpyAsync(radiance_out, s->dn_rad.p, 3 * npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (bgra_out && !bgra_dev) HIP_OR_FAIL(hipMemcpyAsync(bgra_out, s->dn_bgra.p, 4 * npix, hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    if (stats) {
+        float ms = 0.0f;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        stats->pack_ms = ms;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
+        stats->filter_ms = ms;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+        stats->resolve_ms = ms;
+    }
     return TPT_OK;
 }
 

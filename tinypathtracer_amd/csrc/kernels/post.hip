@@ -1,0 +1,266 @@
+// post.hip -- what follows a render: the first-hit feature buffers (tpt_render_aov)
+// and the edge-avoiding a-trous wavelet denoiser (tpt_denoise; Dammertz et al. 2010,
+// DESIGN.md section 5 "Post-pass").
+//
+//  * k_aov: one lane per pixel in 16x16 tiles, each wave an 8x8 sub-tile as in
+//    k_trace (primary rays are coherent); the ray through the pixel centre --
+//    sampleRays (path_tracer.cu:42-59) with the jitter fixed at (0.5, 0.5), no RNG --
+//    walks the render's own closest-hit traversal exactly as k_trace_rays mode 1
+//    (trav_lane<true>, the sliver pass, the grazing re-trace), then the hit prelude
+//    of path_tracer.cu:364-374.  The LDS stack is k_trace_rays'.
+//  * k_dn_pack / k_atrous / k_atrous_lds / k_dn_resolve: the filter.  Two float4
+//    planes per pixel (colour; normal + depth), one launch per iteration ping-ponging
+//    between two colour planes, no atomics.  Each tap is two 16-B loads per lane;
+//    a wave of the direct kernel is a 64-pixel row segment, so its lanes read
+//    1 KiB of contiguous addresses per plane at every step size.
+#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"   // trace_dev.hpp's env helpers, unused here
+#include "trace_dev.hpp"
+
+namespace tpt {
+
+constexpr int kAovLdsSlots = 48;   // LDS stack slots per lane, as k_trace_rays; deeper ones private
+
+__global__ __launch_bounds__(256) void k_aov(TraceArgs a, AovArgs o) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+    const int y = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (x >= a.width || y >= a.height) return;   // (no barrier below)
+    // sampleRays (path_tracer.cu:42-59), k_trace's camera section with ju = jv = 0.5
+    float lx = 0.5f * 1.0f, lyf = 0.5f * 1.0f;
+    lx = lx + (float)x;
+    lyf = lyf + (float)y;
+    lx = lx * a.inv_w;
+    lyf = lyf * a.inv_h;
+    lx = lx * a.sensor_w;
+    lyf = lyf * a.sensor_h;
+    float r4[4];
+    mat4_vec4(a.c2w, lx - a.half_sw, lyf - a.half_sh, 0.0f - 1.0f, 0.0f, r4);
+    const V3 rd = normalize(v3(r4[0], r4[1], r4[2]));
+    const V3 ro = v3(a.origin[0], a.origin[1], a.origin[2]);
+    Trav r;
+    LaneStack<int> stk;
+    stk.lds = (TPT_LDS int*)lds + tid;
+    stk.nlds = kAovLdsSlots;
+    uint32_t c_ovf = 0, c_leaf = 0;
+    trav_begin(r, ro, rd, TM_CLOSEST, a.boxes_finite != 0, a.emit_root, a.cull_eps, false);   // the camera: no surface
+    trav_lane<true>(r, a, stk, c_ovf);
+    if (a.n_sliver_groups > 0) sliver_pass(r, a, c_leaf);
+    // the render's grazing-hit rule (trace.hip "Culling"): traced again on the uncull'd binary path
+    if (r.fin && r.fid >= 0 && r.mode == TM_CLOSEST && a.graze &&
+        grazing(Surf{a.shade[3 * r.fid + 1].w, a.shade[3 * r.fid + 2].w}, r.d)) {
+        trav_begin(r, ro, rd, r.mode, a.boxes_finite != 0, a.emit_root, a.cull_eps, true);
+        trav_lane<true>(r, a, stk, c_ovf);
+    }
+    const size_t off = (size_t)x + (size_t)y * (size_t)a.width;
+    V3 alb = v3(1.0f, 1.0f, 1.0f), nrm = v3(0.0f, 0.0f, 0.0f);   // miss: demodulation leaves the environment alone
+    float depth = 0.0f;
+    int mtl = -1;
+    if (r.fid >= 0) {   // hit prelude (path_tracer.cu:364-374)
+        const float4* sh = a.shade + 3 * r.fid;
+        const float4 s0 = sh[0], s1 = sh[1], s2 = sh[2];
+        const float w = 1.0f - r.u - r.v;
+        nrm = normalize(((w * v3(s0.x, s0.y, s0.z)) + (r.u * v3(s1.x, s1.y, s1.z))) + (r.v * v3(s2.x, s2.y, s2.z)));
+        mtl = __float_as_int(s0.w);
+        const float4 m0 = a.mtl[2 * mtl];
+        alb = v3(m0.x, m0.y, m0.z);
+        depth = r.t;
+    }
+    if (o.albedo) {
+        o.albedo[3 * off] = alb.x;
+        o.albedo[3 * off + 1] = alb.y;
+        o.albedo[3 * off + 2] = alb.z;
+    }
+    if (o.normal) {
+        o.normal[3 * off] = nrm.x;
+        o.normal[3 * off + 1] = nrm.y;
+        o.normal[3 * off + 2] = nrm.z;
+    }
+    if (o.depth) o.depth[off] = depth;
+    if (o.face) o.face[off] = r.fid;
+    if (o.material) o.material[off] = mtl;
+}
+
+hipError_t launch_aov(const TraceArgs& a, const AovArgs& o, hipStream_t s) {
+    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+    const size_t lds = (size_t)kAovLdsSlots * 256 * sizeof(int);
+    hipLaunchKernelGGL(k_aov, grid, dim3(256), lds, s, a, o);
+    return hipGetLastError();
+}
+
+// ---- the a-trous filter (DESIGN.md section 5 "Post-pass" holds the definition the tests pin) ----
+
+constexpr float kAlbedoFloor = 1e-3f;   // demodulation divides by max(albedo, this)
+
+__global__ __launch_bounds__(256) void k_dn_pack(DenoiseArgs a) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.npix) return;
+    float r = a.radiance_in[3 * p], g = a.radiance_in[3 * p + 1], b = a.radiance_in[3 * p + 2];
+    if (a.demodulate) {
+        r = r / fmaxf(a.albedo[3 * p], kAlbedoFloor);
+        g = g / fmaxf(a.albedo[3 * p + 1], kAlbedoFloor);
+        b = b / fmaxf(a.albedo[3 * p + 2], kAlbedoFloor);
+    }
+    a.color0[p] = make_float4(r, g, b, 0.0f);
+    a.guide[p] = make_float4(a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2], a.depth[p]);
+}
+
+// One pixel's accumulation over its taps.  The weighted mean is kept as
+// c(p) + sum w (c(q) - c(p)) / sum w: the same value as sum w c(q) / sum w, and a
+// constant image stays constant exactly.  The three edge-stopping exponentials are
+// one (their arguments add); exp is the hardware's exp2 of a scaled argument.
+struct Taps {
+    float4 cp, gp;
+    float kz;   // 1 / (sigma_z^2 max(z(p)^2, 1e-12))
+    float sw, ar, ag, ab;
+    __device__ __forceinline__ void begin(float4 c, float4 g, float sz2) {
+        cp = c;
+        gp = g;
+        kz = fminf(1.0f / (sz2 * fmaxf(g.w * g.w, 1e-12f)), kRealMax);   // (finite: the centre tap's 0 * kz is 0)
+        sw = 0.0f;
+        ar = ag = ab = 0.0f;
+    }
+    __device__ __forceinline__ void tap(float hh, float4 cq, float4 gq, float inv_sc2, float inv_sn2) {
+        const float dr = cq.x - cp.x, dg = cq.y - cp.y, db = cq.z - cp.z;
+        const float nx = gq.x - gp.x, ny = gq.y - gp.y, nz = gq.z - gp.z, dz = gq.w - gp.w;
+        const float e = (dr * dr + dg * dg + db * db) * inv_sc2 + (nx * nx + ny * ny + nz * nz) * inv_sn2 +
+                        (dz * dz) * kz;
+        const float w = hh * __expf(-e);
+        sw += w;
+        ar += w * dr;
+        ag += w * dg;
+        ab += w * db;
+    }
+    __device__ __forceinline__ float4 end() const {
+        const float inv = 1.0f / sw;   // the centre tap: sw >= h(0)^2 > 0
+        return make_float4(cp.x + ar * inv, cp.y + ag * inv, cp.z + ab * inv, 0.0f);
+    }
+};
+
+__device__ __forceinline__ float atrous_h(int d) {   // [1/16, 1/4, 3/8, 1/4, 1/16]
+    return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f);
+}
+
+// Direct version: every tap from global memory (L1 / L2).  Block (64, 4).
+__global__ __launch_bounds__(256) void k_atrous(AtrousArgs a) {
+    const int x = (int)blockIdx.x * 64 + (int)threadIdx.x, y = (int)blockIdx.y * 4 + (int)threadIdx.y;
+    if (x >= a.width || y >= a.height) return;
+    const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
+    Taps t;
+    t.begin(a.src[p], a.guide[p], a.sz2);
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = y + dy * a.step;
+        if (qy < 0 || qy >= a.height) continue;
+        const size_t row = (size_t)qy * (size_t)a.width;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * a.step;
+            if (qx < 0 || qx >= a.width) continue;
+            t.tap(atrous_h(dx) * atrous_h(dy), a.src[row + qx], a.guide[row + qx], a.inv_sc2, a.inv_sn2);
+        }
+    }
+    a.dst[p] = t.end();
+}
+
+// LDS version for steps 1 and 2: a 16x16 tile and its halo of 2 S pixels staged once
+// ((16 + 4 S)^2 pixels x 32 B: 12.5 KB at S = 1, 18 KB at S = 2), every tap an LDS
+// read.  The same taps in the same order as k_atrous: bit-identical output.
+template <int S>
+__global__ __launch_bounds__(256) void k_atrous_lds(AtrousArgs a) {
+    constexpr int T = 16 + 4 * S;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    TPT_LDS LdsF4* sc = (TPT_LDS LdsF4*)lds;
+    TPT_LDS LdsF4* sg = sc + T * T;
+    const int tid = threadIdx.x;
+    const int x0 = (int)blockIdx.x * 16 - 2 * S, y0 = (int)blockIdx.y * 16 - 2 * S;
+    for (int i = tid; i < T * T; i += 256) {
+        const int gx = x0 + i % T, gy = y0 + i / T;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g = c;
+        if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) {   // (outside the frame: never read as a tap)
+            const size_t q = (size_t)gy * (size_t)a.width + (size_t)gx;
+            c = a.src[q];
+            g = a.guide[q];
+        }
+        sc[i].x = c.x;
+        sc[i].y = c.y;
+        sc[i].z = c.z;
+        sc[i].w = c.w;
+        sg[i].x = g.x;
+        sg[i].y = g.y;
+        sg[i].z = g.z;
+        sg[i].w = g.w;
+    }
+    __syncthreads();
+    const int tx = tid & 15, ty = tid >> 4;
+    const int x = (int)blockIdx.x * 16 + tx, y = (int)blockIdx.y * 16 + ty;
+    if (x >= a.width || y >= a.height) return;
+    const int c0 = (ty + 2 * S) * T + tx + 2 * S;
+    Taps t;
+    t.begin(lds_f4(sc + c0), lds_f4(sg + c0), a.sz2);
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = y + dy * S;
+        if (qy < 0 || qy >= a.height) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * S;
+            if (qx < 0 || qx >= a.width) continue;
+            const int q = c0 + dy * S * T + dx * S;
+            t.tap(atrous_h(dx) * atrous_h(dy), lds_f4(sc + q), lds_f4(sg + q), a.inv_sc2, a.inv_sn2);
+        }
+    }
+    a.dst[(size_t)y * (size_t)a.width + (size_t)x] = t.end();
+}
+
+// Re-modulation, the radiance readout and copyToFB's conventions as k_resolve:
+// row 0 = top, B, G, R written, alpha untouched, truncating to_uchar.
+__global__ __launch_bounds__(256) void k_dn_resolve(DenoiseArgs a) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.npix) return;
+    const float4 c = a.color0[p];
+    float r = c.x, g = c.y, b = c.z;
+    if (a.demodulate) {
+        r = r * fmaxf(a.albedo[3 * p], kAlbedoFloor);
+        g = g * fmaxf(a.albedo[3 * p + 1], kAlbedoFloor);
+        b = b * fmaxf(a.albedo[3 * p + 2], kAlbedoFloor);
+    }
+    if (a.radiance_out) {
+        a.radiance_out[3 * p] = r;
+        a.radiance_out[3 * p + 1] = g;
+        a.radiance_out[3 * p + 2] = b;
+    }
+    if (a.bgra) {
+        const size_t y = p / (size_t)a.width, x = p - y * (size_t)a.width;
+        uint8_t* px = a.bgra + 4 * (((size_t)a.height - y - 1) * (size_t)a.width + x);
+        px[0] = to_uchar(b);
+        px[1] = to_uchar(g);
+        px[2] = to_uchar(r);
+    }
+}
+
+hipError_t launch_denoise_pack(const DenoiseArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_dn_pack, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_atrous(const AtrousArgs& a, bool use_lds, hipStream_t s) {
+    if (use_lds && (a.step == 1 || a.step == 2)) {
+        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+        const int T = 16 + 4 * a.step;
+        const size_t lds = (size_t)T * T * 32;
+        if (a.step == 1) hipLaunchKernelGGL(k_atrous_lds<1>, grid, dim3(256), lds, s, a);
+        else hipLaunchKernelGGL(k_atrous_lds<2>, grid, dim3(256), lds, s, a);
+    } else {
+        const dim3 grid((a.width + 63) / 64, (a.height + 3) / 4);
+        hipLaunchKernelGGL(k_atrous, grid, dim3(64, 4), 0, s, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_resolve(const DenoiseArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_dn_resolve, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace tpt

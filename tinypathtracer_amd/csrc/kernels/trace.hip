@@ -989,9 +989,6 @@ void k_trace(TraceArgs a) {
     }
 }
 
-// Spectrum::toUChar (material.h:74-81): truncating clamp to [0, 255]
-__device__ __forceinline__ uint8_t to_uchar(float c) { return (uint8_t)fclamp(c * 255.0f, 255.0f, 0.0f); }
-
 // copyToFB (path_tracer.cu:451-471) + the radiance readout (color / spp).
 __global__ void k_resolve(ResolveArgs a) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1028,34 +1025,6 @@ __global__ void k_resolve(ResolveArgs a) {
 //          (the probe adds nothing), -1 when no emitter was hit.
 // Modes 1-3 run the same visit / cull / leaf functions as k_trace.
 constexpr int kRaysLdsSlots = 48;   // LDS stack slots per lane in k_trace_rays; deeper ones private
-
-template <bool ORDERED>
-__device__ __forceinline__ void trav_lane(Trav& r, const TraceArgs& a, LaneStack<int>& stk, uint32_t& c_ovf) {
-    const int nint = a.n_faces - 1;
-    while (r.node >= 0) {
-        if (r.node < nint) {
-            int next;
-            if (ORDERED && r.fin) {
-                next = inner_visit4(r, a.inner4, nullptr, 0, stk, r.sp);
-            } else {
-                int deferred;
-                bool push;
-                inner_visit<ORDERED>(r, a.inner, next, push, deferred);
-                stk.put(r.sp, deferred);
-                r.sp += push ? 1 : 0;
-            }
-            if (r.sp > a.stack_depth) {
-                ++c_ovf;
-                r.sp = 0;
-                next = -1;
-            }
-            r.node = next >= 0 ? next : (r.sp == 0 ? -1 : stk.get(--r.sp));
-        } else {
-            const bool stop = leaf_test<ORDERED>(r, a.tri, r.node - nint, a.cull_eps);
-            r.node = (stop || r.sp == 0) ? -1 : stk.get(--r.sp);
-        }
-    }
-}
 
 __global__ __launch_bounds__(256) void k_trace_rays(TraceArgs a, uint32_t n, const float* __restrict__ o,
                                                     const float* __restrict__ d, const int32_t* __restrict__ ofid,

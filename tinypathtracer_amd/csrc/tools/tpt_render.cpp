@@ -5,7 +5,11 @@
 //
 //   tpt_render scene.gltf [--width W] [--height H] [--spp N] [--depth D]
 //              [--seed S] [--env equirect.jpg|.ppm|--sky] [--out prefix] [--device i]
-//              [--frames F [--progressive]]
+//              [--frames F [--progressive]] [--aov] [--denoise [iterations]]
+// --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
+// <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
+// a-trous filter of the written frame (tpt_denoise, the hosts' defaults; with
+// --progressive the written frame is the accumulated one).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -44,17 +48,38 @@ std::vector<uint8_t> procedural_sky(int w, int h) {
     return img;
 }
 
+void write_ppm(const std::string& path, const std::vector<uint8_t>& bgra, int W, int H) {
+    std::ofstream ppm(path, std::ios::binary);
+    ppm << "P6\n" << W << " " << H << "\n255\n";
+    for (size_t i = 0; i < (size_t)W * H; ++i) {   // BGRA -> RGB, rows already top-down
+        const char px[3] = {(char)bgra[4 * i + 2], (char)bgra[4 * i + 1], (char)bgra[4 * i]};
+        ppm.write(px, 3);
+    }
+}
+
+// PFM rows are bottom-up, like the radiance and the feature buffers; 3 channels "PF", 1 channel "Pf"
+void write_pfm(const std::string& path, const std::vector<float>& v, int W, int H, int channels) {
+    std::ofstream pfm(path, std::ios::binary);
+    pfm << (channels == 3 ? "PF" : "Pf") << "\n" << W << " " << H << "\n-1.0\n";
+    pfm.write((const char*)v.data(), (std::streamsize)(v.size() * sizeof(float)));
+}
+
+const char* kUsage =
+    "usage: %s scene.gltf [--width W] [--height H] [--spp N] [--depth D] [--seed S] "
+    "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]] "
+    "[--aov] [--denoise [iterations]]\n";
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s scene.gltf [--width W] [--height H] [--spp N] [--depth D] [--seed S] "
-                             "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]]\n", argv[0]);
+        std::fprintf(stderr, kUsage, argv[0]);
         return 2;
     }
     std::string scene_file = argv[1], env_file, out = "out";
     int W = 1920, H = 1080, spp = 64, depth = 8, device = 0, frames = 1;
-    bool progressive = false;
+    bool progressive = false, aov = false, denoise = false;
+    int dn_iterations = tpt::defaultDenoise().iterations;
     uint64_t seed = 0;
     bool sky = false;
     for (int i = 2; i < argc; ++i) {
@@ -74,6 +99,11 @@ int main(int argc, char** argv) {
         else if (a == "--device") device = std::stoi(next());
         else if (a == "--frames") frames = std::stoi(next());
         else if (a == "--progressive") progressive = true;
+        else if (a == "--aov") aov = true;
+        else if (a == "--denoise") {
+            denoise = true;   // an optional iteration count follows
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn_iterations = std::stoi(argv[++i]);
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     try {
@@ -85,16 +115,36 @@ int main(int argc, char** argv) {
             env = tpt::EnvLight(img.data(), 2048, 1024, device);
         }
         tpt::PathTracer pt(env, W, H, device);
-        tpt::Frame f = pt.render(scene_file, spp, seed, depth, frames, progressive);
-        std::ofstream ppm(out + ".ppm", std::ios::binary);
-        ppm << "P6\n" << W << " " << H << "\n255\n";
-        for (size_t i = 0; i < (size_t)W * H; ++i) {   // BGRA -> RGB, rows already top-down
-            const char px[3] = {(char)f.bgra[4 * i + 2], (char)f.bgra[4 * i + 1], (char)f.bgra[4 * i]};
-            ppm.write(px, 3);
+        // render(meshFile) (path_tracer.cu:556-579) spelled out, so the scene is still there for the post-pass
+        tpt::Scene scene(scene_file, "gltf");
+        tpt::DeviceScene d = scene.copySceneToDevice(device);
+        d.build();
+        tpt::Frame f;
+        f.width = W;
+        f.height = H;
+        f.bgra.assign((size_t)W * H * 4, 255);
+        f.radiance.assign((size_t)W * H * 3, 0.0f);
+        for (int i = 0; i < frames; ++i)
+            f.stats = pt.doTrace(d, scene.m_camera, f.bgra.data(), spp, seed, depth, f.radiance.data(), 1, 0,
+                                 progressive && i > 0);
+        write_ppm(out + ".ppm", f.bgra, W, H);
+        write_pfm(out + ".pfm", f.radiance, W, H, 3);
+        if (aov || denoise) {
+            tpt::AOV g = pt.renderAOV(d, scene.m_camera);
+            if (aov) {
+                write_pfm(out + "_albedo.pfm", g.albedo, W, H, 3);
+                write_pfm(out + "_normal.pfm", g.normal, W, H, 3);
+                write_pfm(out + "_depth.pfm", g.depth, W, H, 1);
+            }
+            if (denoise) {
+                std::vector<float> clean((size_t)W * H * 3);
+                std::vector<uint8_t> fb((size_t)W * H * 4, 255);
+                pt.denoise(d, f.radiance.data(), g.view(), clean.data(), fb.data(),
+                           tpt::defaultDenoise(dn_iterations));
+                write_pfm(out + "_denoised.pfm", clean, W, H, 3);
+                write_ppm(out + "_denoised.ppm", fb, W, H);
+            }
         }
-        std::ofstream pfm(out + ".pfm", std::ios::binary);   // PFM rows are bottom-up, like the radiance
-        pfm << "PF\n" << W << " " << H << "\n-1.0\n";
-        pfm.write((const char*)f.radiance.data(), (std::streamsize)(f.radiance.size() * sizeof(float)));
         const tpt_stats& s = f.stats;
         std::printf("{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %llu, \"rays\": %llu, "
                     "\"trace_ms\": %.3f, \"mrays_per_s\": %.1f, \"out\": \"%s.ppm\"}\n",
