@@ -352,6 +352,65 @@ tpt_status tpt_denoise(tpt_scene* scene, int32_t width, int32_t height, const fl
                        const tpt_aov* guides, const tpt_denoise_params* params, float* radiance_out,
                        uint8_t* bgra_out, tpt_denoise_stats* stats);
 
+/* Temporal reprojection and accumulation across frames (DESIGN.md section 5 "Post-pass").
+ * A history belongs to one frame size and to the scene it was created from, which
+ * supplies the device and the stream and need not be built; destroy the history
+ * before its scene.  It holds two sets of three float4 planes (accumulated colour +
+ * history length; normal + depth; luminance moments + material id), 96 B per pixel,
+ * and up to 56 B per pixel more to stage host buffers.  After tpt_history_create and
+ * after tpt_history_reset there is no state: the next tpt_temporal starts over. */
+typedef struct tpt_history tpt_history;
+tpt_status tpt_history_create(tpt_scene* scene, int32_t width, int32_t height, tpt_history** out);
+tpt_status tpt_history_reset(tpt_history* h);
+void tpt_history_destroy(tpt_history* h);
+
+#define TPT_TEMPORAL_DEMODULATE 0x1   /* accumulate radiance / max(albedo, 1e-3); multiply the current albedo back */
+#define TPT_TEMPORAL_TILES      0x2   /* A/B: lanes in 16x16 tiles instead of 64-pixel row segments
+                                         (bit-identical output) */
+
+typedef struct {
+    float   alpha;         /* (0, 1]: least weight of the new frame */
+    float   depth_tol;     /* > 0, relative */
+    float   normal_min;    /* [-1, 1]: least n'(q) . n(p) */
+    int32_t max_history;   /* 1..65536 */
+    int32_t flags;         /* TPT_TEMPORAL_* */
+} tpt_temporal_params;
+
+typedef struct {
+    double   kernel_ms;    /* the kernel's duration (HIP events) */
+    uint64_t reprojected;  /* pixels that found history */
+} tpt_temporal_stats;
+
+/* One frame through the history.  Each pixel's first hit (a miss: its direction, a
+ * point at infinity) is projected into the previous call's camera; the four bilinear
+ * taps there are kept where the previous frame saw the same material and, on a hit,
+ * a depth within depth_tol (relative) of the distance to the previous origin and a
+ * normal with n' . n >= normal_min.  With valid weights summing to at least 1/16 the
+ * pixel is reprojected: N = min(N' + 1, max_history), a = max(alpha, 1 / N), and the
+ * colour and the luminance moments move a of the way from the weighted history to
+ * this frame.  Otherwise it is disoccluded: N = 1 and the output is the input bit
+ * for bit.  The new state and `camera` then replace the old.  Only the camera may
+ * move between frames, not the scene.
+ *   guides: normal, depth and material (tpt_render_aov) are required, albedo only with
+ *     TPT_TEMPORAL_DEMODULATE; face is ignored.
+ *   radiance_in / radiance_out: W*H*3 floats, row 0 = bottom; may be the same pointer.
+ *   variance_out: nullable, W*H: max(M2 - M1^2, 0) of the accumulated luminance
+ *     (of the demodulated colour under TPT_TEMPORAL_DEMODULATE).
+ *   history_len_out: nullable, W*H: N.
+ *   bgra_out: nullable, as tpt_denoise's.  At least one of radiance_out and bgra_out.
+ * Inputs and outputs may be host or device memory (tpt_render's stream rule for
+ * device memory); all work is complete when the call returns.  Deterministic: no
+ * floating-point atomics.  Non-finite input radiance is the caller's problem: it
+ * stays in the history until the pixel is disoccluded or the history is reset.
+ * TPT_ERR_INVALID_ARG (nothing is written and the history is left as it was): null
+ * h / camera / radiance_in / guides / params, a missing required guide, alpha outside
+ * (0, 1], depth_tol not > 0, normal_min outside [-1, 1], max_history outside
+ * 1..65536, an unknown flag, radiance_out and bgra_out both null. */
+tpt_status tpt_temporal(tpt_history* h, const tpt_camera* camera, const float* radiance_in,
+                        const tpt_aov* guides, const tpt_temporal_params* params,
+                        float* radiance_out, float* variance_out, float* history_len_out,
+                        uint8_t* bgra_out, tpt_temporal_stats* stats);
+
 /* Introspection for tests: copy back the built BVH in the reference node
  * layout (bvh.cuh:52-58, 36 B/node, 2F-1 nodes) and the sorted Morton keys. */
 tpt_status tpt_scene_read_bvh(tpt_scene* scene, void* nodes36, int64_t* keys);

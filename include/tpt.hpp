@@ -168,6 +168,36 @@ inline tpt_denoise_params defaultDenoise(int iterations = 5) {
     return p;
 }
 
+// The hosts' temporal-accumulation defaults (DESIGN.md section 5 "Post-pass")
+inline tpt_temporal_params defaultTemporal() {
+    tpt_temporal_params p{};
+    p.alpha = 0.1f;
+    p.depth_tol = 0.1f;
+    p.normal_min = 0.9f;
+    p.max_history = 32;
+    p.flags = TPT_TEMPORAL_DEMODULATE;
+    return p;
+}
+
+// tpt_temporal's state across frames (tpt_history).  Declared after the
+// DeviceScene it was created from, so that it is destroyed first.
+class History {
+public:
+    History(DeviceScene& scene, int width, int height) {
+        tpt_history* h = nullptr;
+        check(tpt_history_create(scene.handle(), width, height, &h));
+        h_.reset(h);
+    }
+    void reset() { check(tpt_history_reset(h_.get())); }   // the next temporal() starts over
+    tpt_history* handle() const { return h_.get(); }
+
+private:
+    struct Free {
+        void operator()(tpt_history* h) const { tpt_history_destroy(h); }
+    };
+    std::unique_ptr<tpt_history, Free> h_;
+};
+
 class PathTracer {
 public:
     PathTracer() : PathTracer(1920, 1080) {}   // VkEngine default extent (vkEngine.h:24)
@@ -257,6 +287,21 @@ public:
         tpt_denoise_stats st{};
         check(tpt_denoise(scene.handle(), m_width, m_height, radiance_in, &guides, &params, radiance_out, framebuffer,
                           &st));
+        return st;
+    }
+
+    // Temporal reprojection and accumulation (tpt_temporal): this frame's radiance
+    // and feature buffers through `history` (of this tracer's frame size), which
+    // then holds the frame and `camera`.  radiance_out may be radiance_in; variance
+    // and history_len (W*H each) and framebuffer are nullable.  Pointers are host or
+    // device memory.
+    tpt_temporal_stats temporal(History& history, const Camera& camera, const float* radiance_in,
+                                const tpt_aov& guides, float* radiance_out, float* variance = nullptr,
+                                float* history_len = nullptr, uint8_t* framebuffer = nullptr,
+                                const tpt_temporal_params& params = defaultTemporal()) {
+        tpt_temporal_stats st{};
+        check(tpt_temporal(history.handle(), &camera.c, radiance_in, &guides, &params, radiance_out, variance,
+                           history_len, framebuffer, &st));
         return st;
     }
 

@@ -1,0 +1,142 @@
+"""CPU reference for the temporal pass (tests/test_gpu_temporal.py,
+tests/test_temporal_api.py): a float64 numpy restatement of tpt_temporal as DESIGN.md
+section 5 "Post-pass" defines it, the synthetic three-patch scene whose feature
+buffers the tests build analytically, and the cameras they move between.
+
+The rays are post_ref.pixel_centre_rays', so they are the kernel's own float32 rays;
+everything after them is float64.  Where a float32 and a float64 evaluation could
+fall on different sides of one of the definition's thresholds the pixel is marked
+undecidable and left out of comparisons (temporal_ref's `decidable` mask); the
+tests assert that such pixels are at most 1 % of the frame."""
+import numpy as np
+
+from tests import post_ref as R
+
+F = np.float32
+SNAP = 1.0 / 1024.0
+MIN_WSUM = 1.0 / 16.0
+ALBEDO_FLOOR = 1e-3
+LUMA = np.array([0.2126, 0.7152, 0.0722])
+
+
+def sensor(vfov, aspect):
+    """sensor_w, sensor_h, half_sw, half_sh as the library computes them (float32)."""
+    tan_half = F(np.tan(np.float64(F(vfov) * F(0.5))))
+    sensor_h = F(2.0) * tan_half
+    sensor_w = F(aspect) * sensor_h
+    return sensor_w, sensor_h, F(0.5) * sensor_w, F(0.5) * sensor_h
+
+
+def camera(yaw_deg=0.0, translate=(0.0, 0.0, 0.0), vfov=0.8, aspect=1.0):
+    """A camera dict: the identity turned by yaw_deg about +y, then moved by
+    `translate`.  c2w is 16 float32 values, column-major."""
+    t = np.deg2rad(yaw_deg)
+    m = np.eye(4)
+    m[0, 0], m[0, 2], m[2, 0], m[2, 2] = np.cos(t), np.sin(t), -np.sin(t), np.cos(t)
+    m[:3, 3] = translate
+    return {"c2w": m.T.reshape(16).astype(F), "vfov": float(vfov), "aspect": float(aspect)}
+
+
+def synthetic_guides(cam, W, H):
+    """First hits of the pixel-centre rays against three world-space patches, closest
+    first; everything else is a miss (normal 0, depth 0, material -1).
+      far wall:    z = -4, normal +z, y < 1.0, material 0
+      near strip:  z = -2.5, normal +z, -0.4 < x < 0.5, y < 0.6, material 1
+      tilted wall: through (-1.2, 0, -4), normal (0.6, 0, 0.8), x < -1.2, y < 1.0, material 2"""
+    o32, d32 = R.pixel_centre_rays(cam["c2w"], cam["vfov"], cam["aspect"], W, H)
+    o, d = o32.astype(np.float64), d32.astype(np.float64)
+    patches = [
+        ((0.0, 0.0, -4.0), (0.0, 0.0, 1.0), lambda X: X[..., 1] < 1.0, 0),
+        ((0.0, 0.0, -2.5), (0.0, 0.0, 1.0), lambda X: (X[..., 0] > -0.4) & (X[..., 0] < 0.5) & (X[..., 1] < 0.6), 1),
+        ((-1.2, 0.0, -4.0), (0.6, 0.0, 0.8), lambda X: (X[..., 0] < -1.2) & (X[..., 1] < 1.0), 2),
+    ]
+    best = np.full((H, W), np.inf)
+    normal = np.zeros((H, W, 3), F)
+    material = np.full((H, W), -1, np.int32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for point, nrm, inside, mtl in patches:
+            nrm = np.asarray(nrm)
+            t = ((np.asarray(point) - o) @ nrm) / (d @ nrm)
+            X = o + t[..., None] * d
+            ok = np.isfinite(t) & (t > 0) & inside(X) & (t < best)
+            best = np.where(ok, t, best)
+            normal[ok] = nrm.astype(F)
+            material[ok] = mtl
+    depth = np.where(material >= 0, best, 0.0).astype(F)
+    return {"normal": normal, "depth": depth, "material": material}
+
+
+def temporal_ref(state, cam, radiance, aov, alpha, depth_tol, normal_min, max_history, demodulate):
+    """One call of the definition.  state: None (after create / reset) or the dict a
+    previous call returned.  Returns a dict: `out`, `variance`, `history_len`
+    (float64), `reprojected` (bool mask), `decidable` (bool mask) and the new state
+    under `state`."""
+    n = np.asarray(aov["normal"], np.float64)
+    z = np.asarray(aov["depth"], np.float64)
+    m = np.asarray(aov["material"], np.int64)
+    H, W = z.shape
+    a = np.maximum(np.asarray(aov["albedo"], np.float64), ALBEDO_FLOOR) if demodulate else 1.0
+    c = np.asarray(radiance, np.float64) / a
+    L = c @ LUMA
+    hit = m >= 0
+    reproj = np.zeros((H, W), bool)
+    decidable = np.ones((H, W), bool)
+    hC, hN, hM1, hM2 = np.zeros((H, W, 3)), np.zeros((H, W)), np.zeros((H, W)), np.zeros((H, W))
+    if state is not None:
+        o32, d32 = R.pixel_centre_rays(cam["c2w"], cam["vfov"], cam["aspect"], W, H)
+        o, d = o32.astype(np.float64), d32.astype(np.float64)
+        X = o + z[..., None] * d
+        pc = state["cam"]
+        pm = np.asarray(pc["c2w"], F).astype(np.float64).reshape(4, 4).T
+        inv = np.linalg.inv(pm).astype(F).astype(np.float64)          # double, rounded to float32
+        po = pm[:3, 3]
+        local = np.where(hit[..., None], X @ inv[:3, :3].T + inv[:3, 3], d @ inv[:3, :3].T)
+        dist = np.linalg.norm(X - po, axis=-1)
+        front = local[..., 2] < 0
+        sw, sh, hsw, hsh = (np.float64(v) for v in sensor(pc["vfov"], pc["aspect"]))
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            s = -1.0 / local[..., 2]
+            fx = (local[..., 0] * s + hsw) / sw * W - 0.5
+            fy = (local[..., 1] * s + hsh) / sh * H - 0.5
+        fx = np.where(front & np.isfinite(fx), fx, -10.0)               # behind: no tap; kept finite
+        fy = np.where(front & np.isfinite(fy), fy, -10.0)
+        fx, fy = np.clip(fx, -10.0, W + 10.0), np.clip(fy, -10.0, H + 10.0)
+        for f in (fx, fy):
+            off = np.abs(f - np.round(f))
+            decidable &= ~(front & (np.abs(off - SNAP) < 1e-4))
+        fx = np.where(np.abs(fx - np.round(fx)) < SNAP, np.round(fx), fx)
+        fy = np.where(np.abs(fy - np.round(fy)) < SNAP, np.round(fy), fy)
+        x0, y0 = np.floor(fx), np.floor(fy)
+        tx, ty = fx - x0, fy - y0
+        wsum = np.zeros((H, W))
+        for j in (0, 1):
+            for i in (0, 1):
+                w = (tx if i else 1.0 - tx) * (ty if j else 1.0 - ty)
+                qx, qy = (x0 + i).astype(np.int64), (y0 + j).astype(np.int64)
+                inside = (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+                qxc, qyc = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
+                match = front & (w > 0) & inside & (state["m"][qyc, qxc] == m)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    rel = np.abs(state["z"][qyc, qxc] - dist) / dist
+                ndot = (state["n"][qyc, qxc] * n).sum(-1)
+                surf = match & hit
+                decidable &= ~(surf & ((np.abs(rel - depth_tol) < 1e-3) | (np.abs(ndot - normal_min) < 1e-3)))
+                valid = match & (~hit | ((rel <= depth_tol) & (ndot >= normal_min)))
+                wv = np.where(valid, w, 0.0)
+                wsum += wv
+                hC += wv[..., None] * state["C"][qyc, qxc]
+                hN += wv * state["N"][qyc, qxc]
+                hM1 += wv * state["M1"][qyc, qxc]
+                hM2 += wv * state["M2"][qyc, qxc]
+        decidable &= ~(np.abs(wsum - MIN_WSUM) < 1e-3)
+        reproj = wsum >= MIN_WSUM
+        ws = np.where(reproj, wsum, 1.0)
+        hC, hN, hM1, hM2 = hC / ws[..., None], hN / ws, hM1 / ws, hM2 / ws
+    N = np.where(reproj, np.minimum(hN + 1.0, float(max_history)), 1.0)
+    k = np.maximum(alpha, 1.0 / N)
+    C = np.where(reproj[..., None], hC + k[..., None] * (c - hC), c)
+    M1 = np.where(reproj, hM1 + k * (L - hM1), L)
+    M2 = np.where(reproj, hM2 + k * (L * L - hM2), L * L)
+    new = {"cam": cam, "C": C, "N": N, "M1": M1, "M2": M2, "n": n, "z": z, "m": m}
+    return {"out": C * a, "variance": np.maximum(M2 - M1 * M1, 0.0), "history_len": N, "reprojected": reproj,
+            "decidable": decidable, "state": new}

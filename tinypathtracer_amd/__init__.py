@@ -23,7 +23,8 @@ from . import _lib
 from ._lib import TPTError, build_identity, check, lib
 
 __all__ = ["Camera", "Scene", "DeviceScene", "BVH", "EnvLight", "PathTracer", "Frame", "TPTError",
-           "procedural_sky", "version", "device_count", "build_identity", "NODE_DTYPE", "DENOISE_DEFAULTS"]
+           "procedural_sky", "version", "device_count", "build_identity", "NODE_DTYPE", "DENOISE_DEFAULTS",
+           "History", "TEMPORAL_DEFAULTS"]
 
 # BVHNode (include/bvh.cuh:52-58): parent, info{left,right | fid,placeHolder}, box
 NODE_DTYPE = np.dtype([("parent", "<u4"), ("a", "<i4"), ("b", "<i4"), ("bmin", "<f4", 3), ("bmax", "<f4", 3)])
@@ -57,6 +58,16 @@ class Camera:
 
     def getNearPlane(self):
         return self.znear
+
+    def yawed(self, deg: float) -> "Camera":
+        """This camera turned by `deg` degrees about its own origin and up axis
+        (c2w * R_y, as tpt_render --yaw does per frame)."""
+        m = np.asarray(self.c2w, np.float32).reshape(4, 4).astype(np.float64)   # rows = columns of c2w
+        t = np.deg2rad(float(deg))
+        out = m.copy()
+        out[0] = np.cos(t) * m[0] - np.sin(t) * m[2]
+        out[2] = np.sin(t) * m[0] + np.cos(t) * m[2]
+        return Camera(out.astype(np.float32).reshape(16), self.vfov, self.aspect, self.znear)
 
     def to_c(self) -> _lib.Camera:
         c = _lib.Camera()
@@ -402,6 +413,40 @@ def _check_plane(name, buf, width, height):
                          f"got {n} of {have}")
 
 
+# Temporal-accumulation defaults of the hosts and the CLI (tpt.hpp defaultTemporal)
+TEMPORAL_DEFAULTS = {"alpha": 0.1, "depth_tol": 0.1, "normal_min": 0.9, "max_history": 32, "demodulate": True}
+_PLANES.update(variance=(1, "float32"), history_len=(1, "float32"))
+
+
+class History:
+    """tpt_temporal's state across frames (tpt_history): the accumulated colour, the
+    history length, the luminance moments and the feature buffers of the previous
+    frame, for one frame size.  d_scene supplies the device and the stream; close the
+    history before it."""
+
+    def __init__(self, d_scene: DeviceScene, width: int, height: int):
+        self.width, self.height = int(width), int(height)
+        self.handle = C.c_void_p()
+        check(lib().tpt_history_create(d_scene.handle, self.width, self.height, C.byref(self.handle)))
+        self._scene = d_scene                   # kept alive: the history is destroyed first
+
+    def reset(self):
+        """The next temporal() starts over: every pixel disoccluded."""
+        check(lib().tpt_history_reset(self.handle))
+        return self
+
+    def close(self):
+        if self.handle:
+            lib().tpt_history_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PathTracer:
     """PathTracer (include/path_tracer.h:16-35), headless.
 
@@ -554,6 +599,48 @@ class PathTracer:
         st = _lib.DenoiseStats()
         check(lib().tpt_denoise(d_scene.handle, W, H, _addr(radiance), C.byref(g), C.byref(p), _addr(out),
                                 _addr(framebuffer), C.byref(st)))
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out
+
+    def temporal(self, history: History, camera: Camera, radiance, aov, *,
+                 alpha: float = TEMPORAL_DEFAULTS["alpha"], depth_tol: float = TEMPORAL_DEFAULTS["depth_tol"],
+                 normal_min: float = TEMPORAL_DEFAULTS["normal_min"],
+                 max_history: int = TEMPORAL_DEFAULTS["max_history"],
+                 demodulate: bool = TEMPORAL_DEFAULTS["demodulate"], out=None, variance=None, history_len=None,
+                 framebuffer=None, flags: int = 0, stats=None):
+        """Temporal reprojection and accumulation (tpt_temporal, DESIGN.md section 5
+        "Post-pass"): this frame's `radiance` [H, W, 3] and its feature buffers
+        aov["normal"], aov["depth"], aov["material"] (and aov["albedo"] with
+        demodulate) rendered from `camera`, blended with what `history` holds of the
+        previous frames where the previous frame saw the same surface.  out: the
+        accumulated radiance's buffer (may be `radiance` itself; None: a new numpy
+        array); variance / history_len: optional [H, W] float32 buffers for the
+        luminance variance and the history length; framebuffer: optional [H, W, 4]
+        uint8 as doTrace writes it.  Buffers are numpy arrays or torch CUDA tensors.
+        Returns `out`; stats: a dict that receives kernel_ms and reprojected."""
+        W, H = self.m_width, self.m_height
+        if (history.width, history.height) != (W, H):
+            raise ValueError(f"the history is {history.width} x {history.height}, the frame {W} x {H}")
+        _check_plane("radiance", radiance, W, H)
+        g = _lib.Aov()
+        for k in ("albedo", "normal", "depth", "material") if demodulate else ("normal", "depth", "material"):
+            buf = aov.get(k)
+            if buf is not None:
+                _check_plane(k, buf, W, H)
+                setattr(g, k, _addr(buf))
+        if out is None:
+            out = np.zeros((H, W, 3), np.float32)
+        _check_plane("radiance", out, W, H)
+        for name, buf in (("variance", variance), ("history_len", history_len), ("framebuffer", framebuffer)):
+            if buf is not None:
+                _check_plane(name, buf, W, H)
+        p = _lib.TemporalParams(float(alpha), float(depth_tol), float(normal_min), int(max_history),
+                                int(flags) | (_lib.TEMPORAL_DEMODULATE if demodulate else 0))
+        st = _lib.TemporalStats()
+        cam = camera.to_c()
+        check(lib().tpt_temporal(history.handle, C.byref(cam), _addr(radiance), C.byref(g), C.byref(p), _addr(out),
+                                 _addr(variance), _addr(history_len), _addr(framebuffer), C.byref(st)))
         if stats is not None:
             stats.update(st.as_dict())
         return out

@@ -24,6 +24,8 @@ FLAG_FAST = 0x40
 DESC_DELTALIGHT_LAYOUT = 0x1
 DENOISE_DEMODULATE = 0x1
 DENOISE_DIRECT = 0x2
+TEMPORAL_DEMODULATE = 0x1
+TEMPORAL_TILES = 0x2
 
 
 class Material(C.Structure):
@@ -97,6 +99,18 @@ class DenoiseStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float),
+                ("max_history", C.c_int32), ("flags", C.c_int32)]
+
+
+class TemporalStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("reprojected", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # (name, restype, argtypes) -- every symbol include/tpt.h declares
 SIGNATURES = [
     ("tpt_version", C.c_char_p, []),
@@ -122,6 +136,12 @@ SIGNATURES = [
                                  C.POINTER(C.c_double)]),
     ("tpt_denoise", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Aov),
                               C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.POINTER(DenoiseStats)]),
+    ("tpt_history_create", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    ("tpt_history_reset", C.c_int, [C.c_void_p]),
+    ("tpt_history_destroy", None, [C.c_void_p]),
+    ("tpt_temporal", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(Aov),
+                               C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.POINTER(TemporalStats)]),
     ("tpt_scene_read_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_scene_read_world", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_debug_rng_init", C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),

@@ -293,6 +293,46 @@ hipError_t launch_denoise_pack(const DenoiseArgs& a, hipStream_t s);
 hipError_t launch_atrous(const AtrousArgs& a, bool use_lds, hipStream_t s);
 hipError_t launch_denoise_resolve(const DenoiseArgs& a, hipStream_t s);
 
+// post.hip: temporal reprojection and accumulation (tpt_temporal; DESIGN.md section 5
+// "Post-pass").  The state is three float4 planes per pixel, in two sets that ping-pong:
+//   plane 0 = (accumulated colour rgb, history length N)
+//   plane 1 = (normal xyz, depth)
+//   plane 2 = (luminance moments M1, M2, bits(material id), 0)
+struct TemporalArgs {
+    // the current camera, as TraceArgs holds it (k_aov's pixel-centre ray)
+    float c2w[16];
+    float origin[3];
+    float sensor_w, sensor_h, half_sw, half_sh;
+    float inv_w, inv_h;
+    // the previous call's camera: inverse of its c2w (column-major; double, rounded to
+    // float), its origin and sensor
+    float prev_inv[16];
+    float prev_origin[3];
+    float prev_sensor_w, prev_sensor_h, prev_half_sw, prev_half_sh;
+    int32_t has_prev;                    // 0: no state (after create / reset): every pixel disoccluded
+    int32_t width, height;
+    int32_t demodulate;
+    int32_t tiles;                       // 1: 16x16 tiles (8x8 per wave) instead of 64-pixel row segments
+    float alpha, depth_tol, normal_min, max_history;
+    // this frame (device pointers, row 0 = bottom)
+    const float* radiance_in;            // W*H*3
+    const float* albedo;                 // W*H*3 (read when demodulate)
+    const float* normal;                 // W*H*3
+    const float* depth;                  // W*H
+    const int32_t* material;             // W*H
+    const float4* prev[3];               // the previous state (read, gathered)
+    float4* next[3];                     // the new state (written at the lane's own pixel)
+    float* radiance_out;                 // nullable, W*H*3; may be radiance_in
+    float* variance_out;                 // nullable, W*H
+    float* history_out;                  // nullable, W*H
+    uint8_t* bgra;                       // nullable, W*H*4, row 0 = top, alpha untouched
+    unsigned long long* reprojected;     // kTemporalSlots counters, kTemporalSlotStride words apart (zeroed by the
+                                         //   caller): their sum = pixels that found history
+};
+constexpr int kTemporalSlots = 256;
+constexpr int kTemporalSlotStride = 16;  // 128 B: one counter per cache line
+hipError_t launch_temporal(const TemporalArgs& a, hipStream_t s);
+
 }  // namespace tpt
 
 // The tolerance-mode build of trace.hip (TPT_FLAG_FAST; Makefile trace_fast.hip.o):

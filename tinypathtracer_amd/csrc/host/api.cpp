@@ -477,6 +477,68 @@ struct tpt_scene {
     }
 };
 
+constexpr size_t kCountWords = (size_t)tpt::kTemporalSlots * tpt::kTemporalSlotStride;
+
+// tpt_temporal's state (post.hip k_temporal): two sets of three float4 planes that
+// ping-pong, the previous call's camera, device staging of host buffers.
+struct tpt_history {
+    tpt_scene* scene = nullptr;             // the stream; outlives the history's last tpt_temporal
+    int device = 0;
+    int32_t width = 0, height = 0;
+    DevBuf<float4> state[2][3];
+    int cur = 0;                            // the set the last call wrote
+    bool valid = false;                     // false after create / reset: no state
+    float prev_inv[16] = {};                // inverse of the previous c2w, column-major
+    float prev_origin[3] = {};
+    float prev_sensor[4] = {};              // sensor_w, sensor_h, half_sw, half_sh
+    DevBuf<float> st_rad, st_f3[2], st_depth, st_var, st_len;
+    DevBuf<int32_t> st_mtl;
+    DevBuf<uint8_t> st_bgra;
+    DevBuf<unsigned long long> count;       // the reprojected-pixel counters (TemporalArgs::reprojected)
+    HostPinned<unsigned long long> h_count;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+
+    ~tpt_history() {
+        DeviceGuard g(device);
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+namespace {
+
+// Inverse of a column-major 4x4 matrix by Gauss-Jordan elimination with partial
+// pivoting in double, rounded to float.  false: singular.
+bool invert4(const float* m, float* out) {
+    double a[4][8];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            a[i][j] = (double)m[4 * j + i];
+            a[i][4 + j] = i == j ? 1.0 : 0.0;
+        }
+    for (int c = 0; c < 4; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 4; ++r)
+            if (std::fabs(a[r][c]) > std::fabs(a[piv][c])) piv = r;
+        if (!(std::fabs(a[piv][c]) > 0.0)) return false;
+        if (piv != c)
+            for (int j = 0; j < 8; ++j) std::swap(a[c][j], a[piv][j]);
+        const double d = 1.0 / a[c][c];
+        for (int j = 0; j < 8; ++j) a[c][j] *= d;
+        for (int r = 0; r < 4; ++r) {
+            if (r == c) continue;
+            const double f = a[r][c];
+            if (f != 0.0)
+                for (int j = 0; j < 8; ++j) a[r][j] -= f * a[c][j];
+        }
+    }
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) out[4 * j + i] = (float)a[i][4 + j];
+    return true;
+}
+
+}  // namespace
+
 extern "C" {
 
 const char* tpt_version(void) { return "tpt-mi355x 0.1 (gfx950)"; }
@@ -1882,6 +1944,189 @@ tpt_status tpt_denoise(tpt_scene* s, int32_t W, int32_t H, const float* radiance
         stats->filter_ms = ms;
         HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
         stats->resolve_ms = ms;
+    }
+    return TPT_OK;
+}
+
+// Temporal reprojection and accumulation (post.hip k_temporal; DESIGN.md section 5
+// "Post-pass").  The handle keeps the two sets of state planes, the previous call's
+// camera and the device staging of host buffers.
+tpt_status tpt_history_create(tpt_scene* s, int32_t W, int32_t H, tpt_history** out) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (!out) return fail(TPT_ERR_INVALID_ARG, "null out");
+    if (W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size");
+    DeviceGuard g(s->device);
+    std::unique_ptr<tpt_history> h(new tpt_history);
+    h->scene = s;
+    h->device = s->device;
+    h->width = W;
+    h->height = H;
+    const size_t npix = (size_t)W * (size_t)H;
+    for (auto& set : h->state)
+        for (auto& plane : set) HIP_OR_FAIL(plane.alloc(npix));
+    HIP_OR_FAIL(h->count.alloc(kCountWords));
+    HIP_OR_FAIL(h->h_count.alloc(kCountWords));
+    for (auto& e : h->ev) HIP_OR_FAIL(hipEventCreate(&e));
+    *out = h.release();
+    return TPT_OK;
+}
+
+tpt_status tpt_history_reset(tpt_history* h) {
+    if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
+    h->valid = false;
+    return TPT_OK;
+}
+
+void tpt_history_destroy(tpt_history* h) { delete h; }
+
+tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radiance_in, const tpt_aov* guides,
+                        const tpt_temporal_params* p, float* radiance_out, float* variance_out,
+                        float* history_len_out, uint8_t* bgra_out, tpt_temporal_stats* stats) {
+    if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
+    if (!cam) return fail(TPT_ERR_INVALID_ARG, "null camera");
+    if (!radiance_in) return fail(TPT_ERR_INVALID_ARG, "null radiance_in");
+    if (!guides) return fail(TPT_ERR_INVALID_ARG, "null guides");
+    if (!p) return fail(TPT_ERR_INVALID_ARG, "null params");
+    if (p->flags & ~(TPT_TEMPORAL_DEMODULATE | TPT_TEMPORAL_TILES)) return fail(TPT_ERR_INVALID_ARG, "unknown temporal flags");
+    const bool demod = (p->flags & TPT_TEMPORAL_DEMODULATE) != 0;
+    if (!guides->normal || !guides->depth || !guides->material)
+        return fail(TPT_ERR_INVALID_ARG, "temporal accumulation needs the normal, depth and material guides");
+    if (demod && !guides->albedo)
+        return fail(TPT_ERR_INVALID_ARG, "TPT_TEMPORAL_DEMODULATE needs the albedo guides");
+    if (!(p->alpha > 0.0f && p->alpha <= 1.0f)) return fail(TPT_ERR_INVALID_ARG, "alpha must be in (0, 1]");
+    if (!(p->depth_tol > 0.0f)) return fail(TPT_ERR_INVALID_ARG, "depth_tol must be > 0");
+    if (!(p->normal_min >= -1.0f && p->normal_min <= 1.0f))
+        return fail(TPT_ERR_INVALID_ARG, "normal_min must be in [-1, 1]");
+    if (p->max_history < 1 || p->max_history > 65536) return fail(TPT_ERR_INVALID_ARG, "max_history must be 1..65536");
+    if (!radiance_out && !bgra_out) return fail(TPT_ERR_INVALID_ARG, "no output buffer: radiance_out and bgra_out are null");
+    tpt_scene* s = h->scene;
+    DeviceGuard g(s->device);
+    hipStream_t st = s->stream;
+    const int W = h->width, H = h->height;
+    const size_t npix = (size_t)W * (size_t)H;
+    tpt::TemporalArgs a{};
+    // the current camera: fill_trace_args' constants
+    std::memcpy(a.c2w, cam->c2w, sizeof a.c2w);
+    {
+        float r[4];
+        tpt::mat4_vec4(cam->c2w, 0.0f, 0.0f, 0.0f, 1.0f, r);
+        a.origin[0] = r[0];
+        a.origin[1] = r[1];
+        a.origin[2] = r[2];
+        const float tan_half = tpt::ptan(cam->vfov * 0.5f);
+        a.sensor_h = 2.0f * tan_half;
+        a.sensor_w = cam->aspect * a.sensor_h;
+        a.half_sw = 0.5f * a.sensor_w;
+        a.half_sh = 0.5f * a.sensor_h;
+    }
+    a.inv_w = 1.0f / (float)W;
+    a.inv_h = 1.0f / (float)H;
+    a.has_prev = h->valid ? 1 : 0;
+    std::memcpy(a.prev_inv, h->prev_inv, sizeof a.prev_inv);
+    std::memcpy(a.prev_origin, h->prev_origin, sizeof a.prev_origin);
+    a.prev_sensor_w = h->prev_sensor[0];
+    a.prev_sensor_h = h->prev_sensor[1];
+    a.prev_half_sw = h->prev_sensor[2];
+    a.prev_half_sh = h->prev_sensor[3];
+    a.width = W;
+    a.height = H;
+    a.demodulate = demod ? 1 : 0;
+    a.tiles = (p->flags & TPT_TEMPORAL_TILES) ? 1 : 0;
+    a.alpha = p->alpha;
+    a.depth_tol = p->depth_tol;
+    a.normal_min = p->normal_min;
+    a.max_history = (float)p->max_history;
+    // host buffers are staged on the device: inputs go up, outputs come back
+    const bool rin_dev = is_device_ptr(radiance_in), rout_dev = is_device_ptr(radiance_out);
+    const bool var_dev = is_device_ptr(variance_out), len_dev = is_device_ptr(history_len_out);
+    const bool bgra_dev = is_device_ptr(bgra_out);
+    if (!rin_dev || (radiance_out && !rout_dev)) HIP_OR_FAIL(h->st_rad.alloc(3 * npix));
+    if (rin_dev) {
+        a.radiance_in = radiance_in;
+    } else {
+        HIP_OR_FAIL(hipMemcpyAsync(h->st_rad.p, radiance_in, 3 * npix * sizeof(float), hipMemcpyHostToDevice, st));
+        a.radiance_in = h->st_rad.p;
+    }
+    const float* const hf3[2] = {demod ? guides->albedo : nullptr, guides->normal};
+    const float** const df3[2] = {&a.albedo, &a.normal};
+    for (int k = 0; k < 2; ++k) {
+        if (!hf3[k]) continue;
+        if (is_device_ptr(hf3[k])) {
+            *df3[k] = hf3[k];
+        } else {
+            HIP_OR_FAIL(h->st_f3[k].alloc(3 * npix));
+            HIP_OR_FAIL(hipMemcpyAsync(h->st_f3[k].p, hf3[k], 3 * npix * sizeof(float), hipMemcpyHostToDevice, st));
+            *df3[k] = h->st_f3[k].p;
+        }
+    }
+    if (is_device_ptr(guides->depth)) {
+        a.depth = guides->depth;
+    } else {
+        HIP_OR_FAIL(h->st_depth.alloc(npix));
+        HIP_OR_FAIL(hipMemcpyAsync(h->st_depth.p, guides->depth, npix * sizeof(float), hipMemcpyHostToDevice, st));
+        a.depth = h->st_depth.p;
+    }
+    if (is_device_ptr(guides->material)) {
+        a.material = guides->material;
+    } else {
+        HIP_OR_FAIL(h->st_mtl.alloc(npix));
+        HIP_OR_FAIL(hipMemcpyAsync(h->st_mtl.p, guides->material, npix * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        a.material = h->st_mtl.p;
+    }
+    if (radiance_out) a.radiance_out = rout_dev ? radiance_out : h->st_rad.p;   // (a lane reads its pixel first)
+    if (variance_out) {
+        if (!var_dev) HIP_OR_FAIL(h->st_var.alloc(npix));
+        a.variance_out = var_dev ? variance_out : h->st_var.p;
+    }
+    if (history_len_out) {
+        if (!len_dev) HIP_OR_FAIL(h->st_len.alloc(npix));
+        a.history_out = len_dev ? history_len_out : h->st_len.p;
+    }
+    if (bgra_out) {
+        if (bgra_dev) {
+            a.bgra = bgra_out;
+        } else {   // alpha is untouched: the caller's bytes go up first
+            HIP_OR_FAIL(h->st_bgra.alloc(4 * npix));
+            HIP_OR_FAIL(hipMemcpyAsync(h->st_bgra.p, bgra_out, 4 * npix, hipMemcpyHostToDevice, st));
+            a.bgra = h->st_bgra.p;
+        }
+    }
+    const int from = h->cur, to = h->cur ^ 1;
+    for (int k = 0; k < 3; ++k) {
+        a.prev[k] = h->state[from][k].p;
+        a.next[k] = h->state[to][k].p;
+    }
+    a.reprojected = h->count.p;
+    HIP_OR_FAIL(hipMemsetAsync(h->count.p, 0, kCountWords * sizeof(unsigned long long), st));
+    HIP_OR_FAIL(hipEventRecord(h->ev[0], st));
+    HIP_OR_FAIL(tpt::launch_temporal(a, st));
+    HIP_OR_FAIL(hipEventRecord(h->ev[1], st));
+    if (radiance_out && !rout_dev)
+        HIP_OR_FAIL(hipMemcpyAsync(radiance_out, h->st_rad.p, 3 * npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (variance_out && !var_dev)
+        HIP_OR_FAIL(hipMemcpyAsync(variance_out, h->st_var.p, npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (history_len_out && !len_dev)
+        HIP_OR_FAIL(hipMemcpyAsync(history_len_out, h->st_len.p, npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (bgra_out && !bgra_dev) HIP_OR_FAIL(hipMemcpyAsync(bgra_out, h->st_bgra.p, 4 * npix, hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(hipMemcpyAsync(h->h_count.p, h->count.p, kCountWords * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    unsigned long long found = 0;
+    for (int k = 0; k < tpt::kTemporalSlots; ++k) found += h->h_count.p[(size_t)k * tpt::kTemporalSlotStride];
+    // the new state and this camera replace the old
+    h->cur = to;
+    h->valid = true;
+    if (!invert4(cam->c2w, h->prev_inv)) h->valid = false;   // a singular c2w: nothing can be reprojected into it
+    std::memcpy(h->prev_origin, a.origin, sizeof a.origin);
+    h->prev_sensor[0] = a.sensor_w;
+    h->prev_sensor[1] = a.sensor_h;
+    h->prev_sensor[2] = a.half_sw;
+    h->prev_sensor[3] = a.half_sh;
+    if (stats) {
+        float ms = 0.0f;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        stats->kernel_ms = ms;
+        stats->reprojected = found;
     }
     return TPT_OK;
 }

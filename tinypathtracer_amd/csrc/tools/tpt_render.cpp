@@ -6,10 +6,14 @@
 //   tpt_render scene.gltf [--width W] [--height H] [--spp N] [--depth D]
 //              [--seed S] [--env equirect.jpg|.ppm|--sky] [--out prefix] [--device i]
 //              [--frames F [--progressive]] [--aov] [--denoise [iterations]]
+//              [--temporal] [--yaw DEG]
 // --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
 // <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
 // a-trous filter of the written frame (tpt_denoise, the hosts' defaults; with
-// --progressive the written frame is the accumulated one).
+// --progressive the written frame is the accumulated one).  --temporal runs every
+// frame (frame i with seed S + i) and its feature buffers through tpt_temporal and
+// writes <out>_temporal.pfm / .ppm for the last one; --denoise then filters that.
+// --yaw DEG turns the camera about its own origin and up axis by DEG per frame.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -67,7 +71,19 @@ void write_pfm(const std::string& path, const std::vector<float>& v, int W, int 
 const char* kUsage =
     "usage: %s scene.gltf [--width W] [--height H] [--spp N] [--depth D] [--seed S] "
     "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]] "
-    "[--aov] [--denoise [iterations]]\n";
+    "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG]\n";
+
+// The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
+tpt::Camera yawed(const tpt::Camera& base, double deg) {
+    tpt::Camera cam = base;
+    const double t = deg * M_PI / 180.0, c = std::cos(t), s = std::sin(t);
+    for (int i = 0; i < 4; ++i) {
+        const double right = base.c.c2w[i], back = base.c.c2w[8 + i];
+        cam.c.c2w[i] = (float)(c * right - s * back);
+        cam.c.c2w[8 + i] = (float)(s * right + c * back);
+    }
+    return cam;
+}
 
 }  // namespace
 
@@ -78,7 +94,8 @@ int main(int argc, char** argv) {
     }
     std::string scene_file = argv[1], env_file, out = "out";
     int W = 1920, H = 1080, spp = 64, depth = 8, device = 0, frames = 1;
-    bool progressive = false, aov = false, denoise = false;
+    bool progressive = false, aov = false, denoise = false, temporal = false;
+    double yaw = 0.0;
     int dn_iterations = tpt::defaultDenoise().iterations;
     uint64_t seed = 0;
     bool sky = false;
@@ -100,11 +117,17 @@ int main(int argc, char** argv) {
         else if (a == "--frames") frames = std::stoi(next());
         else if (a == "--progressive") progressive = true;
         else if (a == "--aov") aov = true;
+        else if (a == "--temporal") temporal = true;
+        else if (a == "--yaw") yaw = std::stod(next());
         else if (a == "--denoise") {
             denoise = true;   // an optional iteration count follows
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn_iterations = std::stoi(argv[++i]);
         }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
+    }
+    if (temporal && progressive) {   // progressive is already the exact accumulation of an unmoving camera
+        std::fprintf(stderr, "--temporal cannot be combined with --progressive\n");
+        return 2;
     }
     try {
         tpt::EnvLight env;
@@ -124,22 +147,42 @@ int main(int argc, char** argv) {
         f.height = H;
         f.bgra.assign((size_t)W * H * 4, 255);
         f.radiance.assign((size_t)W * H * 3, 0.0f);
-        for (int i = 0; i < frames; ++i)
-            f.stats = pt.doTrace(d, scene.m_camera, f.bgra.data(), spp, seed, depth, f.radiance.data(), 1, 0,
-                                 progressive && i > 0);
+        tpt::Camera cam = scene.m_camera;
+        std::vector<float> acc;       // --temporal: the accumulated frame
+        tpt::AOV g;
+        if (temporal) {
+            tpt::History hist(d, W, H);
+            acc.resize((size_t)W * H * 3);
+            std::vector<uint8_t> fb((size_t)W * H * 4, 255);
+            const uint64_t base = seed ? seed : (uint64_t)std::time(nullptr);
+            for (int i = 0; i < frames; ++i) {
+                cam = yawed(scene.m_camera, yaw * i);
+                f.stats = pt.doTrace(d, cam, f.bgra.data(), spp, base + (uint64_t)i, depth, f.radiance.data());
+                g = pt.renderAOV(d, cam);
+                pt.temporal(hist, cam, f.radiance.data(), g.view(), acc.data(), nullptr, nullptr, fb.data());
+            }
+            write_pfm(out + "_temporal.pfm", acc, W, H, 3);
+            write_ppm(out + "_temporal.ppm", fb, W, H);
+        } else {
+            for (int i = 0; i < frames; ++i) {
+                if (yaw != 0.0) cam = yawed(scene.m_camera, yaw * i);
+                f.stats = pt.doTrace(d, cam, f.bgra.data(), spp, seed, depth, f.radiance.data(), 1, 0,
+                                     progressive && i > 0);
+            }
+        }
         write_ppm(out + ".ppm", f.bgra, W, H);
         write_pfm(out + ".pfm", f.radiance, W, H, 3);
         if (aov || denoise) {
-            tpt::AOV g = pt.renderAOV(d, scene.m_camera);
+            if (!temporal) g = pt.renderAOV(d, cam);
             if (aov) {
                 write_pfm(out + "_albedo.pfm", g.albedo, W, H, 3);
                 write_pfm(out + "_normal.pfm", g.normal, W, H, 3);
                 write_pfm(out + "_depth.pfm", g.depth, W, H, 1);
             }
-            if (denoise) {
+            if (denoise) {   // of the temporal output when there is one
                 std::vector<float> clean((size_t)W * H * 3);
                 std::vector<uint8_t> fb((size_t)W * H * 4, 255);
-                pt.denoise(d, f.radiance.data(), g.view(), clean.data(), fb.data(),
+                pt.denoise(d, temporal ? acc.data() : f.radiance.data(), g.view(), clean.data(), fb.data(),
                            tpt::defaultDenoise(dn_iterations));
                 write_pfm(out + "_denoised.pfm", clean, W, H, 3);
                 write_ppm(out + "_denoised.ppm", fb, W, H);
