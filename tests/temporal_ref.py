@@ -1,5 +1,5 @@
 """CPU reference for the temporal pass (tests/test_gpu_temporal.py,
-tests/test_temporal_api.py): a float64 numpy restatement of tpt_temporal as DESIGN.md
+tests/test_temporal_api.py, tests/test_temporal_ref_teeth.py): a float64 numpy restatement of tpt_temporal as DESIGN.md
 section 5 "Post-pass" defines it, the synthetic three-patch scene whose feature
 buffers the tests build analytically, and the cameras they move between.
 
@@ -27,28 +27,39 @@ def sensor(vfov, aspect):
     return sensor_w, sensor_h, F(0.5) * sensor_w, F(0.5) * sensor_h
 
 
-def camera(yaw_deg=0.0, translate=(0.0, 0.0, 0.0), vfov=0.8, aspect=1.0):
-    """A camera dict: the identity turned by yaw_deg about +y, then moved by
-    `translate`.  c2w is 16 float32 values, column-major."""
+def camera(yaw_deg=0.0, translate=(0.0, 0.0, 0.0), vfov=0.8, aspect=1.0, pitch_deg=0.0, roll_deg=0.0):
+    """A camera dict: the identity turned by R = R_y(yaw) R_x(pitch) R_z(roll) (roll
+    about the viewing axis first, then pitch, then yaw about +y), then moved by
+    `translate`.  c2w is 16 float32 values, column-major.  With pitch = roll = 0 the
+    yaw matrix is not multiplied by anything, so those cameras are what they were
+    before pitch and roll existed, bit for bit."""
     t = np.deg2rad(yaw_deg)
     m = np.eye(4)
     m[0, 0], m[0, 2], m[2, 0], m[2, 2] = np.cos(t), np.sin(t), -np.sin(t), np.cos(t)
+    if pitch_deg != 0.0 or roll_deg != 0.0:
+        p, r = np.deg2rad(pitch_deg), np.deg2rad(roll_deg)
+        rx, rz = np.eye(3), np.eye(3)
+        rx[1, 1], rx[1, 2], rx[2, 1], rx[2, 2] = np.cos(p), -np.sin(p), np.sin(p), np.cos(p)
+        rz[0, 0], rz[0, 1], rz[1, 0], rz[1, 1] = np.cos(r), -np.sin(r), np.sin(r), np.cos(r)
+        m[:3, :3] = m[:3, :3] @ rx @ rz
     m[:3, 3] = translate
     return {"c2w": m.T.reshape(16).astype(F), "vfov": float(vfov), "aspect": float(aspect)}
 
 
-def synthetic_guides(cam, W, H):
+def synthetic_guides(cam, W, H, materials=(0, 1, 2)):
     """First hits of the pixel-centre rays against three world-space patches, closest
     first; everything else is a miss (normal 0, depth 0, material -1).
-      far wall:    z = -4, normal +z, y < 1.0, material 0
-      near strip:  z = -2.5, normal +z, -0.4 < x < 0.5, y < 0.6, material 1
-      tilted wall: through (-1.2, 0, -4), normal (0.6, 0, 0.8), x < -1.2, y < 1.0, material 2"""
+      far wall:    z = -4, normal +z, y < 1.0, material materials[0]
+      near strip:  z = -2.5, normal +z, -0.4 < x < 0.5, y < 0.6, material materials[1]
+      tilted wall: through (-1.2, 0, -4), normal (0.6, 0, 0.8), x < -1.2, y < 1.0, material materials[2]
+    materials = (0, 0, 0) is the single-material scene: the same geometry, but only
+    the depth and the normal rules can tell the patches apart."""
     o32, d32 = R.pixel_centre_rays(cam["c2w"], cam["vfov"], cam["aspect"], W, H)
     o, d = o32.astype(np.float64), d32.astype(np.float64)
     patches = [
-        ((0.0, 0.0, -4.0), (0.0, 0.0, 1.0), lambda X: X[..., 1] < 1.0, 0),
-        ((0.0, 0.0, -2.5), (0.0, 0.0, 1.0), lambda X: (X[..., 0] > -0.4) & (X[..., 0] < 0.5) & (X[..., 1] < 0.6), 1),
-        ((-1.2, 0.0, -4.0), (0.6, 0.0, 0.8), lambda X: (X[..., 0] < -1.2) & (X[..., 1] < 1.0), 2),
+        ((0.0, 0.0, -4.0), (0.0, 0.0, 1.0), lambda X: X[..., 1] < 1.0, materials[0]),
+        ((0.0, 0.0, -2.5), (0.0, 0.0, 1.0), lambda X: (X[..., 0] > -0.4) & (X[..., 0] < 0.5) & (X[..., 1] < 0.6), materials[1]),
+        ((-1.2, 0.0, -4.0), (0.6, 0.0, 0.8), lambda X: (X[..., 0] < -1.2) & (X[..., 1] < 1.0), materials[2]),
     ]
     best = np.full((H, W), np.inf)
     normal = np.zeros((H, W, 3), F)
@@ -66,11 +77,18 @@ def synthetic_guides(cam, W, H):
     return {"normal": normal, "depth": depth, "material": material}
 
 
-def temporal_ref(state, cam, radiance, aov, alpha, depth_tol, normal_min, max_history, demodulate):
+def temporal_ref(state, cam, radiance, aov, alpha, depth_tol, normal_min, max_history, demodulate, _without=None):
     """One call of the definition.  state: None (after create / reset) or the dict a
     previous call returned.  Returns a dict: `out`, `variance`, `history_len`
     (float64), `reprojected` (bool mask), `decidable` (bool mask) and the new state
-    under `state`."""
+    under `state`.
+
+    _without (tests/test_temporal_ref_teeth.py only) evaluates a *wrong* definition, one
+    rule knocked out, to show that a test's inputs can see that rule: "prev_origin"
+    measures the expected depth to the current origin instead of the previous one,
+    "front" drops the local.z < 0 test.  (The depth, normal and sensor rules need no
+    switch: depth_tol 1e9, normal_min -1, a previous camera with the current sensor.)"""
+    assert _without in (None, "prev_origin", "front")
     n = np.asarray(aov["normal"], np.float64)
     z = np.asarray(aov["depth"], np.float64)
     m = np.asarray(aov["material"], np.int64)
@@ -93,6 +111,10 @@ def temporal_ref(state, cam, radiance, aov, alpha, depth_tol, normal_min, max_hi
         local = np.where(hit[..., None], X @ inv[:3, :3].T + inv[:3, 3], d @ inv[:3, :3].T)
         dist = np.linalg.norm(X - po, axis=-1)
         front = local[..., 2] < 0
+        if _without == "prev_origin":
+            dist = np.linalg.norm(X - o, axis=-1)
+        if _without == "front":
+            front = np.ones((H, W), bool)
         sw, sh, hsw, hsh = (np.float64(v) for v in sensor(pc["vfov"], pc["aspect"]))
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
             s = -1.0 / local[..., 2]

@@ -21,24 +21,41 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def synthetic(seed=11):
+def synthetic(w=W, h=H, seed=11):
     """Seeded random colour; normals in two regions; depth a ramp with a step; a
-    block of miss pixels (normal 0, depth 0, albedo 1); one black-albedo pixel."""
+    block of miss pixels (normal 0, depth 0, albedo 1); one black-albedo pixel.  The
+    features sit where they sit at 37 x 29 (columns 20 and 25:33 of 37, rows 15, 3:9
+    and 20 of 29), scaled to the frame and rounded down; a frame too small for one
+    goes without it: the miss block where its rows or columns round to none, one
+    normal region in a single column, no depth step in a single row, and no black
+    pixel in a frame of one pixel."""
     rng = np.random.default_rng(seed)
-    rad = rng.uniform(0.0, 2.0, (H, W, 3)).astype(np.float32)
-    alb = rng.uniform(0.2, 1.0, (H, W, 3)).astype(np.float32)
-    nrm = np.zeros((H, W, 3), np.float32)
-    nrm[:, :20] = (0.0, 0.0, 1.0)
-    nrm[:, 20:] = (0.6, 0.0, 0.8)
-    x = np.arange(W, dtype=np.float32)[None, :]
-    y = np.arange(H, dtype=np.float32)[:, None]
-    z = (2.0 + 0.01 * x + np.where(y >= 15, 1.5, 0.0)).astype(np.float32)
-    nrm[3:9, 25:33] = 0.0
-    z[3:9, 25:33] = 0.0
-    alb[3:9, 25:33] = 1.0
-    alb[20, 5] = 0.0                                       # demodulation divides by the floor 1e-3
-    rad[20, 5] = 0.0
+    rad = rng.uniform(0.0, 2.0, (h, w, 3)).astype(np.float32)
+    alb = rng.uniform(0.2, 1.0, (h, w, 3)).astype(np.float32)
+    col = lambda c: c * w // 37
+    row = lambda r: r * h // 29
+    nrm = np.zeros((h, w, 3), np.float32)
+    nrm[:, :col(20)] = (0.0, 0.0, 1.0)
+    nrm[:, col(20):] = (0.6, 0.0, 0.8)
+    x = np.arange(w, dtype=np.float32)[None, :]
+    y = np.arange(h, dtype=np.float32)[:, None]
+    z = (2.0 + 0.01 * x + np.where(y >= row(15), 1.5, 0.0)).astype(np.float32)
+    nrm[row(3):row(9), col(25):col(33)] = 0.0
+    z[row(3):row(9), col(25):col(33)] = 0.0
+    alb[row(3):row(9), col(25):col(33)] = 1.0
+    if w * h > 1:
+        alb[row(20), col(5)] = 0.0                         # demodulation divides by the floor 1e-3
+        rad[row(20), col(5)] = 0.0
     return rad, {"albedo": alb, "normal": nrm, "depth": z}
+
+
+# (W x H, iterations) beyond the 37 x 29 frame: 131 x 9 is three x-blocks of k_atrous and
+# nine tile columns, the last ones partial; 65 x 5 with 8 iterations has steps 32 to
+# 128 beyond the frame and a k_atrous block that holds one pixel column; 16 x 16 is
+# exactly one tile, its LDS halo all outside the frame; 17 x 16 adds a tile of one
+# column; 2 x 3 and 1 x 1 are smaller than every halo.
+NEW_CASES = [((131, 9), 5), ((65, 5), 8), ((16, 16), 5), ((17, 16), 3), ((2, 3), 8), ((1, 1), 8)]
+NEW_SIZES = [size for size, _ in NEW_CASES]
 
 
 @pytest.fixture(scope="module")
@@ -82,6 +99,70 @@ def test_lds_and_direct_kernels_agree_bit_for_bit(ctx):
     a = pt.denoise(d, rad, aov, iterations=3, **SIG)
     b = pt.denoise(d, rad, aov, iterations=3, flags=_lib.DENOISE_DIRECT, **SIG)
     assert np.array_equal(_bits(a), _bits(b))
+
+
+# The new sizes' own measurement, taken as MEASURED_MAX was and with the same margin;
+# it has to stay below the allowance derived above, about 2e-5 per iteration: 1e-4 at
+# five iterations, 1.6e-4 at eight.
+# Measured on MI355X, without / with demodulation, the same under both kernels:
+#   131 x 9, 5 iterations   1.08e-7 / 1.34e-7      17 x 16, 3 iterations   9.2e-8 / 1.14e-7
+#   65 x 5, 8 iterations    1.49e-7 / 2.15e-7      2 x 3, 8 iterations     4.5e-8 / 6.0e-8
+#   16 x 16, 5 iterations   1.29e-7 / 1.34e-7      1 x 1, 8 iterations     0 (the output is the input)
+MEASURED_MAX_NEW = 2.151e-7         # 65 x 5, 8 iterations, demodulation
+BOUND_NEW = 10 * MEASURED_MAX_NEW
+assert BOUND_NEW <= 1e-4
+
+
+@pytest.mark.parametrize("demodulate", [False, True])
+@pytest.mark.parametrize("size,iterations", NEW_CASES, ids=[f"{w}x{h}-{i}" for (w, h), i in NEW_CASES])
+def test_other_sizes_match_numpy_reference(ctx, size, iterations, demodulate):
+    """Frames of several blocks, of exactly one tile, and smaller than a tile or its
+    halo; up to the 8 iterations the call accepts.  Both kernels against the
+    reference, and against each other bit for bit."""
+    s, d, _, _, _ = ctx
+    w, h = size
+    pt = T.PathTracer("", w, h, 0)
+    rad, aov = synthetic(w, h, 11)
+    ref = R.atrous_ref(rad, aov["albedo"], aov["normal"], aov["depth"], iterations, SIG["sigma_color"],
+                       SIG["sigma_normal"], SIG["sigma_depth"], demodulate)
+    assert np.isfinite(ref).all()
+    scale = np.abs(ref).max()
+    outs = []
+    for flags in (0, _lib.DENOISE_DIRECT):
+        out = pt.denoise(d, rad, aov, iterations=iterations, demodulate=demodulate, flags=flags, **SIG)
+        err = np.abs(out.astype(np.float64) - ref).max() / scale
+        print(f"{w} x {h} iterations {iterations} demodulate {demodulate} flags {flags}: "
+              f"max |gpu - ref| / max|c| = {err:.3e}")
+        assert np.isfinite(out).all()
+        assert err <= BOUND_NEW
+        if w >= 5 or h >= 5:
+            assert np.abs(out.astype(np.float64) - rad).max() > 0.05 * scale   # it filtered
+        outs.append(out)
+    assert np.array_equal(_bits(outs[0]), _bits(outs[1]))
+    if (w, h) == (1, 1):                                   # its only tap is itself
+        assert np.abs(outs[0].astype(np.float64) - rad).max() <= BOUND_NEW * scale
+
+
+@pytest.mark.parametrize("size", [(131, 9), (17, 16)])
+@pytest.mark.parametrize("flags", [0, _lib.DENOISE_DIRECT])
+def test_nothing_is_written_past_the_end(ctx, size, flags):
+    """`out` is the first H rows of a device tensor one row longer: the extra row keeps
+    its sentinel, and no sentinel survives inside."""
+    import torch
+    s, d, _, _, _ = ctx
+    w, h = size
+    rad, aov = synthetic(w, h, 11)
+    dev = torch.device("cuda", 0)
+    whole = torch.full((h + 1, w, 3), -7.0, device=dev)
+    out = whole[:h]
+    t_aov = {k: torch.from_numpy(v).to(dev) for k, v in aov.items()}
+    want = T.PathTracer("", w, h, 0).denoise(d, rad, aov, iterations=3, flags=flags, **SIG)
+    assert T.PathTracer("", w, h, 0).denoise(d, torch.from_numpy(rad).to(dev), t_aov, iterations=3, out=out,
+                                             flags=flags, **SIG) is out
+    got = whole.cpu().numpy()
+    assert (got[h] == -7.0).all()
+    assert not (got[:h] == -7.0).any()
+    assert np.array_equal(_bits(got[:h]), _bits(want))
 
 
 def test_constant_image_stays_constant(ctx):
