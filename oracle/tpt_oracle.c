@@ -634,7 +634,7 @@ static inline v3 env_lookup(const orc_env* env, v3 d, int tm) {
 
 /* Env importance sampling: the build's A15 re-derivation (env_light.cu:10-54
  * intends a 2-D piecewise-constant distribution), restating
- * libtpt's format (api.cpp build_env_is, trace.hip env_is_sample): piecewise
+ * libtpt's format (api_scene.cpp build_env_is, trace.hip env_is_sample): piecewise
  * constant over blocks of B x B texels, B = 1 up to 2^17 texels and doubled
  * until the block grid has at most 2^17 cells.  Block weight = sum over its
  * texels (texel rows, then columns) of luma * sin(theta at the texel row's

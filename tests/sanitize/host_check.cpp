@@ -5,11 +5,15 @@
 //   host_check gltf FILE...   load_gltf (host/gltf.cpp, json_lite.hpp)
 //   host_check image FILE...  load_image (host/image.cpp: JPEG / PPM)
 //   host_check wide N SEED    build_wide_sah (host/wide_bvh.cpp) on N random leaf boxes
+//   host_check plan CASE...   plan_launches (host/launch_plan.cpp); CASE is key=value,... (plan_case below);
+//                             prints the plan as one JSON object per case
+//   host_check plan-sweep N SEED   N random cases, the plan's invariants checked here
 //
 // Prints one line per input: "ok", or "error: <message>" for a parse error
 // (the library's exception, which tpt_gltf_load / tpt_env_load turn into a
 // status).  Any memory error or undefined behaviour aborts with the
 // sanitizer's report instead.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -19,7 +23,203 @@
 #include <string>
 #include <vector>
 
+#include "launch_plan.hpp"
 #include "tpt_internal.hpp"
+
+// A launch-plan case as tpt_render_frames hands it to plan_launches: the frame
+// and deal (bh derived as the entry point derives it), tpt_params, the scene.
+struct PlanCase {
+    tpt::PlanInput in;
+    std::vector<int32_t> list;
+    void finish() {
+        in.list = list.data();
+        in.list_len = list.size();
+        in.bh = in.listed ? tpt::band_list_rows(list.data(), list.size(), in.band_rows, in.height)
+                          : tpt::band_height_of(in.height, in.band_rows, in.band_count, in.band_index);
+    }
+};
+
+// key=value,...: w h rows bc bi list (ids joined by ':', "-" for an empty list) frames | spp flags lanes refill
+// leaf spl sets chunks | faces lights mtls resident env_is quad_fits.  Defaults: 16 band rows, one frame, the whole
+// frame, 327,680 resident lanes, quad_fits, everything else 0.
+static bool plan_case(const std::string& text, PlanCase& c) {
+    c.in.resident_lanes = 327680;
+    c.in.quad_fits = true;
+    size_t at = 0;
+    while (at < text.size()) {
+        const size_t end = std::min(text.find(',', at), text.size()), eq = text.find('=', at);
+        if (eq == std::string::npos || eq >= end) return false;
+        const std::string key = text.substr(at, eq - at), val = text.substr(eq + 1, end - eq - 1);
+        const long long v = std::atoll(val.c_str());
+        if (key == "w") c.in.width = (int32_t)v;
+        else if (key == "h") c.in.height = (int32_t)v;
+        else if (key == "rows") c.in.band_rows = (int32_t)v;
+        else if (key == "bc") c.in.band_count = (int32_t)v;
+        else if (key == "bi") c.in.band_index = (int32_t)v;
+        else if (key == "frames") c.in.n_frames = (int32_t)v;
+        else if (key == "spp") c.in.spp = (int32_t)v;
+        else if (key == "flags") c.in.flags = (int32_t)v;
+        else if (key == "lanes") c.in.lanes_per_pixel = (int32_t)v;
+        else if (key == "refill") c.in.refill = (int32_t)v;
+        else if (key == "leaf") c.in.leaf_batch = (int32_t)v;
+        else if (key == "spl") c.in.spp_per_launch = (int32_t)v;
+        else if (key == "sets") c.in.pipe_sets = (int32_t)v;
+        else if (key == "chunks") c.in.pipe_chunks = (int32_t)v;
+        else if (key == "faces") c.in.n_faces = (int32_t)v;
+        else if (key == "lights") c.in.n_lights = (int32_t)v;
+        else if (key == "mtls") c.in.n_materials = (int32_t)v;
+        else if (key == "resident") c.in.resident_lanes = (uint64_t)v;
+        else if (key == "env_is") c.in.env_is = v != 0;
+        else if (key == "quad_fits") c.in.quad_fits = v != 0;
+        else if (key == "list") {
+            c.in.listed = true;
+            for (size_t i = 0; i < val.size() && val != "-";) {
+                c.list.push_back((int32_t)std::atoi(val.c_str() + i));
+                const size_t colon = val.find(':', i);
+                i = colon == std::string::npos ? val.size() : colon + 1;
+            }
+        } else {
+            return false;
+        }
+        at = end + 1;
+    }
+    c.finish();
+    return true;
+}
+
+template <class It, class F>
+static void print_list(const char* name, It b, It e, F item) {
+    std::printf(",\"%s\":[", name);
+    for (It i = b; i != e; ++i) {
+        if (i != b) std::printf(",");
+        item(*i);
+    }
+    std::printf("]");
+}
+
+static void print_plan(const PlanCase& c, const tpt::LaunchPlan& pl) {
+    if (pl.status != TPT_OK) {
+        std::printf("{\"status\":%d,\"message\":\"%s\"}\n", (int)pl.status, pl.message);
+        return;
+    }
+    std::printf("{\"status\":0,\"bh\":%d,\"pair\":%d,\"pair_kernel\":%d,\"quad\":%d,\"drained\":%d,\"refill\":%d,"
+                "\"leaf_kb\":%d,\"xcd_run\":%d,\"wg_rows\":%d,\"nset\":%d,\"chunk\":%d",
+                c.in.bh, pl.pair, pl.pair_kernel, pl.quad, pl.drained, pl.refill, pl.leaf_kb, pl.xcd_run, pl.wg_rows,
+                pl.nset, pl.chunk);
+    print_list("launches", pl.launches.begin(), pl.launches.end(),
+               [](const tpt::PlanLaunch& l) { std::printf("[%d,%d]", l.set, l.samples); });
+    print_list("order", pl.order.begin(), pl.order.end(), [](size_t j) { std::printf("%zu", j); });
+    print_list("set_rows", pl.set_rows, pl.set_rows + pl.nset, [](int32_t r) { std::printf("%d", r); });
+    print_list("set_off", pl.set_off, pl.set_off + pl.nset, [](size_t o) { std::printf("%zu", o); });
+    print_list("set_list", pl.set_list, pl.set_list + pl.nset, [](const std::vector<int32_t>& l) {
+        std::printf("[");
+        for (size_t i = 0; i < l.size(); ++i) std::printf(i ? ",%d" : "%d", l[i]);
+        std::printf("]");
+    });
+    std::printf("}\n");
+}
+
+// The invariants every plan keeps; returns what is broken (null: nothing).
+static const char* plan_broken(const PlanCase& c, const tpt::LaunchPlan& pl) {
+    const tpt::PlanInput& in = c.in;
+    if (pl.nset < 1 || pl.nset > tpt::kMaxPipe || pl.chunk < 1 || pl.chunk > in.spp) return "nset or chunk out of range";
+    // every set's samples sum to spp (no launches without rows); inner launches are whole chunks
+    std::vector<std::vector<int>> per((size_t)pl.nset);
+    for (const tpt::PlanLaunch& l : pl.launches) {
+        if (l.set < 0 || l.set >= pl.nset || l.samples < 1) return "launch out of range";
+        per[(size_t)l.set].push_back(l.samples);
+    }
+    for (const std::vector<int>& s : per) {
+        long long sum = 0;
+        for (size_t i = 0; i < s.size(); ++i) {
+            sum += s[i];
+            if (i > 0 && i + 1 < s.size() && s[i] != pl.chunk) return "an inner launch is not a whole chunk";
+            if (s[i] > pl.chunk) return "a launch is longer than a chunk";
+        }
+        if (sum != (in.bh > 0 ? in.spp : 0)) return "a set's samples do not sum to spp";
+    }
+    // the issue order: a permutation of the launches, each set's in plan order (plan order is set by set)
+    if (pl.order.size() != pl.launches.size()) return "issue order: wrong length";
+    std::vector<int> seen(pl.launches.size(), 0);
+    std::vector<long long> last((size_t)pl.nset, -1);
+    for (size_t j : pl.order) {
+        if (j >= seen.size() || seen[j]++) return "issue order: not a permutation";
+        const int k = pl.launches[j].set;
+        if ((long long)j < last[(size_t)k]) return "issue order: a set's launches out of order";
+        last[(size_t)k] = (long long)j;
+    }
+    // the sets' rows sum to the call's
+    long long rows = 0;
+    for (int k = 0; k < pl.nset; ++k) rows += pl.set_rows[k];
+    if (rows != in.bh) return "set rows do not sum to bh";
+    // an explicit deal over several sets: the shares partition the list and lie back to back behind it
+    if (in.listed && pl.nset > 1) {
+        std::vector<int32_t> all;
+        size_t off = c.list.size();
+        for (int k = 0; k < pl.nset; ++k) {
+            if (pl.set_off[k] != off) return "set shares are not back to back behind the list";
+            off += pl.set_list[k].size();
+            all.insert(all.end(), pl.set_list[k].begin(), pl.set_list[k].end());
+        }
+        std::vector<int32_t> want = c.list;
+        std::sort(all.begin(), all.end());
+        std::sort(want.begin(), want.end());
+        if (all != want) return "set shares do not partition the list";
+    }
+    return nullptr;
+}
+
+static int check_plan_sweep(int n, unsigned seed) {
+    std::mt19937 rng(seed);
+    auto pick = [&](int lo, int hi) { return lo + (int)(rng() % (unsigned)(hi - lo + 1)); };
+    int planned = 0;
+    for (int i = 0; i < n; ++i) {
+        PlanCase c;
+        tpt::PlanInput& in = c.in;
+        static const int kRows[] = {1, 4, 8, 16, 32};
+        static const int kRes[] = {640, 20480, 327680};
+        in.width = rng() % 4 ? pick(4, 400) : pick(400, 4000);
+        in.height = rng() % 4 ? pick(1, 300) : pick(300, 2200);
+        in.band_rows = kRows[rng() % 5];
+        in.n_frames = pick(1, 3);
+        const int n_bands = (in.height + in.band_rows - 1) / in.band_rows;
+        if (rng() % 3 == 0) {   // an explicit deal: distinct bands in random order, a short last band last
+            in.listed = true;
+            for (int b = 0; b < n_bands; ++b)
+                if (rng() % 2) c.list.push_back(b);
+            std::shuffle(c.list.begin(), c.list.end(), rng);
+            if (in.height % in.band_rows != 0)
+                for (size_t k = 0; k + 1 < c.list.size(); ++k)
+                    if (c.list[k] == n_bands - 1) std::swap(c.list[k], c.list.back());
+        } else {
+            in.band_count = pick(1, 8);
+            in.band_index = pick(0, in.band_count - 1);
+        }
+        in.spp = rng() % 3 ? pick(1, 64) : pick(64, 5000);
+        in.flags = rng() % 8 == 0 ? TPT_FLAG_REF_ORDER : 0;
+        in.lanes_per_pixel = pick(0, 2);
+        in.spp_per_launch = rng() % 4 == 0 ? pick(1, in.spp) : 0;
+        in.pipe_sets = pick(0, 5);
+        in.pipe_chunks = rng() % 2 ? pick(1, 20) : 0;
+        in.n_faces = rng() % 2 ? 1932 : 131072;
+        in.n_lights = rng() % 3 == 0;
+        in.n_materials = pick(0, 8);
+        in.resident_lanes = (uint64_t)kRes[rng() % 3];
+        in.env_is = rng() % 5 == 0;
+        in.quad_fits = rng() % 4 != 0;
+        c.finish();
+        const tpt::LaunchPlan pl = tpt::plan_launches(in);
+        if (pl.status != TPT_OK) continue;
+        ++planned;
+        if (const char* what = plan_broken(c, pl)) {
+            std::printf("error: case %d: %s\n", i, what);
+            print_plan(c, pl);
+            return 1;
+        }
+    }
+    std::printf("ok plan sweep: %d of %d cases planned\n", planned, n);
+    return 0;
+}
 
 static int check_wide(int n, unsigned seed, int threads) {
     std::mt19937 rng(seed);
@@ -83,10 +283,23 @@ static int check_wide(int n, unsigned seed, int threads) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: host_check gltf|image FILE... | wide N SEED [THREADS]\n");
+        std::fprintf(stderr, "usage: host_check gltf|image FILE... | wide N SEED [THREADS] | plan CASE... | "
+                             "plan-sweep N SEED\n");
         return 2;
     }
     const std::string mode = argv[1];
+    if (mode == "plan-sweep") return check_plan_sweep(std::atoi(argv[2]), argc > 3 ? (unsigned)std::atoi(argv[3]) : 1u);
+    if (mode == "plan") {
+        for (int i = 2; i < argc; ++i) {
+            PlanCase c;
+            if (!plan_case(argv[i], c)) {
+                std::printf("error: bad case %s\n", argv[i]);
+                return 1;
+            }
+            print_plan(c, tpt::plan_launches(c.in));
+        }
+        return 0;
+    }
     if (mode == "wide")
         return check_wide(std::atoi(argv[2]), argc > 3 ? (unsigned)std::atoi(argv[3]) : 1u, argc > 4 ? std::atoi(argv[4]) : -1);
     for (int i = 2; i < argc; ++i) {

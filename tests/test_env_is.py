@@ -54,7 +54,7 @@ def test_env_is_follows_brightness():
 
 
 def _block(w, h):
-    """The IS block side (api.cpp env_is_block, oracle env_is_block)."""
+    """The IS block side (api_scene.cpp env_is_block, oracle env_is_block)."""
     b = 1
     while ((w + b - 1) // b) * ((h + b - 1) // b) > (1 << 17):
         b *= 2

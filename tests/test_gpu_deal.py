@@ -172,7 +172,7 @@ def test_full_size_c2_cost_deal_8_ways():
 ])
 def test_xcd_runs_rotated_per_chunk_bit_identical(W, H, kw):
     """A scene larger than an XCD's L2 (c5, 131 K triangles) deals tiles to XCDs in
-    runs that rotate by one per chunk of a set's samples (api.cpp xcd_rot): the
+    runs that rotate by one per chunk of a set's samples (api_render.cpp xcd_rot): the
     chunked, pipelined render equals one launch bit for bit."""
     s = T.Scene(scene_path("c5"))
     d = s.copySceneToDevice(0).build()

@@ -221,7 +221,7 @@ def test_render_parity_full_resolution(built, name, W, H, spp, depth, env):
     if env:
         pt.envLight = T.EnvLight(sky, 0)
     runs = [("ordered", {}), ("reference", {"flags": T._lib.FLAG_REF_ORDER})]
-    if name == "box":   # 3 band sets on 3 streams, 2 chunks each (host/api.cpp launch pipeline)
+    if name == "box":   # 3 band sets on 3 streams, 2 chunks each (host/launch_plan.cpp launch pipeline)
         runs.append(("pipeline", {"pipe_sets": 3, "pipe_chunks": 2}))
     if name == "ball":   # delta light: pair mode is the default; one lane per pixel too
         runs.append(("one lane per pixel", {"lanes_per_pixel": 1}))
@@ -409,7 +409,7 @@ def test_spp_chunking_bit_identical(built):
 
 def test_launch_pipeline_bit_identical(built):
     """The launch pipeline (row band sets on their own streams, spp in offset
-    chunks, host/api.cpp; the default from 1024 spp on, tpt_params.pipe_sets
+    chunks, host/launch_plan.cpp; the default from 1024 spp on, tpt_params.pipe_sets
     forces it from 256) equals one launch bit for bit: 2, 3 and 4 sets, banded
     across ranks, and a frame batch."""
     s, d, _ = built["box"]

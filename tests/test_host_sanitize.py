@@ -7,6 +7,10 @@ malformed JSON, negative / huge / out-of-range accessor fields, broken data
 URIs.  Every input must end in "ok" or a parse error; a memory error or
 undefined behaviour aborts the harness with the sanitizer's report.
 
+The same harness runs the launch planner (host/launch_plan.cpp, the launch rules
+of tpt_render_frames): the test_plan_* cases pin the lane mode, the kernel knobs
+and the launch schedule it decides, which otherwise show only on a GPU.
+
 CPU only (the sanitizer build never travels to the GPU box)."""
 import base64
 import io
@@ -194,6 +198,116 @@ def test_wide_tree_builder(host_check, n, seed, threads):
     r = subprocess.run([host_check, "wide", str(n), str(seed), str(threads)], capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0 and r.stdout.startswith("ok"), r.stdout + r.stderr[-3000:]
+
+
+def _plan(exe, *cases):
+    """plan_launches (host/launch_plan.cpp) on each case ("key=value,..." as
+    host_check.cpp plan_case reads it): one dict per case."""
+    return [json.loads(x) for x in run(exe, "plan", cases)]
+
+
+def _sets(plan):
+    """Each set's launches, in order."""
+    return [[n for k, n in plan["launches"] if k == s] for s in range(plan["nset"])]
+
+
+BOX = "faces=1932"   # box.gltf: 1,932 triangles, no delta lights; resident lanes 327,680, 16 band rows, one frame
+
+
+def test_plan_default_1080p(host_check):
+    """The launch rules of tpt_render_frames, as the code before the planner was
+    split out computed them (derived by hand from it): box at 1080p, 1024 spp."""
+    p, = _plan(host_check, f"w=1920,h=1080,spp=1024,{BOX}")
+    assert (p["pair"], p["pair_kernel"], p["quad"], p["drained"]) == (0, 0, 0, 0)
+    assert (p["refill"], p["leaf_kb"], p["xcd_run"], p["wg_rows"]) == (16, 4, 0, 16)
+    assert (p["nset"], p["chunk"], len(p["launches"])) == (3, 128, 26)
+    assert _sets(p) == [[128] * 8, [86] + [128] * 7 + [42], [43] + [128] * 7 + [85]]
+    assert p["set_rows"] == [368, 360, 352]
+
+
+def test_plan_small_frame_and_forced_sets(host_check):
+    """96 x 80 at 256 spp (test_gpu_parity.py test_launch_pipeline_bit_identical
+    asserts the same launch counts on the GPU: 1, 5, 8, 11 for pipe_sets 1..4).
+
+    With pipe_sets 0 the frame runs as one set in two launches of 128, not one of
+    256: the default three sets cap the chunk at max(128, ceil(256 / 8)) = 128
+    before the "only from 1024 spp on" rule takes the sets back to one, and the
+    cap stays.  One launch of 256 is what pipe_sets 1 gives, which is the case
+    the GPU test pins."""
+    one, zero, two, three, four = _plan(host_check, *(f"w=96,h=80,spp=256,{BOX},sets={k}" for k in (1, 0, 2, 3, 4)))
+    for p in (one, zero):
+        assert (p["quad"], p["drained"]) == (1, 1)   # 7,680 pixels <= resident lanes
+        assert (p["refill"], p["leaf_kb"], p["wg_rows"], p["nset"]) == (4, 2, 8, 1)
+    assert one["launches"] == [[0, 256]]
+    assert zero["launches"] == [[0, 128], [0, 128]]
+    assert [len(p["launches"]) for p in (two, three, four)] == [5, 8, 11]
+    assert two["launches"] == [[0, 128], [0, 128], [1, 64], [1, 128], [1, 64]]
+    assert two["order"] == [0, 2, 3, 1, 4]
+
+
+def test_plan_chunked_and_exact_schedules(host_check):
+    p, q, r = _plan(host_check, f"w=32,h=32,spp=12,spl=5,{BOX}", f"w=64,h=48,spp=8,sets=3,chunks=2,{BOX}",
+                    f"w=96,h=40,spp=1024,sets=3,{BOX}")
+    assert p["nset"] == 1 and _sets(p) == [[5, 5, 2]]
+    assert (q["nset"], q["chunk"], len(q["launches"])) == (3, 4, 8)
+    assert _sets(q) == [[4, 4], [3, 4, 1], [2, 4, 2]]
+    assert r["nset"] == 1   # 40 rows < 3 sets x 16 band rows
+
+
+def test_plan_pair_mode(host_check):
+    p, q = _plan(host_check, f"w=1920,h=1080,spp=4096,lights=1,{BOX}",
+                 f"w=1920,h=1080,spp=4096,lights=1,{BOX},flags=2")   # TPT_FLAG_REF_ORDER
+    assert (p["pair"], p["pair_kernel"]) == (1, 1)
+    assert (p["refill"], p["leaf_kb"], p["wg_rows"]) == (1, 1, 8)
+    assert (p["nset"], p["chunk"], len(p["launches"])) == (3, 256, 50)
+    assert _sets(p) == [[256] * 16, [171] + [256] * 15 + [85], [86] + [256] * 15 + [170]]
+    assert (q["pair"], q["pair_kernel"]) == (1, 0)
+    assert (q["refill"], q["leaf_kb"], q["wg_rows"]) == (16, 4, 16)   # the one-lane rules
+
+
+def test_plan_xcd_runs(host_check):
+    widths = (3840, 1920, 640, 256, 100)
+    big = _plan(host_check, *(f"w={w},h=64,spp=8,faces=131072" for w in widths))
+    assert [p["xcd_run"] for p in big] == [10, 5, 5, 2, 0]
+    small = _plan(host_check, *(f"w={w},h=64,spp=8,faces=16384" for w in widths))
+    assert [p["xcd_run"] for p in small] == [0] * 5
+
+
+def test_plan_lane_mode_per_rank(host_check):
+    """1920 wide, one rank's bands of 1080 rows (test_gpu_deal.py asserts the lane
+    mode and `drained` per rank on the GPU)."""
+    p8, p4, p2 = _plan(host_check, *(f"w=1920,h=1080,spp=1024,bc={n},bi=0,{BOX}" for n in (8, 4, 2)))
+    assert [p["bh"] for p in (p8, p4, p2)] == [144, 272, 544]   # 9, 17 and 34 whole bands (an eighth is 135 rows)
+    assert (p8["quad"], p8["drained"]) == (1, 1)                  # 276,480 pixels <= 327,680 resident lanes
+    assert (p4["quad"], p4["pair"], p4["drained"]) == (0, 0, 1)   # 522,240 < twice the resident lanes
+    assert (p2["quad"], p2["pair"], p2["drained"]) == (0, 0, 0)
+
+
+def test_plan_explicit_deal(host_check):
+    p, = _plan(host_check, f"w=96,h=96,spp=8,sets=2,chunks=2,list=5:1:3:0:2,{BOX}")
+    assert p["nset"] == 2
+    assert p["set_list"] == [[5, 3, 2], [1, 0]]
+    assert p["set_rows"] == [48, 32]
+    assert p["set_off"] == [5, 8]   # behind the whole list, back to back
+
+
+def test_plan_argument_errors(host_check):
+    a, b, c = _plan(host_check, f"w=64,h=64,spp=8,lanes=3,{BOX}", f"w=64,h=64,spp=8,lanes=4,lights=1,{BOX}",
+                    f"w=64,h=1080,rows=1080,frames=65535,spp=8,lanes=1,{BOX}")
+    assert a == {"status": 1, "message": "lanes_per_pixel: 0, 1, 2 or 4"}
+    assert b == {"status": 1, "message": "lanes_per_pixel 4: scenes without delta lights, no env IS, ordered "
+                                         "traversal, stacks in LDS"}
+    assert c == {"status": 1, "message": "frame batch too large for one launch"}
+
+
+def test_plan_invariants_random_sweep(host_check):
+    """500 seeded random cases; the harness checks that every set's samples sum to
+    spp, inner launches are whole chunks, the issue order is a permutation that
+    keeps each set's order, the sets' rows sum to the call's and their shares
+    partition an explicit list."""
+    r = subprocess.run([host_check, "plan-sweep", "500", "20"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.startswith("ok plan sweep"), r.stdout + r.stderr[-3000:]
+    assert int(r.stdout.split()[3]) >= 400   # (a few cases may end in an argument error)
 
 
 def test_wide_tree_pool_under_tsan():

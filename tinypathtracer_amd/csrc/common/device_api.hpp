@@ -60,7 +60,7 @@ struct TraceArgs {
     // env (nullable)
     const uint32_t* env;                 // RGBA8 packed, row 0 = bottom
     int32_t env_w, env_h;
-    // env importance sampling (A15) over blocks of is_b x is_b texels (api.cpp build_env_is)
+    // env importance sampling (A15) over blocks of is_b x is_b texels (api_scene.cpp build_env_is)
     int32_t is_b, is_bw, is_bh;          // block side; blocks per block row; block rows
     const float* is_cond;                //   block-row prefix sums [bh][bw]
     const float* is_row;                 //   block-row sums [bh]

@@ -1,0 +1,285 @@
+// api_post.cpp -- the post-pass entry points of the C-ABI (post.hip): tpt_render_aov,
+// tpt_denoise, tpt_history_* and tpt_temporal.  Each takes its buffers from either
+// side: host buffers go through the device staging the scene / history keeps
+// (api_internal.hpp Staging).
+#include <cmath>
+
+#include "api_internal.hpp"
+
+namespace {
+
+constexpr size_t kCountWords = (size_t)tpt::kTemporalSlots * tpt::kTemporalSlotStride;
+
+// Inverse of a column-major 4x4 matrix by Gauss-Jordan elimination with partial
+// pivoting in double, rounded to float.  false: singular.
+bool invert4(const float* m, float* out) {
+    double a[4][8];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            a[i][j] = (double)m[4 * j + i];
+            a[i][4 + j] = i == j ? 1.0 : 0.0;
+        }
+    for (int c = 0; c < 4; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 4; ++r)
+            if (std::fabs(a[r][c]) > std::fabs(a[piv][c])) piv = r;
+        if (!(std::fabs(a[piv][c]) > 0.0)) return false;
+        if (piv != c)
+            for (int j = 0; j < 8; ++j) std::swap(a[c][j], a[piv][j]);
+        const double d = 1.0 / a[c][c];
+        for (int j = 0; j < 8; ++j) a[c][j] *= d;
+        for (int r = 0; r < 4; ++r) {
+            if (r == c) continue;
+            const double f = a[r][c];
+            if (f != 0.0)
+                for (int j = 0; j < 8; ++j) a[r][j] -= f * a[c][j];
+        }
+    }
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) out[4 * j + i] = (float)a[i][4 + j];
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// First-hit feature buffers (post.hip k_aov): the whole frame, one ray per pixel
+// centre.  Host outputs are written to the scene's staging buffers and copied back.
+tpt_status tpt_render_aov(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_t H, const tpt_aov* out,
+                          double* trace_ms) {
+    if (!s || !s->built) return fail(TPT_ERR_INVALID_ARG, "scene not built");
+    if (!cam || !out) return fail(TPT_ERR_INVALID_ARG, "null argument");
+    if (W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size");
+    if (!out->albedo && !out->normal && !out->depth && !out->face && !out->material)
+        return fail(TPT_ERR_INVALID_ARG, "no feature buffer requested: every pointer of out is null");
+    {
+        const tpt_status bs = finish_pending(s);
+        if (bs != TPT_OK) return bs;
+    }
+    DeviceGuard g(s->device);
+    hipStream_t st = s->stream;
+    const size_t npix = (size_t)W * (size_t)H;
+    tpt::TraceArgs a{};
+    fill_trace_args(s, nullptr, cam, a);
+    a.width = W;
+    a.height = H;
+    a.inv_w = 1.0f / (float)W;
+    a.inv_h = 1.0f / (float)H;
+    tpt::AovArgs o{};
+    Staging sg(st);
+    HIP_OR_FAIL(sg.out(s->aov_f3[0], out->albedo, 3 * npix, &o.albedo));
+    HIP_OR_FAIL(sg.out(s->aov_i[0], out->face, npix, &o.face));
+    HIP_OR_FAIL(sg.out(s->aov_f3[1], out->normal, 3 * npix, &o.normal));
+    HIP_OR_FAIL(sg.out(s->aov_i[1], out->material, npix, &o.material));
+    HIP_OR_FAIL(sg.out(s->aov_depth, out->depth, npix, &o.depth));
+    HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
+    HIP_OR_FAIL(tpt::launch_aov(a, o, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
+    HIP_OR_FAIL(sg.finish());
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    if (trace_ms) {
+        float ms = 0.0f;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        *trace_ms = ms;
+    }
+    return TPT_OK;
+}
+
+// The a-trous denoiser (post.hip; DESIGN.md section 5 "Post-pass"): pack, one launch
+// per iteration between the two colour planes, resolve.  Host inputs are uploaded
+// to the scene's staging buffers, host outputs copied back from them.
+tpt_status tpt_denoise(tpt_scene* s, int32_t W, int32_t H, const float* radiance_in, const tpt_aov* guides,
+                       const tpt_denoise_params* p, float* radiance_out, uint8_t* bgra_out,
+                       tpt_denoise_stats* stats) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (!radiance_in || !guides || !p) return fail(TPT_ERR_INVALID_ARG, "null argument");
+    if (!guides->albedo || !guides->normal || !guides->depth)
+        return fail(TPT_ERR_INVALID_ARG, "the denoiser needs the albedo, normal and depth guides");
+    if (W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size");
+    if (p->iterations < 0 || p->iterations > 8) return fail(TPT_ERR_INVALID_ARG, "iterations must be 0..8");
+    if (!(p->sigma_color > 0.0f) || !(p->sigma_normal > 0.0f) || !(p->sigma_depth > 0.0f))
+        return fail(TPT_ERR_INVALID_ARG, "sigma_color, sigma_normal and sigma_depth must be > 0");
+    if (p->flags & ~(TPT_DENOISE_DEMODULATE | TPT_DENOISE_DIRECT)) return fail(TPT_ERR_INVALID_ARG, "unknown denoise flags");
+    if (!radiance_out && !bgra_out) return fail(TPT_ERR_INVALID_ARG, "no output buffer");
+    DeviceGuard g(s->device);
+    hipStream_t st = s->stream;
+    const size_t npix = (size_t)W * (size_t)H;
+    // iterations 0: the input bit for bit, so no demodulation round trip
+    const bool demod = (p->flags & TPT_DENOISE_DEMODULATE) && p->iterations > 0;
+    HIP_OR_FAIL(s->dn_color[0].alloc(npix));
+    HIP_OR_FAIL(s->dn_color[1].alloc(npix));
+    HIP_OR_FAIL(s->dn_guide.alloc(npix));
+    tpt::DenoiseArgs d{};
+    d.npix = npix;
+    d.width = W;
+    d.height = H;
+    d.demodulate = demod ? 1 : 0;
+    d.color0 = s->dn_color[0].p;
+    d.guide = s->dn_guide.p;
+    Staging sg(st);
+    HIP_OR_FAIL(sg.in(s->dn_rad, radiance_in, 3 * npix, &d.radiance_in));
+    HIP_OR_FAIL(sg.in(s->dn_f3[0], guides->albedo, 3 * npix, &d.albedo));
+    HIP_OR_FAIL(sg.in(s->dn_f3[1], guides->normal, 3 * npix, &d.normal));
+    HIP_OR_FAIL(sg.in(s->dn_depth, guides->depth, npix, &d.depth));
+    // radiance in and out share dn_rad: pack has read it by the time resolve writes it
+    HIP_OR_FAIL(sg.out(s->dn_rad, radiance_out, 3 * npix, &d.radiance_out));
+    // alpha is untouched: the caller's bytes go up first
+    HIP_OR_FAIL(sg.inout(s->dn_bgra, bgra_out, 4 * npix, &d.bgra));
+    HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
+    HIP_OR_FAIL(tpt::launch_denoise_pack(d, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
+    tpt::AtrousArgs f{};
+    f.guide = s->dn_guide.p;
+    f.width = W;
+    f.height = H;
+    constexpr double kFltMax = 3.402823466e+38;
+    f.inv_sn2 = (float)std::min(1.0 / ((double)p->sigma_normal * p->sigma_normal), kFltMax);
+    f.sz2 = (float)((double)p->sigma_depth * p->sigma_depth);
+    const bool use_lds = !(p->flags & TPT_DENOISE_DIRECT);
+    for (int i = 0; i < p->iterations; ++i) {
+        f.src = s->dn_color[i & 1].p;
+        f.dst = s->dn_color[(i + 1) & 1].p;
+        f.step = 1 << i;
+        const double sc = (double)p->sigma_color / (double)(1 << i);   // sigma_c,i = sigma_color 2^-i
+        f.inv_sc2 = (float)std::min(1.0 / (sc * sc), kFltMax);
+        HIP_OR_FAIL(tpt::launch_atrous(f, use_lds, st));
+    }
+    HIP_OR_FAIL(hipEventRecord(s->ev[2], st));
+    d.color0 = s->dn_color[p->iterations & 1].p;
+    HIP_OR_FAIL(tpt::launch_denoise_resolve(d, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[3], st));
+    HIP_OR_FAIL(sg.finish());
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    if (stats) {
+        float ms = 0.0f;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        stats->pack_ms = ms;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
+        stats->filter_ms = ms;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+        stats->resolve_ms = ms;
+    }
+    return TPT_OK;
+}
+
+// Temporal reprojection and accumulation (post.hip k_temporal; DESIGN.md section 5
+// "Post-pass").  The handle keeps the two sets of state planes, the previous call's
+// camera and the device staging of host buffers.
+tpt_status tpt_history_create(tpt_scene* s, int32_t W, int32_t H, tpt_history** out) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (!out) return fail(TPT_ERR_INVALID_ARG, "null out");
+    if (W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size");
+    DeviceGuard g(s->device);
+    std::unique_ptr<tpt_history> h(new tpt_history);
+    h->scene = s;
+    h->device = s->device;
+    h->width = W;
+    h->height = H;
+    const size_t npix = (size_t)W * (size_t)H;
+    for (auto& set : h->state)
+        for (auto& plane : set) HIP_OR_FAIL(plane.alloc(npix));
+    HIP_OR_FAIL(h->count.alloc(kCountWords));
+    HIP_OR_FAIL(h->h_count.alloc(kCountWords));
+    for (auto& e : h->ev) HIP_OR_FAIL(hipEventCreate(&e));
+    *out = h.release();
+    return TPT_OK;
+}
+
+tpt_status tpt_history_reset(tpt_history* h) {
+    if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
+    h->valid = false;
+    return TPT_OK;
+}
+
+void tpt_history_destroy(tpt_history* h) { delete h; }
+
+tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radiance_in, const tpt_aov* guides,
+                        const tpt_temporal_params* p, float* radiance_out, float* variance_out,
+                        float* history_len_out, uint8_t* bgra_out, tpt_temporal_stats* stats) {
+    if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
+    if (!cam) return fail(TPT_ERR_INVALID_ARG, "null camera");
+    if (!radiance_in) return fail(TPT_ERR_INVALID_ARG, "null radiance_in");
+    if (!guides) return fail(TPT_ERR_INVALID_ARG, "null guides");
+    if (!p) return fail(TPT_ERR_INVALID_ARG, "null params");
+    if (p->flags & ~(TPT_TEMPORAL_DEMODULATE | TPT_TEMPORAL_TILES)) return fail(TPT_ERR_INVALID_ARG, "unknown temporal flags");
+    const bool demod = (p->flags & TPT_TEMPORAL_DEMODULATE) != 0;
+    if (!guides->normal || !guides->depth || !guides->material)
+        return fail(TPT_ERR_INVALID_ARG, "temporal accumulation needs the normal, depth and material guides");
+    if (demod && !guides->albedo)
+        return fail(TPT_ERR_INVALID_ARG, "TPT_TEMPORAL_DEMODULATE needs the albedo guides");
+    if (!(p->alpha > 0.0f && p->alpha <= 1.0f)) return fail(TPT_ERR_INVALID_ARG, "alpha must be in (0, 1]");
+    if (!(p->depth_tol > 0.0f)) return fail(TPT_ERR_INVALID_ARG, "depth_tol must be > 0");
+    if (!(p->normal_min >= -1.0f && p->normal_min <= 1.0f))
+        return fail(TPT_ERR_INVALID_ARG, "normal_min must be in [-1, 1]");
+    if (p->max_history < 1 || p->max_history > 65536) return fail(TPT_ERR_INVALID_ARG, "max_history must be 1..65536");
+    if (!radiance_out && !bgra_out) return fail(TPT_ERR_INVALID_ARG, "no output buffer: radiance_out and bgra_out are null");
+    tpt_scene* s = h->scene;
+    DeviceGuard g(s->device);
+    hipStream_t st = s->stream;
+    const int W = h->width, H = h->height;
+    const size_t npix = (size_t)W * (size_t)H;
+    tpt::TemporalArgs a{};
+    const CameraConsts cc = camera_consts(cam);
+    set_camera(a, cc);
+    a.inv_w = 1.0f / (float)W;
+    a.inv_h = 1.0f / (float)H;
+    a.has_prev = h->valid ? 1 : 0;
+    std::memcpy(a.prev_inv, h->prev_inv, sizeof a.prev_inv);
+    std::memcpy(a.prev_origin, h->prev.origin, sizeof a.prev_origin);
+    a.prev_sensor_w = h->prev.sensor_w;
+    a.prev_sensor_h = h->prev.sensor_h;
+    a.prev_half_sw = h->prev.half_sw;
+    a.prev_half_sh = h->prev.half_sh;
+    a.width = W;
+    a.height = H;
+    a.demodulate = demod ? 1 : 0;
+    a.tiles = (p->flags & TPT_TEMPORAL_TILES) ? 1 : 0;
+    a.alpha = p->alpha;
+    a.depth_tol = p->depth_tol;
+    a.normal_min = p->normal_min;
+    a.max_history = (float)p->max_history;
+    // host buffers are staged on the device: inputs go up, outputs come back
+    Staging sg(st);
+    HIP_OR_FAIL(sg.in(h->st_rad, radiance_in, 3 * npix, &a.radiance_in));
+    HIP_OR_FAIL(sg.in(h->st_f3[0], demod ? guides->albedo : nullptr, 3 * npix, &a.albedo));
+    HIP_OR_FAIL(sg.in(h->st_f3[1], guides->normal, 3 * npix, &a.normal));
+    HIP_OR_FAIL(sg.in(h->st_depth, guides->depth, npix, &a.depth));
+    HIP_OR_FAIL(sg.in(h->st_mtl, guides->material, npix, &a.material));
+    // radiance in and out share st_rad: a lane reads its pixel before it writes it
+    HIP_OR_FAIL(sg.out(h->st_rad, radiance_out, 3 * npix, &a.radiance_out));
+    HIP_OR_FAIL(sg.out(h->st_var, variance_out, npix, &a.variance_out));
+    HIP_OR_FAIL(sg.out(h->st_len, history_len_out, npix, &a.history_out));
+    // alpha is untouched: the caller's bytes go up first
+    HIP_OR_FAIL(sg.inout(h->st_bgra, bgra_out, 4 * npix, &a.bgra));
+    const int from = h->cur, to = h->cur ^ 1;
+    for (int k = 0; k < 3; ++k) {
+        a.prev[k] = h->state[from][k].p;
+        a.next[k] = h->state[to][k].p;
+    }
+    a.reprojected = h->count.p;
+    HIP_OR_FAIL(hipMemsetAsync(h->count.p, 0, kCountWords * sizeof(unsigned long long), st));
+    HIP_OR_FAIL(hipEventRecord(h->ev[0], st));
+    HIP_OR_FAIL(tpt::launch_temporal(a, st));
+    HIP_OR_FAIL(hipEventRecord(h->ev[1], st));
+    HIP_OR_FAIL(sg.finish());
+    HIP_OR_FAIL(hipMemcpyAsync(h->h_count.p, h->count.p, kCountWords * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    unsigned long long found = 0;
+    for (int k = 0; k < tpt::kTemporalSlots; ++k) found += h->h_count.p[(size_t)k * tpt::kTemporalSlotStride];
+    // the new state and this camera replace the old
+    h->cur = to;
+    h->valid = true;
+    if (!invert4(cam->c2w, h->prev_inv)) h->valid = false;   // a singular c2w: nothing can be reprojected into it
+    h->prev = cc;
+    if (stats) {
+        float ms = 0.0f;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        stats->kernel_ms = ms;
+        stats->reprojected = found;
+    }
+    return TPT_OK;
+}
+
+}  // extern "C"

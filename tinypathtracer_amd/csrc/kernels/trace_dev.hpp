@@ -770,7 +770,7 @@ __device__ __forceinline__ void emit_probe_inline(Trav& r, const float4* __restr
 // pre-test").  The probe only adds the emission of its closest hit, and an
 // emissive triangle can be that hit only if the probe's line passes its leaf
 // box (rayHitBBox, :61-107), which lies inside one of the boxes a.emit_box
-// (api.cpp emitter_boxes).  This is the slab test of those boxes with the
+// (api_scene.cpp emitter_boxes).  This is the slab test of those boxes with the
 // hardware's approximate reciprocal (v_rcp_f32, 1 ulp) instead of the
 // correctly rounded 1/d, and it answers "miss" only when the slab intervals
 // fail to overlap by more than 2^-16 (|T0| + |T1|).  Every t it computes is
@@ -1103,7 +1103,7 @@ __device__ __forceinline__ int lower_bound_guided(const float* __restrict__ a, i
 
 // x1, x2: the two uniforms, drawn by the pixel's path lane in RNG order (pair
 // mode hands them to the side lane with the bounce's shadow job).  The
-// distribution is piecewise constant over blocks of B x B texels (api.cpp
+// distribution is piecewise constant over blocks of B x B texels (api_scene.cpp
 // build_env_is): a block row by the marginal CDF, a block by that row's CDF,
 // the remapped uniforms as the position inside the block (x0 + f2 * width,
 // y0 + f1 * height in texels), and the pdf from the CDF steps the two

@@ -112,7 +112,7 @@ def cost_deal(costs, world: int, max_iter: int = 2000, order: str = "ascending",
 def set_balanced_order(bands, costs, nset: int = 3, short_band=None):
     """One rank's bands ordered so that the launch pipeline's band sets carry
     equal costs.  tpt_render splits a listed share into nset sets on their own
-    streams, set k taking list entries k, k + nset, ... (api.cpp); the sets run
+    streams, set k taking list entries k, k + nset, ... (launch_plan.cpp); the sets run
     side by side and the last one to finish ends the frame, so a share whose
     bands do not divide evenly -- or whose few light bands fall into one set --
     ends on its heaviest set.  Set k gets ceil((n - k) / nset) slots; the bands
