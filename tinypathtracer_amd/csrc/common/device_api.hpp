@@ -47,8 +47,12 @@ struct TraceArgs {
     const float4* inner;
     const float4* inner4;
     int32_t n4;                          // 4-wide nodes
-    int32_t lds_nodes;                   // set by launch_trace: 4-wide nodes [0, lds_nodes) staged in LDS
-    int32_t lds_nodes_offset;            // set by launch_trace: their byte offset in LDS
+    // Always 0 / the stack's offset (launch_trace).  k_trace's prologue still runs its staging loop
+    // over 8 * lds_nodes float4 (the withdrawn "top nodes in LDS" experiment):
+    // taking the loop out changes the register allocation of 21 k_trace variants (C2's among them:
+    // 9 -> 16 spilled VGPRs), so it waits for a change that is measured on its own.
+    int32_t lds_nodes;
+    int32_t lds_nodes_offset;
     const float4* tri;
     const float4* shade;
     const float4* mtl;
@@ -95,7 +99,6 @@ struct TraceArgs {
     int32_t boxes_finite;                // all node boxes finite: min/max slab test is exact
     int32_t any_emitter;                 // some triangle emits (else a direct probe adds nothing)
     int32_t emit_root;                   // inner4 id of the emissive-triangle tree (-1: none)
-    int32_t emit_inline;                 // that tree is one node of leaves: probe pass 1 in the shading pass
     // Boxes enclosing every emissive triangle's leaf box (the emissive tree
     // root's child boxes, overlapping ones merged): (lo.xyz, 0), (hi.xyz, 0) per
     // box.  A direct probe whose line misses all of them by a margin can hit no
@@ -112,9 +115,6 @@ struct TraceArgs {
     int32_t quad;                        // 1: four lanes per pixel, each node visit split over them (k_trace QUAD)
     int32_t xcd_run;                     // > 0: workgroup tiles dealt to XCDs in runs of this many (k_trace)
     int32_t xcd_rot;                     // the runs' XCD rotation of this launch (its chunk of the set's spp)
-    int32_t tile_pool;                   // 1: each workgroup renders two adjacent tiles, the second as a pixel
-                                         //    pool its finished lanes draw from (k_trace; set by launch_trace)
-    int32_t lds_pool_offset;             // set by launch_trace: byte offset of the pool counter in LDS
     int32_t lds_rec_offset;              // set by launch_trace: byte offset of the record region
     int32_t rec_lds_levels;              // set by launch_trace: path-record levels held in LDS
     int32_t stack_lds_slots;             // set by launch_trace: stack slots held in LDS (rest private)

@@ -298,7 +298,6 @@ struct tpt_scene {
     int32_t n4 = 0;
     int32_t wide_tree = 0;                  // 1: inner4 holds the SAH 4-wide tree (wide_bvh.cpp)
     int32_t emit_root = -1;                 // inner4 id of the emissive-triangle tree's root (-1: none)
-    int32_t emit_inline = 0;                // that tree is one node of leaves (<= 4 emitters)
     float emit_box[24] = {};                // boxes around the emitters' leaf boxes (TraceArgs emit_box)
     int32_t n_emit_box = 0;
     int32_t slivers = 0;                    // sliver triangles (trace.hip "Culling"), re-tested after traversal

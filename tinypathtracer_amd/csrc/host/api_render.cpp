@@ -35,19 +35,11 @@ void tpt::host::fill_trace_args(tpt_scene* s, const tpt_env* env, const tpt_came
         a.emit_box[2 * k] = make_float4(b[0], b[1], b[2], 0.0f);
         a.emit_box[2 * k + 1] = make_float4(b[3], b[4], b[5], 0.0f);
     }
-#ifdef TPT_NO_PROBE_PRETEST
-    a.n_emit_box = 0;   // A/B builds: no probe pre-test
-#endif
     a.sliver_groups = s->sliver_groups.p;
     a.sliver_list = s->sliver_list.p;
     a.n_sliver_groups = s->n_sliver_groups;
     a.cull_eps = s->cull_eps;
     a.graze = 1;
-#ifdef TPT_NO_EMIT_INLINE
-    a.emit_inline = 0;   // A/B builds: probe pass 1 as a traversal always
-#else
-    a.emit_inline = s->emit_inline;
-#endif
     a.env = env ? env->texels.p : nullptr;
     a.env_w = env ? env->w : 0;
     a.env_h = env ? env->h : 0;

@@ -205,7 +205,6 @@ tpt_status upload_host_trees(tpt_scene* s, HostTrees& j, uint32_t* wide_need) {
         HIP_OR_FAIL(hipMemcpyAsync(s->inner4.p + 8 * (size_t)s->n4, j.e4.data(), j.e4.size() * sizeof(float),
                                    hipMemcpyHostToDevice, s->stream));
         s->emit_root = s->n4;
-        s->emit_inline = j.ne4 == 1 ? 1 : 0;
         s->n_emit_box = emitter_boxes(j.e4.data(), s->emit_box);
         *wide_need = std::max(*wide_need, (uint32_t)j.eneed);
     }
@@ -320,7 +319,6 @@ tpt_status scene_build(tpt_scene* s, bool async) {
     uint32_t wide_need = 3 * ((td + 1) / 2) + 1;
     s->wide_tree = 0;
     s->emit_root = -1;
-    s->emit_inline = 0;
     s->n_emit_box = 0;
     s->slivers = 0;
     s->n_sliver_groups = 0;

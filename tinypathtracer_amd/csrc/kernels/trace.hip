@@ -27,6 +27,8 @@
 //    LDS or not, 16/32-bit stack ids, record depth 8/64; the reference order
 //    and the opt-in env importance sampling have one general variant each;
 //  * triangles are pre-gathered (v0, e1, e2, fid: three 16-B loads).
+#include <type_traits>
+
 #include "trace_dev.hpp"
 
 namespace tpt {
@@ -81,23 +83,6 @@ __device__ __noinline__ void verify_ray(const TraceArgs& a, const Trav& r, int p
 }
 #endif
 
-// Pair mode's mid-pass exchange (round 6): 1 in every pair variant, 2 only with env
-// importance sampling, 0 off (the side lanes' sums then reach their path lanes at the
-// end of the pass only).
-#ifndef TPT_PAIR_MID
-#define TPT_PAIR_MID 2
-#endif
-
-// Shadow rays' first step in the pass (round 6): a fresh shadow ray (delta light or env
-// sample) takes its root visit before the wave enters the traversal loop; when no
-// child of the root passes, the ray is finished there, and the wave runs its shading
-// pass again before traversing, so a side lane's next shadow ray (or its direct sum)
-// follows at once instead of after the traversal round.  The same visit, the same
-// counters: the frame is the same.  1 on, 0 off.
-#ifndef TPT_SHADOW_FIRST
-#define TPT_SHADOW_FIRST 0
-#endif
-
 // LIGHTS == false (no delta lights, packed 2-word records): the shadow-ray
 // state (direct term, normal, light index, incoming direction -- r.d during an
 // extension ray) is dead across traversals and drops out of the registers.
@@ -115,8 +100,8 @@ __device__ __noinline__ void verify_ray(const TraceArgs& a, const Trav& r, int p
 // each level's direct term is the same sum in the same order: the image is
 // bit-identical.  A pixel's sample chain then pays one traversal per bounce
 // instead of 1 + lights, which is what bounds tail-heavy frames (C3).
-template <int MAXD, bool ORDERED, bool LIGHTS, bool MTL_LDS, typename StackT, bool ENVIS = false, bool INL = false,
-          bool PAIR = false, bool DRAIN = false, bool QUAD = false, bool NOEMIT = false>
+template <int MAXD, bool ORDERED, bool LIGHTS, bool MTL_LDS, typename StackT, bool ENVIS = false, bool PAIR = false,
+          bool DRAIN = false, bool QUAD = false, bool NOEMIT = false>
 __global__ __launch_bounds__(256, ENVIS ? TPT_TRACE_WAVES_IS
                                         : (PAIR ? TPT_TRACE_WAVES_PAIR
                                                 : (QUAD ? TPT_TRACE_WAVES_QUAD
@@ -148,35 +133,26 @@ void k_trace(TraceArgs a) {
         bx = ((m / g) * 8 + k) * g + m % g;
     }
     const int frame = by % nfr;
-    // Pixel pool (round 4; DESIGN.md section 5 "Round 4: N1"): workgroup b renders
-    // tiles 2b and 2b + 1 of its row.  Its lanes start on the first; a lane whose
-    // pixel has run all its samples stores it and takes the next unclaimed pixel
-    // of the second (an LDS counter), so the lanes of cheap pixels (misses, walls)
-    // keep working while their wave's heavy pixels finish.  Every pixel still runs
-    // all its samples in order on one lane with its own XORWOW stream: the image
-    // is bit-identical to one tile per workgroup.
-    const bool pool = !PAIR && !DRAIN && TPT_TILE_POOL && a.tile_pool > 0;
-    const int tx = pool ? 2 * bx : bx;
     // pair mode: lane 2q (path) and 2q + 1 (side) serve pixel q of the wave's 8x4 tile
     const bool side = PAIR && (lane & 1);
     // QUAD: lanes 4q..4q+3 all run pixel q of the wave's 4x4 tile (8x8 pixels per
     // workgroup) with the same state; lane 4q (lead) counts and stores it
     const bool lead = !QUAD || (lane & 3) == 0;
     const int pl = PAIR ? (lane >> 1) : (QUAD ? (lane >> 2) : lane);   // pixel slot in the wave
-    int x = QUAD ? tx * 8 + (wave & 1) * 4 + (pl & 3) : tx * 16 + (wave & 1) * 8 + (pl & 7);
+    const int x = QUAD ? bx * 8 + (wave & 1) * 4 + (pl & 3) : bx * 16 + (wave & 1) * 8 + (pl & 7);
     const int ly = PAIR   ? (by / nfr) * 8 + (wave >> 1) * 4 + (pl >> 3)
                    : QUAD ? (by / nfr) * 8 + (wave >> 1) * 4 + (pl >> 2)
                           : (by / nfr) * 16 + (wave >> 1) * 8 + (pl >> 3);
-    int y = band_row(ly, a.band_rows, a.band_count, a.band_index, a.band_list);
+    const int y = band_row(ly, a.band_rows, a.band_count, a.band_index, a.band_list);
     const bool pixel = x < a.width && ly < a.band_height && y < a.height;
     // cost-balanced deals (tpt_params.band_cost): the wave's life in s_memrealtime
     // ticks, charged to the global band of its first row (lane 0's)
     const unsigned long long t_cost0 = a.band_cost ? wall_clock64() : 0ull;
-    bool active = pixel && !side;   // owns the pixel's RNG stream and sums
+    const bool active = pixel && !side;   // owns the pixel's RNG stream and sums
     uint32_t c_trav = 0, c_inner = 0, c_wide = 0, c_leaf = 0, c_shade = 0, c_ovf = 0;
     uint32_t c_local = 0;   // rays resolved in the shading pass without a BVH traversal
     const size_t npix = (size_t)a.width * (size_t)a.height;
-    size_t off = active ? (size_t)x + (size_t)y * (size_t)a.width : 0;
+    const size_t off = active ? (size_t)x + (size_t)y * (size_t)a.width : 0;
     // frame batch: each frame owns its own RNG and accumulator planes
     uint32_t* const g_rng = a.rng + (size_t)frame * 6 * npix;
     float* const g_acc = a.accum + (size_t)frame * 3 * npix;
@@ -195,8 +171,7 @@ void k_trace(TraceArgs a) {
             smtl[i].w = m.w;
         }
     }
-    // the top 4-wide nodes (breadth-first prefix of inner4): every ray starts
-    // there, so their loads become LDS reads
+    // a.lds_nodes is always 0 (device_api.hpp says why this loop is still here)
     TPT_LDS LdsF4* snodes = (TPT_LDS LdsF4*)(slds + a.lds_nodes_offset);
     for (int i = tid; i < 8 * a.lds_nodes; i += 256) {
         const float4 m = a.inner4[i];
@@ -205,9 +180,7 @@ void k_trace(TraceArgs a) {
         snodes[i].z = m.z;
         snodes[i].w = m.w;
     }
-    TPT_LDS int* pool_next = (TPT_LDS int*)(slds + a.lds_pool_offset);   // next unclaimed pixel of tile 2b + 1
-    if (pool && tid == 0) *pool_next = (tx + 1) * 16 < a.width ? 0 : 256;   // (no second tile: an empty pool)
-    if (MTL_LDS || a.lds_nodes > 0 || pool) __syncthreads();
+    if (MTL_LDS || a.lds_nodes > 0) __syncthreads();
     auto MT = [&](int i) -> float4 {
         if constexpr (MTL_LDS) {
             return make_float4(smtl[i].x, smtl[i].y, smtl[i].z, smtl[i].w);
@@ -217,8 +190,7 @@ void k_trace(TraceArgs a) {
     };
     // (QUAD: one stack per quad in its four lanes' columns; the host keeps it all in LDS)
     LaneStack<StackT, QUAD> stk;
-    stk.lds = (TPT_LDS StackT*)(slds + a.lds_stack_offset) +
-              (QUAD ? (tid & ~3) : ((TPT_STACK_PAIRED && sizeof(StackT) == 2) ? 2 * tid : tid));
+    stk.lds = (TPT_LDS StackT*)(slds + a.lds_stack_offset) + (QUAD ? (tid & ~3) : tid);
     stk.nlds = a.stack_lds_slots;
     PathRecords<MAXD, PAIR ? 128 : 256> rec;
     rec.lds = (TPT_LDS float*)(slds + a.lds_rec_offset) + (PAIR ? wave * 32 + pl : tid);
@@ -327,15 +299,13 @@ void k_trace(TraceArgs a) {
             t_iter0 = now;
         }
 #endif
-#ifndef TPT_NO_SLIVERS
         if (ORDERED && a.n_sliver_groups > 0) {   // (uniform) slivers after a culled traversal (Culling)
             if (ts == TS_DONE && sl_pend) {
                 sl_pend = false;
                 sliver_pass(r, a, c_leaf);
             }
         }
-#endif
-        if (TPT_GRAZE_HIT && ORDERED && !NOEMIT && ts == TS_DONE && phase == PH_PROBE && r.fin && r.fid >= 0 && r.mode == TM_EMIT &&
+        if (ORDERED && !NOEMIT && ts == TS_DONE && phase == PH_PROBE && r.fin && r.fid >= 0 && r.mode == TM_EMIT &&
             a.graze && grazing(Surf{a.shade[3 * r.fid + 1].w, a.shade[3 * r.fid + 2].w}, r.d)) {
             // a grazing probe hit (Culling: "Grazing hits"): pass 1 again on the
             // uncull'd binary path, which tests every leaf whose box its line passes
@@ -359,7 +329,7 @@ void k_trace(TraceArgs a) {
             vpend = false;
             // (an extension hit the shading prelude will trace again -- the grazing-hit
             // rule -- is verified after that traversal)
-            if (!(TPT_GRAZE_HIT && phase == PH_EXT && r.fin && r.fid >= 0 && a.graze &&
+            if (!(phase == PH_EXT && r.fin && r.fid >= 0 && a.graze &&
                   grazing(Surf{a.shade[3 * r.fid + 1].w, a.shade[3 * r.fid + 2].w}, r.d)))
                 verify_ray(a, r, phase, a.mtl);
         }
@@ -372,7 +342,6 @@ void k_trace(TraceArgs a) {
         // its level in this pass unwinds in this pass instead of waiting for the next.
         const bool in_pass = ts == TS_DONE;
         bool finish = false;   // the path ends this pass: unwind
-        bool begun = false;    // the next ray is already set up (inline probe pass 1)
         bool redo = false;     // a grazing extension hit: traced again, uncull'd
         bool shadow = false;   // the next ray is a shadow ray
         bool tg = false;       // the next ray leaves its face within 1e-3 of its plane (grazing())
@@ -381,8 +350,6 @@ void k_trace(TraceArgs a) {
             TPT_SEC_BEGIN()
             // ---- consume the finished traversal (nothing yet for a fresh sample) ----
             bool lights_next = false, after = false;
-            Hemi hb;              // this pass's hemisphere frame (new_direction), shared by the
-            bool hb_ok = false;   // bounce's extension sample and its direct probe
             if (!LIGHTS) rd = r.d;   // the extension ray's direction (unused otherwise)
             Surf gpass = gsurf;   // the face this pass's new rays leave
             if (phase == PH_EXT) {
@@ -395,7 +362,7 @@ void k_trace(TraceArgs a) {
                     // the grazing-hit rule (Culling: "Grazing hits"): a culled walk's hit
                     // within 1e-3 of the face's plane is not shaded; the same ray is traced
                     // again on the uncull'd binary path (ray set-up below, not counted)
-                    redo = TPT_GRAZE_HIT && ORDERED && r.fin && a.graze && grazing(Surf{s1.w, s2.w}, rd);
+                    redo = ORDERED && r.fin && a.graze && grazing(Surf{s1.w, s2.w}, rd);
                     if (!redo) {
                         ++c_shade;
                         const float w = 1.0f - r.u - r.v;
@@ -407,7 +374,7 @@ void k_trace(TraceArgs a) {
                         const int mtl = __float_as_int(s0.w);
                         const float4 m1 = MT(2 * mtl + 1);
                         float af;
-                        const float prob = new_direction(rd, nrm, m1.x, m1.y, st, nd, af, hb, hb_ok);
+                        const float prob = new_direction(rd, nrm, m1.x, m1.y, st, nd, af);
                         graze_next = grazing(gpass, nd);
                         rec.put(depth, 0, af);
                         mk = (uint32_t)mtl | (p_kind(prob) << 30);
@@ -504,9 +471,8 @@ void k_trace(TraceArgs a) {
                         ts = TS_IDLE;
                     } else if (!(m1.x >= 1.0f || m1.y > 0.0f)) {   // direct probe (:387-389)
                         float af2;
-                        if (!TPT_SHARE_HEMI) hb_ok = false;   // (A/B builds: the frame recomputed)
-                        new_direction(rd, nrm, m1.x, m1.y, st, td, af2, hb, hb_ok);
-                        if ((TPT_PROBE_SHORTCUT && ORDERED && (NOEMIT || !a.any_emitter)) ||
+                        new_direction(rd, nrm, m1.x, m1.y, st, td, af2);
+                        if ((ORDERED && (NOEMIT || !a.any_emitter)) ||
                             (ORDERED && probe_misses_emitters(a, r.o, td))) {
                             // no triangle emits, or the probe's line passes no emitter's
                             // leaf box: the probe's emitter pass ends with no hit, exactly
@@ -516,29 +482,6 @@ void k_trace(TraceArgs a) {
                             ++c_local;
                             put_level(kNoProbe, direct);
                             after = true;
-                        } else if (INL && TPT_PROBE_INLINE) {
-                            tg = grazing(gpass, td);
-                            // <= 4 emitters: pass 1 here; a miss resolves the probe in
-                            // this pass, an emitter hit goes on to pass 2 (occlusion)
-                            ++c_trav;
-                            trav_begin(r, r.o, td, TM_EMIT, a.boxes_finite != 0, a.emit_root, a.cull_eps, tg);
-                            begun = true;
-                            phase = PH_PROBE;
-                            if (r.mode == TM_EMIT && r.fin) {
-                                ++c_wide;
-                                emit_probe_inline<DRAIN>(r, a.inner4 + 8 * (size_t)a.emit_root, a.tri, nint, c_leaf,
-                                                         a.cull_eps);
-                                if (a.n_sliver_groups > 0) sliver_pass(r, a, c_leaf);
-                                if (r.fid < 0) {
-                                    ++c_local;
-                                    put_level(kNoProbe, direct);
-                                    after = true;
-                                    begun = false;
-                                } else {
-                                    r.mode = TM_OCCL;
-                                    r.node = 0;
-                                }
-                            }
                         } else {
                             tg = grazing(gpass, td);
                             phase = PH_PROBE;
@@ -567,8 +510,9 @@ void k_trace(TraceArgs a) {
             TPT_SEC(3)
         }
         bool woke = false;   // pair mode: a path lane that waited for its side lane, released mid-pass
-        if constexpr (PAIR && (TPT_PAIR_MID == 1 || (TPT_PAIR_MID == 2 && ENVIS))) {
-            // ---- mid-pass exchange, side -> path: a level's direct sum, in light order ----
+        if constexpr (PAIR && ENVIS) {
+            // ---- mid-pass exchange (round 6; pair variants with env importance sampling only),
+            // side -> path: a level's direct sum, in light order ----
             // (a side lane becomes ready in the first part of its pass; a path lane that
             // finishes in this pass, or has waited since an earlier one, then unwinds in
             // the second part -- the same sums in the same order, one pass sooner)
@@ -671,34 +615,6 @@ void k_trace(TraceArgs a) {
             }
             TPT_SEC(4)
             V3 to = r.o;
-            if (pool && phase == PH_CAMERA && remaining == 0 && active) {
-                // this pixel is done: store it and draw the next pixel of the pool tile
-#pragma unroll
-                for (int i = 0; i < 6; ++i) g_rng[i * npix + off] = st[i];
-                g_acc[off] = total.x;
-                g_acc[npix + off] = total.y;
-                g_acc[2 * npix + off] = total.z;
-                active = false;
-                for (;;) {
-                    const int j = __atomic_fetch_add(pool_next, 1, __ATOMIC_RELAXED);
-                    if (j >= 256) break;
-                    const int wj = j >> 6, lj = j & 63;
-                    const int px = (tx + 1) * 16 + (wj & 1) * 8 + (lj & 7);
-                    const int ply = (by / nfr) * 16 + (wj >> 1) * 8 + (lj >> 3);
-                    const int py = band_row(ply, a.band_rows, a.band_count, a.band_index, a.band_list);
-                    if (px < a.width && ply < a.band_height && py < a.height) {
-                        x = px;
-                        y = py;
-                        off = (size_t)x + (size_t)y * (size_t)a.width;
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) st[i] = g_rng[i * npix + off];
-                        total = v3(g_acc[off], g_acc[npix + off], g_acc[2 * npix + off]);
-                        remaining = a.samples;
-                        active = true;
-                        break;
-                    }
-                }
-            }
             if (phase == PH_CAMERA) {
                 if (remaining == 0) {
                     ts = TS_DEAD;
@@ -726,11 +642,9 @@ void k_trace(TraceArgs a) {
             }
             TPT_SEC(5)
             if (ts != TS_DEAD && ts != TS_IDLE) {
-                if (!begun) {
-                    if (!redo) ++c_trav;
-                    trav_begin(r, to, td, shadow ? TM_ANY : ((ORDERED && phase == PH_PROBE) ? TM_EMIT : TM_CLOSEST),
-                               a.boxes_finite != 0, a.emit_root, a.cull_eps, tg);
-                }
+                if (!redo) ++c_trav;
+                trav_begin(r, to, td, shadow ? TM_ANY : ((ORDERED && phase == PH_PROBE) ? TM_EMIT : TM_CLOSEST),
+                           a.boxes_finite != 0, a.emit_root, a.cull_eps, tg);
                 ts = TS_TRAV;
                 sl_pend = true;
 #ifdef TPT_VERIFY_CULL
@@ -813,21 +727,6 @@ void k_trace(TraceArgs a) {
             if (side && ts == TS_IDLE && pdead) ts = TS_DEAD;
         }
         if (__ballot(ts != TS_DEAD) == 0ull) break;
-        if constexpr (TPT_SHADOW_FIRST && ORDERED && (LIGHTS || ENVIS) && !QUAD) {
-            // a fresh shadow ray's root visit (the loop's first step for it, below)
-            bool quick = false;
-            if (ts == TS_TRAV && r.mode == TM_ANY && r.fin && r.node == 0 && r.sp == 0 && r.pend < 0 &&
-                r.fid < 0 && r.t == kRealMax) {
-                ++c_wide;
-                const int next = inner_visit4(r, a.inner4, snodes, a.lds_nodes, stk, r.sp);
-                r.node = next >= 0 ? next : (r.sp == 0 ? -1 : stk.get(--r.sp));
-                if (r.node < 0) {   // no child passes: the ray is done, unoccluded
-                    ts = TS_DONE;
-                    quick = true;
-                }
-            }
-            if (__ballot(quick) != 0ull) continue;   // shade those lanes before traversing
-        }
 #ifdef TPT_PROFILE_PHASES
         t_loop0 = wall_clock64();
         p_done += t_loop0 - t_iter0;
@@ -870,7 +769,7 @@ void k_trace(TraceArgs a) {
                         }
                     } else if (ORDERED && r.fin) {   // 4-wide (r.fin includes a.boxes_finite)
                         ++c_wide;
-                        next = inner_visit4(r, a.inner4, snodes, a.lds_nodes, stk, r.sp);
+                        next = inner_visit4(r, a.inner4, a.lds_nodes, stk, r.sp);
                     } else {                  // binary, the reference's exact slab test
                         ++c_inner;
                         int deferred;
@@ -1147,51 +1046,36 @@ hipError_t launch_hot_kat(int op, uint32_t n, const float* in, float* out, hipSt
     return hipGetLastError();
 }
 
-template <int MAXD, bool ORDERED, bool LIGHTS, bool MTL_LDS, typename StackT, bool ENVIS = false, bool INL = false,
-          bool PAIR = false, bool DRAIN = false, bool QUAD = false, bool NOEMIT = false>
+template <int MAXD, bool ORDERED, bool LIGHTS, bool MTL_LDS, typename StackT, bool ENVIS = false, bool PAIR = false,
+          bool DRAIN = false, bool QUAD = false, bool NOEMIT = false>
 static void launch_one(const TraceArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((k_trace<MAXD, ORDERED, LIGHTS, MTL_LDS, StackT, ENVIS, INL, PAIR, DRAIN, QUAD, NOEMIT>), grid,
+    hipLaunchKernelGGL((k_trace<MAXD, ORDERED, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, QUAD, NOEMIT>), grid,
                        dim3(256), lds, s, a);
 }
 // four lanes per pixel (a.quad): one-lane logic without delta lights
 template <bool MTL_LDS, typename StackT>
 static void launch_quad(const TraceArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    if (TPT_PROBE_INLINE && a.emit_inline) {
-        if (a.max_depth <= 8) launch_one<8, true, false, MTL_LDS, StackT, false, true, false, false, true>(a, grid, lds, s);
-        else launch_one<64, true, false, MTL_LDS, StackT, false, true, false, false, true>(a, grid, lds, s);
-    } else {
-        if (a.max_depth <= 8) launch_one<8, true, false, MTL_LDS, StackT, false, false, false, false, true>(a, grid, lds, s);
-        else launch_one<64, true, false, MTL_LDS, StackT, false, false, false, false, true>(a, grid, lds, s);
-    }
+    if (a.max_depth <= 8) launch_one<8, true, false, MTL_LDS, StackT, false, false, false, true>(a, grid, lds, s);
+    else launch_one<64, true, false, MTL_LDS, StackT, false, false, false, true>(a, grid, lds, s);
 }
 
-// INL: probe pass 1 in the shading pass (an emissive tree of one node); its own
-// variant, so scenes with larger emitter sets keep the leaner kernel.  PAIR:
-// pair mode (delta-light scenes only).  NOEMIT (pair variants): no triangle
-// emits, so every direct probe ends in the shading pass (TPT_PROBE_SHORTCUT) and
-// the probe's traversal phases are compiled out -- the pair kernel's registers
-// for C3's and C3 + IS's ball.
-#ifndef TPT_NOEMIT_PAIR
-#define TPT_NOEMIT_PAIR 1
-#endif
+// PAIR: pair mode (delta-light scenes only).  NOEMIT (pair variants): no triangle
+// emits, so every direct probe ends in the shading pass and the probe's
+// traversal phases are compiled out -- the pair kernel's registers for C3's and
+// C3 + IS's ball.
 template <bool LIGHTS, bool MTL_LDS, typename StackT, bool PAIR = false, bool ENVIS = false, bool DRAIN = false>
 static void launch_ordered_d(const TraceArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    if constexpr (PAIR && TPT_NOEMIT_PAIR && TPT_PROBE_SHORTCUT) {
+    if constexpr (PAIR) {
         if (!a.any_emitter) {
             if (a.max_depth <= 8)
-                launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, false, PAIR, DRAIN, false, true>(a, grid, lds, s);
+                launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, false, true>(a, grid, lds, s);
             else
-                launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, false, PAIR, DRAIN, false, true>(a, grid, lds, s);
+                launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, false, true>(a, grid, lds, s);
             return;
         }
     }
-    if (TPT_PROBE_INLINE && a.emit_inline) {
-        if (a.max_depth <= 8) launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, true, PAIR, DRAIN>(a, grid, lds, s);
-        else launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, true, PAIR, DRAIN>(a, grid, lds, s);
-    } else {
-        if (a.max_depth <= 8) launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, false, PAIR, DRAIN>(a, grid, lds, s);
-        else launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, false, PAIR, DRAIN>(a, grid, lds, s);
-    }
+    if (a.max_depth <= 8) launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN>(a, grid, lds, s);
+    else launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN>(a, grid, lds, s);
 }
 // DRAIN variants (parked triangles prefetched) for launches that cannot fill the
 // chip (a.drained), one-lane-per-pixel ordered kernels only
@@ -1216,15 +1100,14 @@ constexpr size_t kLdsBudgetQuad = (163840 / TPT_TRACE_WAVES_QUAD) & ~(size_t)255
 #define TPT_MTL_LDS_MAX 2048
 #endif
 constexpr size_t kLdsMtlMax = TPT_MTL_LDS_MAX;   // material tables up to 64 entries go to LDS
-constexpr size_t kLdsNodesMax = TPT_LDS_NODES_MAX;
 
-size_t trace_lds_bytes(TraceArgs& a, int words, size_t elem, bool mtl_lds, bool wide, int rec_cols = 256,
+size_t trace_lds_bytes(TraceArgs& a, int words, size_t elem, bool mtl_lds, int rec_cols = 256,
                        size_t lds_budget = kLdsBudget, bool quad = false) {
-    // [material table][top 4-wide nodes][traversal stack][path records].
+    // [material table][traversal stack][path records].
     // Priorities (measured on box): the whole stack (a
     // stack capped at 23 of its 40 slots cost 7 %), then path records up to
     // max_depth (records of long paths in private memory slow the heaviest
-    // tiles), then as many top nodes as the remaining bytes hold.
+    // tiles).
     const size_t mtl_bytes = mtl_lds ? ((size_t)(a.n_materials + 1) * 2 * 16 + 127) / 128 * 128 : 0;
     a.mtl_in_lds = mtl_lds ? 1 : 0;
     a.lds_mtl_offset = 0;
@@ -1239,41 +1122,21 @@ size_t trace_lds_bytes(TraceArgs& a, int words, size_t elem, bool mtl_lds, bool 
     // (44 slots of 32-bit ids): 27 stack slots + 2 record levels 7.63 Grays/s,
     // 19 + 6: 7.97, 12 + 8: 8.20.
     size_t slots = (size_t)a.stack_depth + 3;
-#ifndef TPT_RECORDS_FIRST
-#define TPT_RECORDS_FIRST 1
-#endif
     const size_t want = std::min<size_t>((size_t)a.max_depth, (budget - 12 * slot) / level);
-    if (TPT_RECORDS_FIRST ? (slots * slot + want * level > budget) : (slots * slot + 2 * level > budget))
+    if (slots * slot + want * level > budget)
         slots = std::min(slots, std::max<size_t>(12, ((budget - want * level) / slot) & ~(size_t)1));   // even
+    // the region holds a whole number of slot pairs (quad: of 4-slot rows), rounded to 16 bytes
     const size_t stack = quad ? ((slots + 3) / 4 * 4 * slot + 15) / 16 * 16
-                              : ((slots + 1) / 2 * 2 * slot + 15) / 16 * 16;   // even slot count (paired u16 layout)
+                              : ((slots + 1) / 2 * 2 * slot + 15) / 16 * 16;
     size_t levels = (budget - stack) / level;
     if (levels > (size_t)a.max_depth) levels = (size_t)a.max_depth;
-    size_t nodes = wide ? (budget - stack - levels * level) / 128 : 0;
-    nodes = std::min(nodes, std::min<size_t>((size_t)a.n4, kLdsNodesMax / 128));
-    a.lds_nodes = (int)nodes;
+    a.lds_nodes = 0;
     a.lds_nodes_offset = (int)mtl_bytes;
-    const size_t head = mtl_bytes + nodes * 128;
     a.stack_lds_slots = (int)slots;
-    a.lds_stack_offset = (int)head;
-    a.lds_rec_offset = (int)(head + stack);
+    a.lds_stack_offset = (int)mtl_bytes;
+    a.lds_rec_offset = (int)(mtl_bytes + stack);
     a.rec_lds_levels = (int)levels;
-    return head + stack + levels * level;
-}
-
-// pixel pool (k_trace): two tiles per workgroup, the second drawn from by the
-// lanes that finish their pixel first; its LDS counter follows the rest
-static void use_tile_pool(TraceArgs& a, dim3& grid, size_t& lds) {
-    a.tile_pool = 1;
-    grid.x = (grid.x + 1) / 2;
-    if (a.xcd_run > 0) {   // runs of workgroups now: half as many, each two tiles wide
-        const int per = grid.x % 8 == 0 ? (int)grid.x / 8 : 0, want = std::max(2, a.xcd_run / 2);
-        a.xcd_run = 0;
-        for (int g = std::min(per, want); g >= 2 && a.xcd_run == 0; --g)
-            if (per % g == 0) a.xcd_run = g;
-    }
-    a.lds_pool_offset = (int)((lds + 15) / 16 * 16);
-    lds = (size_t)a.lds_pool_offset + 16;
+    return mtl_bytes + stack + levels * level;
 }
 
 // waves per SIMD the one-lane trace variants are built for (__launch_bounds__):
@@ -1284,26 +1147,37 @@ bool trace_quad_fits(const TraceArgs& a_in) {
     TraceArgs a = a_in;
     const bool small = (2 * (size_t)a.n_faces - 1) <= 65535;
     const bool mtl_lds = (size_t)(a.n_materials + 1) * 2 * sizeof(float4) <= kLdsMtlMax;
-    trace_lds_bytes(a, 2, small ? 2 : 4, mtl_lds, true, 256, kLdsBudgetQuad, true);
+    trace_lds_bytes(a, 2, small ? 2 : 4, mtl_lds, 256, kLdsBudgetQuad, true);
     return rec_words(a.n_lights, a.n_materials) == 2 && a.stack_lds_slots >= a.stack_depth + 3;
+}
+
+// f(MTL_LDS as std::bool_constant, StackT as a value) for the launch's material-table
+// placement and node-id width
+template <typename F>
+static void for_mtl_stack(bool mtl_lds, bool small, F f) {
+    if (mtl_lds) {
+        if (small) f(std::true_type{}, uint16_t{});
+        else f(std::true_type{}, int{});
+    } else {
+        if (small) f(std::false_type{}, uint16_t{});
+        else f(std::false_type{}, int{});
+    }
 }
 
 hipError_t launch_trace(const TraceArgs& a_in, hipStream_t s) {
     TraceArgs a = a_in;
-    a.tile_pool = 0;
-    a.lds_pool_offset = 0;
     dim3 grid((a.width + 15) / 16, ((a.band_height + 15) / 16) * (a.n_frames > 0 ? a.n_frames : 1));
     // the XCD-run remap is a permutation of a row's tiles only if runs tile gridDim.x / 8
     if (a.xcd_run > 0 && (grid.x % 8 != 0 || (grid.x / 8) % (unsigned)a.xcd_run != 0)) a.xcd_run = 0;
     if (a.flags & TPT_FLAG_REF_ORDER) {
         // the reference's visit order (tests, diagnostics): one general variant
-        const size_t lds = trace_lds_bytes(a, 5, sizeof(int), false, false);
+        const size_t lds = trace_lds_bytes(a, 5, sizeof(int), false);
         if (a.env_is) launch_one<64, false, true, false, int, true>(a, grid, lds, s);
         else launch_one<64, false, true, false, int>(a, grid, lds, s);
         return hipGetLastError();
     }
     const bool small = (2 * (size_t)a.n_faces - 1) <= 65535;
-    const bool mtl_lds_ok = (size_t)(a.n_materials + 1) * 2 * sizeof(float4) <= kLdsMtlMax;
+    const bool mtl_lds = (size_t)(a.n_materials + 1) * 2 * sizeof(float4) <= kLdsMtlMax;
     if (a.env_is) {
         // opt-in env next-event estimation (A15): variants of their own (the
         // delta-light machinery: 5-word records), so the others stay lean; pair
@@ -1311,73 +1185,41 @@ hipError_t launch_trace(const TraceArgs& a_in, hipStream_t s) {
         // rays) to the side lane
         const bool pair_is = a.pair && (a.n_materials + 1) < (int)kNoProbe;
         if (pair_is) grid.y = ((a.band_height + 7) / 8) * (a.n_frames > 0 ? a.n_frames : 1);
-        const size_t lds = trace_lds_bytes(a, 5, small ? 2 : 4, mtl_lds_ok, true, pair_is ? 128 : 256, kLdsBudgetIS);
-#define TPT_IS_LAUNCH(MTL, ST)                                                         \
-    {                                                                                  \
-        if (pair_is) launch_ordered<true, MTL, ST, true, true>(a, grid, lds, s);        \
-        else launch_ordered<true, MTL, ST, false, true>(a, grid, lds, s);               \
-    }
-        if (mtl_lds_ok) {
-            if (small) TPT_IS_LAUNCH(true, uint16_t) else TPT_IS_LAUNCH(true, int)
-        } else {
-            if (small) TPT_IS_LAUNCH(false, uint16_t) else TPT_IS_LAUNCH(false, int)
-        }
-#undef TPT_IS_LAUNCH
+        const size_t lds = trace_lds_bytes(a, 5, small ? 2 : 4, mtl_lds, pair_is ? 128 : 256, kLdsBudgetIS);
+        for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
+            if (pair_is) launch_ordered<true, decltype(m)::value, decltype(st), true, true>(a, grid, lds, s);
+            else launch_ordered<true, decltype(m)::value, decltype(st), false, true>(a, grid, lds, s);
+        });
         return hipGetLastError();
     }
     const bool lights = rec_words(a.n_lights, a.n_materials) == 5;
-    const bool mtl_lds = (size_t)(a.n_materials + 1) * 2 * sizeof(float4) <= kLdsMtlMax;
     if (a.quad) {
         // four lanes per pixel: 8x8-pixel workgroups; the quads' stacks must lie in
         // LDS whole (the host checked lights == 0)
         grid = dim3((a.width + 7) / 8, ((a.band_height + 7) / 8) * (a.n_frames > 0 ? a.n_frames : 1));
         a.xcd_run = 0;
-        const size_t lds = trace_lds_bytes(a, 2, small ? 2 : 4, mtl_lds, true, 256, kLdsBudgetQuad, true);
+        const size_t lds = trace_lds_bytes(a, 2, small ? 2 : 4, mtl_lds, 256, kLdsBudgetQuad, true);
         if (lights || a.stack_lds_slots < a.stack_depth + 3) return hipErrorInvalidValue;
-        if (mtl_lds) {
-            if (small) launch_quad<true, uint16_t>(a, grid, lds, s);
-            else launch_quad<true, int>(a, grid, lds, s);
-        } else {
-            if (small) launch_quad<false, uint16_t>(a, grid, lds, s);
-            else launch_quad<false, int>(a, grid, lds, s);
-        }
+        for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
+            launch_quad<decltype(m)::value, decltype(st)>(a, grid, lds, s);
+        });
         return hipGetLastError();
     }
     // pair mode: delta lights (shadow rays to hand off), packed probe ids
     const bool pair = a.pair && lights && a.n_lights > 0 && (a.n_materials + 1) < (int)kNoProbe;
     if (pair) {
         grid.y = ((a.band_height + 7) / 8) * (a.n_frames > 0 ? a.n_frames : 1);   // 16x8 pixels per workgroup
-        const size_t lds = trace_lds_bytes(a, 5, small ? 2 : 4, mtl_lds, true, 128, kLdsBudgetPair);
-        if (mtl_lds) {
-            if (small) launch_ordered<true, true, uint16_t, true>(a, grid, lds, s);
-            else launch_ordered<true, true, int, true>(a, grid, lds, s);
-        } else {
-            if (small) launch_ordered<true, false, uint16_t, true>(a, grid, lds, s);
-            else launch_ordered<true, false, int, true>(a, grid, lds, s);
-        }
+        const size_t lds = trace_lds_bytes(a, 5, small ? 2 : 4, mtl_lds, 128, kLdsBudgetPair);
+        for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
+            launch_ordered<true, decltype(m)::value, decltype(st), true>(a, grid, lds, s);
+        });
         return hipGetLastError();
     }
-    // pixel pool; its LDS counter comes out of the budget
-    const bool use_pool = TPT_TILE_POOL && !a.drained;
-    size_t lds = trace_lds_bytes(a, lights ? 5 : 2, small ? 2 : 4, mtl_lds, true, 256, kLdsBudget - (use_pool ? 16 : 0));
-    if (use_pool) use_tile_pool(a, grid, lds);
-    if (lights) {
-        if (mtl_lds) {
-            if (small) launch_ordered<true, true, uint16_t>(a, grid, lds, s);
-            else launch_ordered<true, true, int>(a, grid, lds, s);
-        } else {
-            if (small) launch_ordered<true, false, uint16_t>(a, grid, lds, s);
-            else launch_ordered<true, false, int>(a, grid, lds, s);
-        }
-    } else {
-        if (mtl_lds) {
-            if (small) launch_ordered<false, true, uint16_t>(a, grid, lds, s);
-            else launch_ordered<false, true, int>(a, grid, lds, s);
-        } else {
-            if (small) launch_ordered<false, false, uint16_t>(a, grid, lds, s);
-            else launch_ordered<false, false, int>(a, grid, lds, s);
-        }
-    }
+    const size_t lds = trace_lds_bytes(a, lights ? 5 : 2, small ? 2 : 4, mtl_lds);
+    for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
+        if (lights) launch_ordered<true, decltype(m)::value, decltype(st)>(a, grid, lds, s);
+        else launch_ordered<false, decltype(m)::value, decltype(st)>(a, grid, lds, s);
+    });
     return hipGetLastError();
 }
 
@@ -1391,7 +1233,7 @@ hipError_t launch_trace(const TraceArgs& a_in, hipStream_t s) {
 // the wave's loop iterations, the wave's shader cycles (s_memtime) for the
 // walk, the hit fid.
 constexpr int kLatStackSlots = 64;
-// LaneStack's [slot][lane] layout has a 256-lane row per slot (stack_slot_offset)
+// LaneStack's [slot][lane] layout has a 256-lane row per slot
 constexpr size_t kLatStackBytes = (size_t)kLatStackSlots * 256 * sizeof(int);
 __global__ __launch_bounds__(64) void k_step_latency(TraceArgs a, uint32_t n, const float* __restrict__ o,
                                                      const float* __restrict__ d, int nodes_lds,
@@ -1433,7 +1275,7 @@ __global__ __launch_bounds__(64) void k_step_latency(TraceArgs a, uint32_t n, co
                         next = inner_visit4_q(r, lds_f4(nd), lds_f4(nd + 1), lds_f4(nd + 2), lds_f4(nd + 3),
                                               lds_f4(nd + 4), lds_f4(nd + 5), lds_f4(nd + 6), stk, r.sp);
                     } else {
-                        next = inner_visit4(r, a.inner4, nullptr, 0, stk, r.sp);
+                        next = inner_visit4(r, a.inner4, 0, stk, r.sp);
                     }
                 } else {
                     int deferred;

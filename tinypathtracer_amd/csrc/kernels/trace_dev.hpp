@@ -30,25 +30,8 @@
 #ifndef TPT_FAST_RCP      // tolerance build: v_rcp_f32 for 1/d and the triangle test's 1/denom (0: IEEE divides)
 #define TPT_FAST_RCP 1
 #endif
-#ifndef TPT_PROBE_SHORTCUT
-#define TPT_PROBE_SHORTCUT 1   // no emissive triangle: resolve direct probes in the shading pass
-#endif
-#ifndef TPT_PK_SLAB   // 4-wide visits: slab products as packed fp32 pairs (v_pk_add_f32 / v_pk_mul_f32)
-#define TPT_PK_SLAB 0
-#endif
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifndef TPT_PACKED_SORT   // 4-wide visits with 16-bit node ids: children sorted by packed (entry, link) keys
-#define TPT_PACKED_SORT 0   // measured: C2 -1.6 %, C4 +1.5 %
-#endif
 #ifndef TPT_LEAF_KP
 #define TPT_LEAF_KP 24    // run the triangle branch once this many lanes hold a parked leaf (or a.leaf_kb are blocked)
-#endif
-// Top 4-wide nodes staged in LDS (breadth-first prefix of inner4).  Off by
-// default: measured on box 256 spp, 14 staged nodes cost 10 % (the per-visit
-// LDS/global branch and LDS reads outweigh the shorter latency of the first
-// levels); build with -DTPT_LDS_NODES_MAX=4096 to stage up to 32.
-#ifndef TPT_LDS_NODES_MAX
-#define TPT_LDS_NODES_MAX 0
 #endif
 #ifndef TPT_TRACE_WAVES
 #define TPT_TRACE_WAVES 5   // min waves per SIMD requested from the register allocator
@@ -72,38 +55,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef TPT_TRACE_WAVES_QUAD
 #define TPT_TRACE_WAVES_QUAD 4   // four lanes per pixel (k_trace QUAD)
 #endif
-#ifndef TPT_GRAZE_HIT   // the grazing-hit rule (Culling: "Grazing hits"); 0 only to measure its cost
-#define TPT_GRAZE_HIT 1
-#endif
-#ifndef TPT_TILE_POOL
-// 1: one-lane-per-pixel, full-occupancy launches give each workgroup two
-// adjacent 16x16 tiles; the second is a pixel pool its finished lanes draw
-// from ("Round 4: N1").  0 (default): one tile per
-// workgroup -- the pool measured C2 -15 %, C4 -39 %, C5 -5 % (workgroups live
-// twice as long, so a launch's tail of heavy workgroups grows, while lanes
-// without work were only 7.6 % of C2's lane-steps).
-#define TPT_TILE_POOL 0
-#endif
-#ifndef TPT_ENV_FAST
-#define TPT_ENV_FAST 1     // env texel indices from fp32 bounds, double trig only near texel edges (0: A/B builds)
-#endif
-#ifndef TPT_PROBE_INLINE
-// 1: probe pass 1 inside the shading pass for <= 4 emitters (INL variants,
-// emit_probe_inline; round 3).  0 (default): the conservative slab pre-test
-// (probe_misses_emitters) resolves the probes that can hit no emitter in the
-// shading pass and the others trace pass 1 as a traversal.
-#define TPT_PROBE_INLINE 0
-#endif
-#ifndef TPT_SHARE_HEMI
-#define TPT_SHARE_HEMI 0   // 1: the direct probe reuses the extension sample's hemisphere frame (new_direction)
-#endif
-#ifndef TPT_FMA_SLAB_UB
-#define TPT_FMA_SLAB_UB 0   // 1: A/B builds only -- every slab as one FMA per bound (NOT exact: the
-                            // upper bound of the inner-box FMA cut, DESIGN.md section 5 "Round 6")
-#endif
-#ifndef TPT_ENV_INLINE
-#define TPT_ENV_INLINE 0   // 1: env_lookup inlined in every variant (A/B builds)
-#endif
 
 namespace tpt {
 
@@ -114,6 +65,7 @@ namespace tpt {
 struct alignas(16) LdsF4 {   // float4 stand-in usable in LDS address space
     float x, y, z, w;
 };
+__device__ __forceinline__ float4 lds_f4(const TPT_LDS LdsF4* p) { return make_float4(p->x, p->y, p->z, p->w); }
 
 // rayHitBBox (geometry_queries.h:18-46) with 1/dir hoisted per ray (same
 // values), written without branches: the reference returns false at the first
@@ -314,7 +266,7 @@ __device__ __forceinline__ void inner_visit(const Trav& r, const float4* __restr
 // differ from the ternaries; only comparisons consume T0/T1.
 __device__ __forceinline__ void slab_minmax(const V3& o, const V3& inv, float nx, float ny, float nz, float xx,
                                             float xy, float xz, float& t0, float& t1) {
-#if TPT_FAST || TPT_FMA_SLAB_UB
+#if TPT_FAST
     // (n - o) / d as one FMA per bound: n * (1/d) - o * (1/d) (the o * (1/d) terms
     // are common to every box a visit tests)
     const float ox = -(o.x * inv.x), oy = -(o.y * inv.y), oz = -(o.z * inv.z);
@@ -338,21 +290,7 @@ __device__ __forceinline__ void slab_minmax(const V3& o, const V3& inv, float nx
 // the LDS fast path for all but the deepest moments.
 constexpr int kMaxStackSlots = 160 + 3;
 
-// LDS slot addressing: [slot][lane].  TPT_STACK_PAIRED=1 pairs two 16-bit
-// slots in one dword per lane ([slot/2][lane][slot%2]) so the 32 lanes of a
-// ds_read/ds_write group touch 32 distinct banks instead of two lanes per bank
-// (2-way conflicts whenever neighbouring lanes' stack depths differ).  Measured
-// (3 interleaved reps): box 256 spp -2.5 %, C3 +2 %, C5 0 -- the extra
-// address arithmetic costs more than the conflicts, so it is off.
-#ifndef TPT_STACK_PAIRED
-#define TPT_STACK_PAIRED 0
-#endif
-template <typename StackT>
-__device__ __forceinline__ int stack_slot_offset(int i) {
-    if (TPT_STACK_PAIRED && sizeof(StackT) == 2) return (i >> 1) * 512 + (i & 1);
-    return i * 256;
-}
-
+// LDS slot addressing: [slot][lane], a 256-lane row per slot.
 // QS (four lanes per ray): one stack per quad, in its four lanes' columns --
 // slot i at row i / 4, column 4q + i % 4 -- a quarter of the rows
 template <typename StackT, bool QS = false>
@@ -362,7 +300,7 @@ struct LaneStack {
     StackT deep[kMaxStackSlots];
     __device__ static __forceinline__ int off(int i) {
         if constexpr (QS) return (i >> 2) * 256 + (i & 3);
-        else return stack_slot_offset<StackT>(i);
+        else return i * 256;
     }
     __device__ __forceinline__ void put(int i, int v) {
         if (i < nlds) lds[off(i)] = (StackT)v;
@@ -381,71 +319,16 @@ struct LaneStack {
 // is the binary traversal's.  Hit children are sorted by slab entry; the
 // nearest is returned, the others (up to 3) are pushed farthest-first.  The
 // stack region has 3 spare slots so all three writes are unconditional.
-__device__ __forceinline__ float4 lds_f4(const TPT_LDS LdsF4* p) { return make_float4(p->x, p->y, p->z, p->w); }
-
-// (packed v_pk_add/v_pk_mul slab math was measured 17 % slower: register-pair
-// constraints outweigh the halved instruction count)
-
-template <typename StackT, bool QS>
-__device__ __forceinline__ int inner_visit4_q(const Trav& r, float4 q0, float4 q1, float4 q2, float4 q3, float4 q4,
-                                              float4 q5, float4 q6, LaneStack<StackT, QS>& stk, int& sp);
-template <typename StackT, bool QS>
-__device__ __forceinline__ int inner_visit4(const Trav& r, const float4* __restrict__ inner4,
-                                            const TPT_LDS LdsF4* snodes, int nlds_nodes, LaneStack<StackT, QS>& stk,
-                                            int& sp) {
-    float4 q0, q1, q2, q3, q4, q5, q6;
-    if (TPT_LDS_NODES_MAX > 0 && r.node < nlds_nodes) {   // top levels, staged in LDS at kernel start
-        const TPT_LDS LdsF4* nd = snodes + 8 * r.node;
-        q0 = lds_f4(nd);
-        q1 = lds_f4(nd + 1);
-        q2 = lds_f4(nd + 2);
-        q3 = lds_f4(nd + 3);
-        q4 = lds_f4(nd + 4);
-        q5 = lds_f4(nd + 5);
-        q6 = lds_f4(nd + 6);
-    } else {
-        const float4* nd = inner4 + 8 * r.node;
-        q0 = nd[0];
-        q1 = nd[1];
-        q2 = nd[2];
-        q3 = nd[3];
-        q4 = nd[4];
-        q5 = nd[5];
-        q6 = nd[6];
-    }
-    return inner_visit4_q(r, q0, q1, q2, q3, q4, q5, q6, stk, sp);
-}
-// the visit's arithmetic on the node's seven float4 (from global memory or LDS)
+// The visit's arithmetic on the node's seven float4 (k_step_latency also feeds
+// it from its LDS copy of the tree).
 template <typename StackT, bool QS>
 __device__ __forceinline__ int inner_visit4_q(const Trav& r, float4 q0, float4 q1, float4 q2, float4 q3, float4 q4,
                                               float4 q5, float4 q6, LaneStack<StackT, QS>& stk, int& sp) {
     float k0, k1, k2, k3, e0, e1, e2, e3;
-#if TPT_PK_SLAB && !TPT_FAST
-    // The slab products as packed fp32 pairs (v_pk_add_f32 / v_pk_mul_f32: two IEEE
-    // operations per lane per instruction, the same rounding as the scalar ones, so
-    // the same verdicts): a child's six bounds are three register pairs of the
-    // loaded node -- (min.x, min.y), (min.z, max.x), (max.y, max.z) -- against the
-    // ray's origin and 1/dir arranged the same way.
-    {
-        const f32x2 oa = {r.o.x, r.o.y}, ob = {r.o.z, r.o.x}, oc = {r.o.y, r.o.z};
-        const f32x2 ia = {r.inv.x, r.inv.y}, ib = {r.inv.z, r.inv.x}, ic = {r.inv.y, r.inv.z};
-        auto slab2 = [&](f32x2 pa, f32x2 pb, f32x2 pc, float& t0, float& t1) {
-            const f32x2 a = (pa - oa) * ia, b = (pb - ob) * ib, c = (pc - oc) * ic;
-            // a = (lo.x, lo.y), b = (lo.z, hi.x), c = (hi.y, hi.z) in slab-time units
-            t0 = fmaxf(fmaxf(fminf(a.x, b.y), fminf(a.y, c.x)), fminf(b.x, c.y));
-            t1 = fminf(fminf(fmaxf(a.x, b.y), fmaxf(a.y, c.x)), fmaxf(b.x, c.y));
-        };
-        slab2(f32x2{q0.x, q0.y}, f32x2{q0.z, q0.w}, f32x2{q1.x, q1.y}, k0, e0);
-        slab2(f32x2{q1.z, q1.w}, f32x2{q2.x, q2.y}, f32x2{q2.z, q2.w}, k1, e1);
-        slab2(f32x2{q3.x, q3.y}, f32x2{q3.z, q3.w}, f32x2{q4.x, q4.y}, k2, e2);
-        slab2(f32x2{q4.z, q4.w}, f32x2{q5.x, q5.y}, f32x2{q5.z, q5.w}, k3, e3);
-    }
-#else
     slab_minmax(r.o, r.inv, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, k0, e0);
     slab_minmax(r.o, r.inv, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, k1, e1);
     slab_minmax(r.o, r.inv, q3.x, q3.y, q3.z, q3.w, q4.x, q4.y, k2, e2);
     slab_minmax(r.o, r.inv, q4.z, q4.w, q5.x, q5.y, q5.z, q5.w, k3, e3);
-#endif
     const float hi = r.lim;
     int i0 = __float_as_int(q6.x), i1 = __float_as_int(q6.y), i2 = __float_as_int(q6.z), i3 = __float_as_int(q6.w);
     const float hd = 0.5f * kDelta;
@@ -455,46 +338,6 @@ __device__ __forceinline__ int inner_visit4_q(const Trav& r, float4 q0, float4 q
     const bool h2 = (i2 >= 0) & (fmaxf(k2, hd) <= fminf(e2, hi));
     const bool h3 = (i3 >= 0) & (fmaxf(k3, hd) <= fminf(e3, hi));
     const int m = (int)h0 + (int)h1 + (int)h2 + (int)h3;
-    if constexpr (TPT_PACKED_SORT && sizeof(StackT) == 2 && !QS) {
-        // 16-bit node ids: one sort key per child, the clamped slab entry's top 16 bits
-        // (sign, exponent, 7 mantissa bits; >= Delta/2, so never a denormal) over the
-        // link's 16 bits, sorted as floats with one min and one max per comparator.
-        // Entries within 1/128 of each other, and the children holding the origin
-        // (entry < Delta/2), order by link instead -- the visit order only steers:
-        // the walk's hit is the least t, then the larger leaf position, whatever the
-        // order (Culling), so the frame is the same.
-        const float inf = __builtin_inff();
-        auto pk = [inf](bool h, float k, int i, float hd_) {
-            return h ? __uint_as_float((__float_as_uint(fmaxf(k, hd_)) & 0xffff0000u) | ((uint32_t)i & 0xffffu)) : inf;
-        };
-        float p0 = pk(h0, k0, i0, hd), p1 = pk(h1, k1, i1, hd), p2 = pk(h2, k2, i2, hd), p3 = pk(h3, k3, i3, hd);
-#define TPT_CXP(a, b)                    \
-    {                                    \
-        const float lo_ = fminf(a, b);   \
-        b = fmaxf(a, b);                 \
-        a = lo_;                         \
-    }
-        TPT_CXP(p0, p1)
-        TPT_CXP(p2, p3)
-        TPT_CXP(p0, p2)
-        TPT_CXP(p1, p3)
-        TPT_CXP(p1, p2)
-#undef TPT_CXP
-        const int np = m > 0 ? m - 1 : 0;
-        const uint32_t u0 = __float_as_uint(np == 3 ? p3 : (np == 2 ? p2 : p1)), u1 = __float_as_uint(np == 3 ? p2 : p1),
-                       u2 = __float_as_uint(p1);
-        if (sp + 3 <= stk.nlds) {   // (StackT)u: the low 16 bits, the link
-            stk.lds[stk.off(sp)] = (StackT)u0;
-            stk.lds[stk.off(sp + 1)] = (StackT)u1;
-            stk.lds[stk.off(sp + 2)] = (StackT)u2;
-        } else {
-            stk.put(sp, (int)(u0 & 0xffffu));
-            stk.put(sp + 1, (int)(u1 & 0xffffu));
-            stk.put(sp + 2, (int)(u2 & 0xffffu));
-        }
-        sp += np;
-        return m > 0 ? (int)(__float_as_uint(p0) & 0xffffu) : -1;   // -1 when no child was entered
-    }
     i0 &= kLinkMask;
     i1 &= kLinkMask;
     i2 &= kLinkMask;
@@ -538,6 +381,17 @@ __device__ __forceinline__ int inner_visit4_q(const Trav& r, float4 q0, float4 q
     }
     sp += np;
     return i0;   // -1 when no child was entered
+}
+// nlds_nodes is a dead parameter (k_trace passes a.lds_nodes, always 0; the others pass 0), kept
+// only for codegen stability: without that dead read of a.lds_nodes at k_trace's call site, the
+// eight ordered env-IS variants without an LDS material table compile to other code (PAIR: 7089 ->
+// 6968 instructions, 12 -> 8 spilled VGPRs; tolerance build 23 -> 26).  It goes with k_trace's
+// staging loop (device_api.hpp, lds_nodes), in a change measured on its own.
+template <typename StackT, bool QS>
+__device__ __forceinline__ int inner_visit4(const Trav& r, const float4* __restrict__ inner4, int nlds_nodes,
+                                            LaneStack<StackT, QS>& stk, int& sp) {
+    const float4* nd = inner4 + 8 * r.node;
+    return inner_visit4_q(r, nd[0], nd[1], nd[2], nd[3], nd[4], nd[5], nd[6], stk, sp);
 }
 
 // rayHitTriangle (geometry_queries.h:65-86) on leaf position pos, e1/e2
@@ -638,10 +492,6 @@ __device__ __forceinline__ int inner_visit4_quad(Trav& r, const float4* __restri
     const bool h = (link >= 0) & (fmaxf(kk, hd) <= fminf(ee, r.lim));
     const bool lf = h & (id >= nint);
     stop = false;
-#ifndef TPT_QUAD_EARLY
-#define TPT_QUAD_EARLY 1
-#endif
-#if TPT_QUAD_EARLY
     // the leaf children's triangles in flight while the internal children are ranked
     // against the bound the node was entered with (strong-scaled C2 at N = 8, 2
     // interleaved reps: 245.0 / 245.7 ms against 249.8 / 250.1 with the ranking after
@@ -650,22 +500,6 @@ __device__ __forceinline__ int inner_visit4_quad(Trav& r, const float4* __restri
                    make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
     if (lf) tq = tri_load(tri, id - nint);
     const bool in = h & (id < nint);
-#else
-    if (__ballot(lf) != 0ull) {
-        int s = 0;
-        if (lf) {
-            ++c_leaf;
-            s = leaf_test<true>(r, tri, id - nint, cull_eps) ? 1 : 0;
-        }
-        quad_best<kQuadXor1>(r);
-        quad_best<kQuadXor2>(r);
-        s |= quad_mov<kQuadXor1>(s);
-        s |= quad_mov<kQuadXor2>(s);
-        stop = s != 0;
-    }
-    // internal children against the bound the leaves left
-    const bool in = !stop & h & (id < nint) & (fmaxf(kk, hd) <= fminf(ee, r.lim));
-#endif
     const float key = in ? kk : __builtin_inff();
     const float c0 = quad_mov<0x00>(key), c1 = quad_mov<0x55>(key), c2 = quad_mov<0xaa>(key), c3 = quad_mov<0xff>(key);
     const int rank = ((c0 < key) | ((c0 == key) & (0 < k))) + ((c1 < key) | ((c1 == key) & (1 < k))) +
@@ -676,7 +510,6 @@ __device__ __forceinline__ int inner_visit4_quad(Trav& r, const float4* __restri
     near = max(near, quad_mov<kQuadXor1>(near));
     near = max(near, quad_mov<kQuadXor2>(near));
     sp += n_in > 0 ? n_in - 1 : 0;
-#if TPT_QUAD_EARLY
     if (__ballot(lf) != 0ull) {
         int s = 0;
         if (lf) {
@@ -689,81 +522,7 @@ __device__ __forceinline__ int inner_visit4_quad(Trav& r, const float4* __restri
         s |= quad_mov<kQuadXor2>(s);
         stop = s != 0;
     }
-#endif
     return near;
-}
-
-// Probe pass 1 over an emissive-triangle tree that is a single 4-wide node of
-// leaves (<= 4 emitters), run inside the shading pass instead of a traversal:
-// the node's leaf boxes by the same min/max slab test, then the triangle test
-// of every passing leaf.  The closest hit under the ordered tie rule does not
-// depend on the order the leaves are tested in, so r ends as the traversal
-// would leave it.
-template <bool HOIST = false>
-__device__ __forceinline__ void emit_probe_inline(Trav& r, const float4* __restrict__ nd,
-                                                  const float4* __restrict__ tri, int nint, uint32_t& c_leaf,
-                                                  float cull_eps) {
-    const float4 q0 = nd[0], q1 = nd[1], q2 = nd[2], q3 = nd[3], q4 = nd[4], q5 = nd[5], q6 = nd[6];
-    if constexpr (HOIST) {
-        // (DRAIN variants) the leaves' triangles are loaded together, before any
-        // test: the node's links are the same for every lane, so these are
-        // uniform loads issued at once instead of one round trip per leaf
-        const float hi = kRealMax, hd = 0.5f * kDelta;
-        const int i0 = __float_as_int(q6.x), i1 = __float_as_int(q6.y), i2 = __float_as_int(q6.z),
-                  i3 = __float_as_int(q6.w);
-        // (empty slots -- uniform -- skip their slab test; their verdict below is false)
-        float k0 = 0.0f, k1 = 0.0f, k2 = 0.0f, k3 = 0.0f, e0 = 0.0f, e1 = 0.0f, e2 = 0.0f, e3 = 0.0f;
-        if (i0 >= 0) slab_minmax(r.o, r.inv, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, k0, e0);
-        if (i1 >= 0) slab_minmax(r.o, r.inv, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, k1, e1);
-        if (i2 >= 0) slab_minmax(r.o, r.inv, q3.x, q3.y, q3.z, q3.w, q4.x, q4.y, k2, e2);
-        if (i3 >= 0) slab_minmax(r.o, r.inv, q4.z, q4.w, q5.x, q5.y, q5.z, q5.w, k3, e3);
-        const int p0 = i0 >= 0 ? (i0 & kLinkMask) - nint : 0, p1 = i1 >= 0 ? (i1 & kLinkMask) - nint : 0,
-                  p2 = i2 >= 0 ? (i2 & kLinkMask) - nint : 0, p3 = i3 >= 0 ? (i3 & kLinkMask) - nint : 0;
-        const TriQ ta = tri_load(tri, p0), tb = tri_load(tri, p1);
-        const float4 a0 = ta.q0, a1 = ta.q1, a2 = ta.q2;
-        const float4 b0 = tb.q0, b1 = tb.q1, b2 = tb.q2;
-        float4 c0 = a0, c1 = a1, c2 = a2, d0 = a0, d1 = a1, d2 = a2;
-        if (i2 >= 0) {
-            const TriQ tc = tri_load(tri, p2);
-            c0 = tc.q0;
-            c1 = tc.q1;
-            c2 = tc.q2;
-        }
-        if (i3 >= 0) {
-            const TriQ td = tri_load(tri, p3);
-            d0 = td.q0;
-            d1 = td.q1;
-            d2 = td.q2;
-        }
-        if ((i0 >= 0) & (fmaxf(k0, hd) <= fminf(e0, hi))) { ++c_leaf; leaf_test_q<true>(r, a0, a1, a2, p0, cull_eps); }
-        if ((i1 >= 0) & (fmaxf(k1, hd) <= fminf(e1, hi))) { ++c_leaf; leaf_test_q<true>(r, b0, b1, b2, p1, cull_eps); }
-        if ((i2 >= 0) & (fmaxf(k2, hd) <= fminf(e2, hi))) { ++c_leaf; leaf_test_q<true>(r, c0, c1, c2, p2, cull_eps); }
-        if ((i3 >= 0) & (fmaxf(k3, hd) <= fminf(e3, hi))) { ++c_leaf; leaf_test_q<true>(r, d0, d1, d2, p3, cull_eps); }
-        return;
-    }
-    const float hi = kRealMax;   // nothing hit yet: r.t = FLT_MAX
-    const float hd = 0.5f * kDelta;
-    // the node is the same for every lane (links uniform): a child slot that is
-    // empty (-1, fewer than 4 emitters) skips its slab test as a whole wave
-    const int i0 = __float_as_int(q6.x), i1 = __float_as_int(q6.y), i2 = __float_as_int(q6.z),
-              i3 = __float_as_int(q6.w);
-    float k, e;
-    if (i0 >= 0) {
-        slab_minmax(r.o, r.inv, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, k, e);
-        if (fmaxf(k, hd) <= fminf(e, hi)) { ++c_leaf; leaf_test<true>(r, tri, (i0 & kLinkMask) - nint, cull_eps); }
-    }
-    if (i1 >= 0) {
-        slab_minmax(r.o, r.inv, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, k, e);
-        if (fmaxf(k, hd) <= fminf(e, hi)) { ++c_leaf; leaf_test<true>(r, tri, (i1 & kLinkMask) - nint, cull_eps); }
-    }
-    if (i2 >= 0) {
-        slab_minmax(r.o, r.inv, q3.x, q3.y, q3.z, q3.w, q4.x, q4.y, k, e);
-        if (fmaxf(k, hd) <= fminf(e, hi)) { ++c_leaf; leaf_test<true>(r, tri, (i2 & kLinkMask) - nint, cull_eps); }
-    }
-    if (i3 >= 0) {
-        slab_minmax(r.o, r.inv, q4.z, q4.w, q5.x, q5.y, q5.z, q5.w, k, e);
-        if (fmaxf(k, hd) <= fminf(e, hi)) { ++c_leaf; leaf_test<true>(r, tri, (i3 & kLinkMask) - nint, cull_eps); }
-    }
 }
 
 // Direct-probe pre-test (path_tracer.cu:382-405; DESIGN.md section 5 "Probe
@@ -872,14 +631,10 @@ __device__ __forceinline__ V3 reflect_dir(V3 d, V3 n) { return d - (2.0f * dot(d
 // HemisphereCosine's frame (sampler.h:75-89) for the incident-side normal:
 // getNewDirection flips n toward the incident side (path_tracer.cu:216-218),
 // then xBase = (1, 0, -n.x / n.z) / |.| (or (0, 0, 1)), zBase = xBase x n.
-// The direct probe (:387-389) samples the same hemisphere as the bounce's
-// extension ray (same incident direction and normal), so a shading pass
-// computes the frame once and both samples use it (the same values as two
-// evaluations: bit-identical).
-// TPT_SHARE_HEMI 1 keeps the whole frame (6 floats) for the probe; 2 keeps
-// only the two values that cost divides and a sqrt -- q = -n.x / n.z and
-// r = 1 / |xBase| -- and rebuilds n, xBase = r * (1, 0, q) (or r * (0, 0, 1))
-// from them: the same values, two live registers instead of six.
+// q = -n.x / n.z and r = 1 / |xBase| are dead fields, kept only for codegen stability: no caller
+// reads them, but a second use of q keeps the compiler from folding its select into xBase's, and
+// without them every kernel's diffuse path gains 3-7 instructions.  To be removed in a change of
+// their own, measured on the GPU (they are what is left of the withdrawn shared-frame experiment).
 struct Hemi {
     V3 n, xb;
     float q, r;
@@ -893,18 +648,11 @@ __device__ __forceinline__ Hemi hemi_basis(V3 d, V3 n) {
     xb = r * xb;
     return Hemi{n, xb, q, r};
 }
-__device__ __forceinline__ Hemi hemi_rebuild(V3 d, V3 n, float q, float r) {
-    const float sign = dot(d, n) > 0.0f ? -1.0f : 1.0f;
-    n = sign * n;
-    const V3 xb = r * (n.z == 0.0f ? v3(0.0f, 0.0f, 1.0f) : v3(1.0f, 0.0f, q));
-    return Hemi{n, xb, q, r};
-}
 
 // getNewDirection (path_tracer.cu:187-225) for a material (eta, metallic).
 // Returns the pdf; consumes 1 (dielectric), 0 (metal) or 2 (diffuse) uniforms.
-// hb / hb_ok: the pass's hemisphere frame for (d, n), computed on first use.
 __device__ __forceinline__ float new_direction(V3 d, V3 n, float eta_m, float metallic, uint32_t st[6], V3& next,
-                                               float& atten, Hemi& hb, bool& hb_ok) {
+                                               float& atten) {
     if (eta_m > 0.0f) {
         // refract (:143-163)
         float cos_i = dot(d, n);
@@ -934,12 +682,7 @@ __device__ __forceinline__ float new_direction(V3 d, V3 n, float eta_m, float me
         next = reflect_dir(d, n);
         return 1.0f;
     }
-    if (TPT_SHARE_HEMI == 2 && hb_ok) {
-        hb = hemi_rebuild(d, n, hb.q, hb.r);
-    } else if (!hb_ok) {
-        hb = hemi_basis(d, n);
-        hb_ok = true;
-    }
+    const Hemi hb = hemi_basis(d, n);
     n = hb.n;
     const V3 xb = hb.xb;
     // HemisphereCosine (sampler.h:75-89)
@@ -1015,18 +758,15 @@ __device__ __forceinline__ int env_row_exact(float y, int h) {
 // env_lookup_call of the other variants).
 static __device__ __noinline__ int env_col_exact_call(float z, float x, int w) { return env_col_exact(z, x, w); }
 static __device__ __noinline__ int env_row_exact_call(float y, int h) { return env_row_exact(y, h); }
-#ifndef TPT_ENV_COLD_CALL
-#define TPT_ENV_COLD_CALL 1
-#endif
 template <bool COLD>
 __device__ __forceinline__ V3 env_lookup_inl(const uint32_t* __restrict__ env, int w, int h, V3 d) {
     // the texel indices from fp32 bounds (ptrig.hpp env_col_fast / env_row_fast:
     // the same indices as the double evaluation wherever they decide); the
     // double path only within ~1e-3 texel of an edge
-    int ix = TPT_ENV_FAST ? env_col_fast(d.z, d.x, w) : -1;
-    int iy = TPT_ENV_FAST ? env_row_fast(d.y, h) : -1;
-    if (ix < 0) ix = (COLD && TPT_ENV_COLD_CALL) ? env_col_exact_call(d.z, d.x, w) : env_col_exact(d.z, d.x, w);
-    if (iy < 0) iy = (COLD && TPT_ENV_COLD_CALL) ? env_row_exact_call(d.y, h) : env_row_exact(d.y, h);
+    int ix = env_col_fast(d.z, d.x, w);
+    int iy = env_row_fast(d.y, h);
+    if (ix < 0) ix = COLD ? env_col_exact_call(d.z, d.x, w) : env_col_exact(d.z, d.x, w);
+    if (iy < 0) iy = COLD ? env_row_exact_call(d.y, h) : env_row_exact(d.y, h);
     const uint32_t t = env[(size_t)iy * (size_t)w + (size_t)ix];
     return (1.0f / 255.0f) * v3((float)(t & 0xffu), (float)((t >> 8) & 0xffu), (float)((t >> 16) & 0xffu));
 }
@@ -1040,7 +780,7 @@ static __device__ __noinline__ V3 env_lookup_call(const uint32_t* __restrict__ e
 }
 template <bool INLINE>
 __device__ __forceinline__ V3 env_lookup(const uint32_t* __restrict__ env, int w, int h, V3 d) {
-    if constexpr (INLINE || TPT_ENV_INLINE) return env_lookup_inl<true>(env, w, h, d);
+    if constexpr (INLINE) return env_lookup_inl<true>(env, w, h, d);
     else return env_lookup_call(env, w, h, d);
 }
 
@@ -1223,7 +963,7 @@ __device__ __forceinline__ void trav_lane(Trav& r, const TraceArgs& a, LaneStack
         if (r.node < nint) {
             int next;
             if (ORDERED && r.fin) {
-                next = inner_visit4(r, a.inner4, nullptr, 0, stk, r.sp);
+                next = inner_visit4(r, a.inner4, 0, stk, r.sp);
             } else {
                 int deferred;
                 bool push;

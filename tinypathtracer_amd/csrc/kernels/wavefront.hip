@@ -170,8 +170,6 @@ __global__ __launch_bounds__(256) void k_wf_logic(WfArgs w, int init) {
             // ---- consume the finished ray (k_trace's shading pass, path_tracer.cu:356-433) ----
             const int fid = __float_as_int(h.w);
             bool finish = false, lights_next = false, after = false;
-            Hemi hb;
-            bool hb_ok = false;
             V3 L = v3(0.0f, 0.0f, 0.0f);
             if (!LIGHTS) rd = rdir;   // the extension ray's direction
             Surf gpass = gsurf;
@@ -193,7 +191,7 @@ __global__ __launch_bounds__(256) void k_wf_logic(WfArgs w, int init) {
                     const int mtl = __float_as_int(s0.w);
                     const float4 m1 = mt[2 * mtl + 1];
                     float af;
-                    const float prob = new_direction(rd, nrm, m1.x, m1.y, st, nd, af, hb, hb_ok);
+                    const float prob = new_direction(rd, nrm, m1.x, m1.y, st, nd, af);
                     graze_next = grazing(gpass, nd);
                     rec[depth * rw] = af;
                     mk = (uint32_t)mtl | (p_kind(prob) << 30);
@@ -251,9 +249,8 @@ __global__ __launch_bounds__(256) void k_wf_logic(WfArgs w, int init) {
                     if (env_ray) {
                     } else if (!(m1.x >= 1.0f || m1.y > 0.0f)) {   // direct probe (:387-389)
                         float af2;
-                        hb_ok = false;
-                        new_direction(rd, nrm, m1.x, m1.y, st, td, af2, hb, hb_ok);
-                        if ((TPT_PROBE_SHORTCUT && ORDERED && !a.any_emitter) ||
+                        new_direction(rd, nrm, m1.x, m1.y, st, td, af2);
+                        if ((ORDERED && !a.any_emitter) ||
                             (ORDERED && probe_misses_emitters(a, ro, td))) {
                             // the probe's emitter pass ends with no hit, exactly as a
                             // traversal would (still counted: the reference traces it)
@@ -507,7 +504,7 @@ __global__ __launch_bounds__(256, TPT_WF_TRACE_WAVES) void k_wf_trace(WfArgs w) 
                 sliver_pass(r, a, c_leaf);
             }
             ts = WT_TRAV;
-            if (TPT_GRAZE_HIT && ORDERED && (fl & WF_PROBE) && r.fin && r.fid >= 0 && r.mode == TM_EMIT && a.graze &&
+            if (ORDERED && (fl & WF_PROBE) && r.fin && r.fid >= 0 && r.mode == TM_EMIT && a.graze &&
                 grazing(Surf{a.shade[3 * r.fid + 1].w, a.shade[3 * r.fid + 2].w}, r.d)) {
                 // a grazing probe hit: pass 1 again on the uncull'd binary path
                 trav_begin(r, r.o, r.d, r.mode, a.boxes_finite != 0, a.emit_root, a.cull_eps, true);
@@ -519,7 +516,7 @@ __global__ __launch_bounds__(256, TPT_WF_TRACE_WAVES) void k_wf_trace(WfArgs w) 
                 r.sp = 0;
                 r.pend = -1;
                 sl_pend = true;
-            } else if (TPT_GRAZE_HIT && ORDERED && (fl & WF_EXT) && r.fin && r.fid >= 0 && a.graze &&
+            } else if (ORDERED && (fl & WF_EXT) && r.fin && r.fid >= 0 && a.graze &&
                        grazing(Surf{a.shade[3 * r.fid + 1].w, a.shade[3 * r.fid + 2].w}, r.d)) {
                 // a grazing extension hit: traced again on the uncull'd binary path
                 trav_begin(r, r.o, r.d, TM_CLOSEST, a.boxes_finite != 0, a.emit_root, a.cull_eps, true);
@@ -592,7 +589,7 @@ __global__ __launch_bounds__(256, TPT_WF_TRACE_WAVES) void k_wf_trace(WfArgs w) 
                     int next;
                     if (ORDERED && r.fin) {
                         ++c_wide;
-                        next = inner_visit4(r, a.inner4, nullptr, 0, stk, r.sp);
+                        next = inner_visit4(r, a.inner4, 0, stk, r.sp);
                     } else {
                         ++c_inner;
                         int deferred;

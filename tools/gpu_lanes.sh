@@ -5,7 +5,7 @@
 # the wave's next shading pass / without work, and the lanes each shading pass
 # serves.  One 256-spp full-frame launch per config.
 # Usage: [PROF_LIB=variants/NAME] bash tools/gpu_lanes.sh "C2 C5" [extra bench args]
-#   (PROF_LIB: another phase-profiling build, e.g. variants/poolprof = -DTPT_TILE_POOL=1)
+#   (PROF_LIB: another phase-profiling build)
 set -o pipefail
 export TMPDIR=/tmp
 CFGS=${1:-"C2 C5"}; shift; EXTRA="$@"

@@ -51,7 +51,7 @@ HELPERS = [("box_hit", "trav: binary visit"), ("inner_visit", "trav: binary visi
            ("probe_misses_emitters", "pass: probe pre-test"),
            ("trav_begin", "pass: ray set-up (trav_begin)"), ("grazing", "pass: grazing test"),
            ("light_sample", "pass: delta lights"), ("env_lookup_inl", "pass: env lookup"),
-           ("env_is_sample", "pass: env IS"), ("emit_probe_inline", "pass: inline emitter test")]
+           ("env_is_sample", "pass: env IS")]
 
 
 class Src:
