@@ -411,6 +411,65 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* camera, const float* r
                         float* radiance_out, float* variance_out, float* history_len_out,
                         uint8_t* bgra_out, tpt_temporal_stats* stats);
 
+#define TPT_SVGF_DEMODULATE 0x1   /* filter radiance / max(albedo, 1e-3), multiply back afterwards */
+#define TPT_SVGF_DIRECT     0x2   /* A/B: steps 1 and 2 through the direct kernel too instead of the
+                                     LDS-staged one (bit-identical output) */
+
+typedef struct {
+    int32_t iterations;    /* 0..8 */
+    float   sigma_lum;     /* > 0, in standard deviations of the luminance */
+    float   sigma_normal;  /* > 0 */
+    float   sigma_depth;   /* > 0, relative */
+    int32_t min_history;   /* 1..65536: a history shorter than this takes the spatial variance estimate */
+    int32_t flags;         /* TPT_SVGF_* */
+} tpt_svgf_params;
+
+typedef struct {
+    double   pack_ms, estimate_ms, filter_ms, resolve_ms;   /* the kernels' durations (HIP events) */
+    uint64_t estimated;                                      /* pixels that took the spatial estimate */
+} tpt_svgf_stats;
+
+/* Variance-guided a-trous filter (Schied et al. 2017, SVGF) of a radiance frame,
+ * guided by its first-hit normal and depth and by the per-pixel variance of its
+ * luminance, which is filtered alongside the colour.  The filter is defined in
+ * DESIGN.md section 5 "Post-pass".  With L = 0.2126 r + 0.7152 g + 0.0722 b:
+ * iteration i has step 2^i and tpt_denoise's 5x5 taps, each weighted by
+ * exp(-|L(c(p)) - L(c(q))| / (sigma_lum sqrt(vbar(p) + 1e-10))) and tpt_denoise's
+ * normal and depth factors, where vbar is the variance through a 3x3 binomial
+ * prefilter of step 1; the colour is the weighted mean, the variance
+ * sum w^2 v(q) / (sum w)^2.  A pixel whose history is shorter than min_history (N <
+ * min_history, N = max(history_len_in, 1)) starts from a spatial estimate instead of
+ * variance_in: the variance of L over the 7x7 window under the normal and depth
+ * factors, times min_history / N.
+ *   radiance_in / radiance_out / bgra_out: as tpt_denoise's.  iterations 0: radiance_out
+ *     is the input bit for bit.
+ *   guides: normal and depth are required, albedo only with TPT_SVGF_DEMODULATE; face
+ *     and material are ignored.
+ *   variance_in: nullable, W*H: the variance of the luminance of the colour the filter
+ *     works on (tpt_temporal's variance_out; run both passes with or both without
+ *     DEMODULATE).  Negative values count as 0.  Null: every pixel takes the spatial
+ *     estimate with N = 1.
+ *   history_len_in: nullable, W*H (tpt_temporal's history_len_out), only with
+ *     variance_in.  Null with a variance_in: every history counts as long.
+ *   variance_out: nullable, W*H: the filtered variance after the last iteration (with
+ *     iterations 0 the variance the filter would start from).  May be variance_in.
+ *   stats->estimated: the pixels that took the spatial estimate.
+ * Inputs and outputs may be host or device memory (tpt_render's stream rule for
+ * device memory); all work is complete when the call returns.  `scene` supplies the
+ * device, the stream and tpt_denoise's scratch planes (48 B per pixel, and up to 52 B
+ * more to stage host buffers: tpt_denoise's 44 B, the variance and the history
+ * length); it need not be built.  Deterministic: no floating-point atomics.
+ * Non-finite input is the caller's problem.
+ * TPT_ERR_INVALID_ARG (nothing is written): null scene / radiance_in / guides / params,
+ * a missing normal or depth guide, a missing albedo guide under TPT_SVGF_DEMODULATE,
+ * history_len_in without variance_in, width or height <= 0, iterations outside 0..8,
+ * a sigma that is not > 0, min_history outside 1..65536, an unknown flag,
+ * radiance_out and bgra_out both null. */
+tpt_status tpt_denoise_svgf(tpt_scene* scene, int32_t width, int32_t height, const float* radiance_in,
+                            const tpt_aov* guides, const float* variance_in, const float* history_len_in,
+                            const tpt_svgf_params* params, float* radiance_out, float* variance_out,
+                            uint8_t* bgra_out, tpt_svgf_stats* stats);
+
 /* Introspection for tests: copy back the built BVH in the reference node
  * layout (bvh.cuh:52-58, 36 B/node, 2F-1 nodes) and the sorted Morton keys. */
 tpt_status tpt_scene_read_bvh(tpt_scene* scene, void* nodes36, int64_t* keys);

@@ -179,6 +179,19 @@ inline tpt_temporal_params defaultTemporal() {
     return p;
 }
 
+// The hosts' defaults of the variance-guided filter (DESIGN.md section 5 "Post-pass":
+// sigma_lum by the sweep there, not the paper's 4)
+inline tpt_svgf_params defaultSVGF(int iterations = 5) {
+    tpt_svgf_params p{};
+    p.iterations = iterations;
+    p.sigma_lum = 0.5f;
+    p.sigma_normal = 0.3f;
+    p.sigma_depth = 0.05f;
+    p.min_history = 4;
+    p.flags = TPT_SVGF_DEMODULATE;
+    return p;
+}
+
 // tpt_temporal's state across frames (tpt_history).  Declared after the
 // DeviceScene it was created from, so that it is destroyed first.
 class History {
@@ -302,6 +315,21 @@ public:
         tpt_temporal_stats st{};
         check(tpt_temporal(history.handle(), &camera.c, radiance_in, &guides, &params, radiance_out, variance,
                            history_len, framebuffer, &st));
+        return st;
+    }
+
+    // Variance-guided a-trous filter (tpt_denoise_svgf) of a radiance frame, guided by
+    // its feature buffers and by temporal()'s variance and history_len (each nullable:
+    // without a variance every pixel takes the spatial estimate).  radiance_out may be
+    // radiance_in and variance_out variance_in; variance_out and framebuffer are
+    // nullable.  Pointers are host or device memory.
+    tpt_svgf_stats denoiseSVGF(DeviceScene& scene, const float* radiance_in, const tpt_aov& guides,
+                               const float* variance, const float* history_len, float* radiance_out,
+                               float* variance_out = nullptr, uint8_t* framebuffer = nullptr,
+                               const tpt_svgf_params& params = defaultSVGF(5)) {
+        tpt_svgf_stats st{};
+        check(tpt_denoise_svgf(scene.handle(), m_width, m_height, radiance_in, &guides, variance, history_len, &params,
+                               radiance_out, variance_out, framebuffer, &st));
         return st;
     }
 

@@ -417,6 +417,12 @@ def _check_plane(name, buf, width, height):
 TEMPORAL_DEFAULTS = {"alpha": 0.1, "depth_tol": 0.1, "normal_min": 0.9, "max_history": 32, "demodulate": True}
 _PLANES.update(variance=(1, "float32"), history_len=(1, "float32"))
 
+# Defaults of the variance-guided filter of the hosts and the CLI (tpt.hpp defaultSVGF;
+# DESIGN.md section 5 "Post-pass": sigma_lum by the sweep there, not the paper's phi_l = 4, which blurs
+# an accumulated frame whose variance_in is the variance of one frame's luminance)
+SVGF_DEFAULTS = {"iterations": 5, "sigma_lum": 0.5, "sigma_normal": 0.3, "sigma_depth": 0.05, "min_history": 4,
+                 "demodulate": True}
+
 
 class History:
     """tpt_temporal's state across frames (tpt_history): the accumulated colour, the
@@ -641,6 +647,52 @@ class PathTracer:
         cam = camera.to_c()
         check(lib().tpt_temporal(history.handle, C.byref(cam), _addr(radiance), C.byref(g), C.byref(p), _addr(out),
                                  _addr(variance), _addr(history_len), _addr(framebuffer), C.byref(st)))
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out
+
+    def denoiseSVGF(self, d_scene: DeviceScene, radiance, aov, variance=None, history_len=None, *,
+                    iterations: int = SVGF_DEFAULTS["iterations"], sigma_lum: float = SVGF_DEFAULTS["sigma_lum"],
+                    sigma_normal: float = SVGF_DEFAULTS["sigma_normal"],
+                    sigma_depth: float = SVGF_DEFAULTS["sigma_depth"],
+                    min_history: int = SVGF_DEFAULTS["min_history"],
+                    demodulate: bool = SVGF_DEFAULTS["demodulate"], out=None, variance_out=None, framebuffer=None,
+                    flags: int = 0, stats=None):
+        """Variance-guided a-trous filter (tpt_denoise_svgf, DESIGN.md section 5
+        "Post-pass") of `radiance` [H, W, 3] guided by aov["normal"], aov["depth"] (and
+        aov["albedo"] with demodulate) and by temporal()'s `variance` and `history_len`
+        [H, W] float32: a pixel whose history is shorter than min_history takes a spatial
+        variance estimate instead.  variance None: every pixel does; history_len None
+        with a variance: none does.  Run temporal() and this with the same
+        `demodulate`.  out: the filtered radiance's buffer (may be `radiance` itself;
+        None: a new numpy array); variance_out: optional [H, W] float32 for the
+        filtered variance (may be `variance`); framebuffer: optional [H, W, 4] uint8 as
+        doTrace writes it.  Buffers are numpy arrays or torch CUDA tensors.  Returns
+        `out`; stats: a dict that receives pack_ms, estimate_ms, filter_ms, resolve_ms
+        and estimated."""
+        W, H = self.m_width, self.m_height
+        if history_len is not None and variance is None:
+            raise ValueError("history_len needs a variance")
+        _check_plane("radiance", radiance, W, H)
+        g = _lib.Aov()
+        for k in ("albedo", "normal", "depth") if demodulate else ("normal", "depth"):
+            buf = aov.get(k)
+            if buf is not None:
+                _check_plane(k, buf, W, H)
+                setattr(g, k, _addr(buf))
+        if out is None:
+            out = np.zeros((H, W, 3), np.float32)
+        _check_plane("radiance", out, W, H)
+        for name, buf in (("variance", variance), ("history_len", history_len), ("variance", variance_out),
+                          ("framebuffer", framebuffer)):
+            if buf is not None:
+                _check_plane(name, buf, W, H)
+        p = _lib.SvgfParams(int(iterations), float(sigma_lum), float(sigma_normal), float(sigma_depth),
+                            int(min_history), int(flags) | (_lib.SVGF_DEMODULATE if demodulate else 0))
+        st = _lib.SvgfStats()
+        check(lib().tpt_denoise_svgf(d_scene.handle, W, H, _addr(radiance), C.byref(g), _addr(variance),
+                                     _addr(history_len), C.byref(p), _addr(out), _addr(variance_out),
+                                     _addr(framebuffer), C.byref(st)))
         if stats is not None:
             stats.update(st.as_dict())
         return out

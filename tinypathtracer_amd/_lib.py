@@ -26,6 +26,8 @@ DENOISE_DEMODULATE = 0x1
 DENOISE_DIRECT = 0x2
 TEMPORAL_DEMODULATE = 0x1
 TEMPORAL_TILES = 0x2
+SVGF_DEMODULATE = 0x1
+SVGF_DIRECT = 0x2
 
 
 class Material(C.Structure):
@@ -67,6 +69,19 @@ class Params(C.Structure):
                 ("lanes_per_pixel", C.c_int32), ("leaf_batch", C.c_int32), ("wf_slots", C.c_int32),
                 ("wf_refill", C.c_int32), ("band_list_len", C.c_int32), ("band_list", C.POINTER(C.c_int32)),
                 ("band_cost", C.POINTER(C.c_float))]
+
+
+class SvgfParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("min_history", C.c_int32), ("flags", C.c_int32)]
+
+
+class SvgfStats(C.Structure):
+    _fields_ = [("pack_ms", C.c_double), ("estimate_ms", C.c_double), ("filter_ms", C.c_double),
+                ("resolve_ms", C.c_double), ("estimated", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -142,6 +157,9 @@ SIGNATURES = [
     ("tpt_temporal", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(Aov),
                                C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(TemporalStats)]),
+    ("tpt_denoise_svgf", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Aov), C.c_void_p,
+                                   C.c_void_p, C.POINTER(SvgfParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(SvgfStats)]),
     ("tpt_scene_read_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_scene_read_world", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_debug_rng_init", C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),

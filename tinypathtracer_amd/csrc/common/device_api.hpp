@@ -333,6 +333,48 @@ constexpr int kTemporalSlots = 256;
 constexpr int kTemporalSlotStride = 16;  // 128 B: one counter per cache line
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t s);
 
+// post.hip: the variance-guided a-trous filter (tpt_denoise_svgf; DESIGN.md section 5
+// "Post-pass").  tpt_denoise's planes, the colour plane's fourth component carrying the
+// variance: colour = (r, g, b, v), guide = (n.xyz, z).
+struct SvgfArgs {                        // pack (inputs -> planes), estimate (plane -> plane), resolve (plane -> outputs)
+    const float* radiance_in;            // pack: W*H*3; resolve reads it again when passthrough
+    const float* albedo;                 // W*H*3 (read when demodulate)
+    const float* normal;                 // pack: W*H*3
+    const float* depth;                  // pack: W*H
+    const float* variance_in;            // pack: nullable, W*H; null: every pixel takes the spatial estimate, N = 1
+    const float* history_len;            // estimate: nullable, W*H; null with a variance_in: no pixel is short
+    const float4* src;                   // estimate, resolve: the plane read
+    float4* dst;                         // pack, estimate: the plane written
+    float4* guide;                       // pack writes it, estimate reads it
+    float* radiance_out;                 // resolve: nullable, W*H*3, row 0 = bottom
+    float* variance_out;                 // resolve: nullable, W*H
+    uint8_t* bgra;                       // resolve: nullable, W*H*4, row 0 = top, alpha untouched
+    unsigned long long* estimated;       // estimate: kTemporalSlots counters, kTemporalSlotStride words apart
+                                         //   (zeroed by the caller): their sum = pixels that took the estimate
+    size_t npix;
+    int32_t width, height;
+    int32_t demodulate;
+    int32_t passthrough;                 // resolve: radiance_out = radiance_in bit for bit (iterations 0)
+    float min_history;
+    float inv_sn2;                       // 1 / sigma_n^2
+    float sz2;                           // sigma_z^2
+};
+struct SvgfFilterArgs {                  // one iteration: dst = filter(src) at this step
+    const float4* src;
+    const float4* guide;
+    float4* dst;
+    int32_t width, height;
+    int32_t step;                        // 2^i
+    float sigma_lum;
+    float inv_sn2;                       // 1 / sigma_n^2
+    float sz2;                           // sigma_z^2
+};
+hipError_t launch_svgf_pack(const SvgfArgs& a, hipStream_t s);
+hipError_t launch_svgf_estimate(const SvgfArgs& a, hipStream_t s);
+// use_lds: steps 1 and 2 through the LDS-staged kernel (bit-identical to the direct one)
+hipError_t launch_svgf_filter(const SvgfFilterArgs& a, bool use_lds, hipStream_t s);
+hipError_t launch_svgf_resolve(const SvgfArgs& a, hipStream_t s);
+
 }  // namespace tpt
 
 // The tolerance-mode build of trace.hip (TPT_FLAG_FAST; Makefile trace_fast.hip.o):

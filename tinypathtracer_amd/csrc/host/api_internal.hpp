@@ -370,9 +370,16 @@ struct tpt_scene {
     DevBuf<float4> dn_color[2], dn_guide;
     DevBuf<float> dn_rad, dn_f3[2], dn_depth;   // radiance in / out; albedo, normal; depth
     DevBuf<uint8_t> dn_bgra;
+    // tpt_denoise_svgf: the planes and staging above, and of its own the staging of the variance
+    // (in and out share it), of the history length, the counters of SvgfArgs::estimated and a fifth event
+    DevBuf<float> sv_var, sv_len;
+    DevBuf<unsigned long long> sv_count;
+    HostPinned<unsigned long long> sv_h_count;
+    hipEvent_t sv_ev = nullptr;
 
     ~tpt_scene() {
         DeviceGuard g(device);
+        if (sv_ev) (void)hipEventDestroy(sv_ev);
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
         for (auto& e : lev)

@@ -1,5 +1,5 @@
 // api_post.cpp -- the post-pass entry points of the C-ABI (post.hip): tpt_render_aov,
-// tpt_denoise, tpt_history_* and tpt_temporal.  Each takes its buffers from either
+// tpt_denoise, tpt_history_*, tpt_temporal and tpt_denoise_svgf.  Each takes its buffers from either
 // side: host buffers go through the device staging the scene / history keeps
 // (api_internal.hpp Staging).
 #include <cmath>
@@ -278,6 +278,117 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radi
         HIP_OR_FAIL(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
         stats->kernel_ms = ms;
         stats->reprojected = found;
+    }
+    return TPT_OK;
+}
+
+// The variance-guided a-trous filter (post.hip k_svgf_*; DESIGN.md section 5
+// "Post-pass"): pack into plane 0, the spatial variance estimate into plane 1, one
+// launch per iteration between the two, resolve.  Where no pixel can be short (a
+// variance without history lengths) the estimate is not launched.
+tpt_status tpt_denoise_svgf(tpt_scene* s, int32_t W, int32_t H, const float* radiance_in, const tpt_aov* guides,
+                            const float* variance_in, const float* history_len_in, const tpt_svgf_params* p,
+                            float* radiance_out, float* variance_out, uint8_t* bgra_out, tpt_svgf_stats* stats) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (!radiance_in) return fail(TPT_ERR_INVALID_ARG, "null radiance_in");
+    if (!guides) return fail(TPT_ERR_INVALID_ARG, "null guides");
+    if (!p) return fail(TPT_ERR_INVALID_ARG, "null params");
+    if (p->flags & ~(TPT_SVGF_DEMODULATE | TPT_SVGF_DIRECT)) return fail(TPT_ERR_INVALID_ARG, "unknown svgf flags");
+    const bool demod = (p->flags & TPT_SVGF_DEMODULATE) != 0;
+    if (!guides->normal || !guides->depth)
+        return fail(TPT_ERR_INVALID_ARG, "the variance-guided filter needs the normal and depth guides");
+    if (demod && !guides->albedo) return fail(TPT_ERR_INVALID_ARG, "TPT_SVGF_DEMODULATE needs the albedo guides");
+    if (history_len_in && !variance_in)
+        return fail(TPT_ERR_INVALID_ARG, "history_len_in needs a variance_in");
+    if (W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size: width and height must be > 0");
+    if (p->iterations < 0 || p->iterations > 8) return fail(TPT_ERR_INVALID_ARG, "iterations must be 0..8");
+    if (!(p->sigma_lum > 0.0f) || !(p->sigma_normal > 0.0f) || !(p->sigma_depth > 0.0f))
+        return fail(TPT_ERR_INVALID_ARG, "sigma_lum, sigma_normal and sigma_depth must be > 0");
+    if (p->min_history < 1 || p->min_history > 65536) return fail(TPT_ERR_INVALID_ARG, "min_history must be 1..65536");
+    if (!radiance_out && !bgra_out) return fail(TPT_ERR_INVALID_ARG, "no output buffer: radiance_out and bgra_out are null");
+    DeviceGuard g(s->device);
+    hipStream_t st = s->stream;
+    const size_t npix = (size_t)W * (size_t)H;
+    HIP_OR_FAIL(s->dn_color[0].alloc(npix));
+    HIP_OR_FAIL(s->dn_color[1].alloc(npix));
+    HIP_OR_FAIL(s->dn_guide.alloc(npix));
+    HIP_OR_FAIL(s->sv_count.alloc(kCountWords));
+    HIP_OR_FAIL(s->sv_h_count.alloc(kCountWords));
+    if (!s->sv_ev) HIP_OR_FAIL(hipEventCreate(&s->sv_ev));
+    constexpr double kFltMax = 3.402823466e+38;
+    tpt::SvgfArgs d{};
+    d.npix = npix;
+    d.width = W;
+    d.height = H;
+    d.demodulate = demod ? 1 : 0;
+    d.passthrough = p->iterations == 0 ? 1 : 0;   // the input bit for bit, so no demodulation round trip
+    d.min_history = (float)p->min_history;
+    d.inv_sn2 = (float)std::min(1.0 / ((double)p->sigma_normal * p->sigma_normal), kFltMax);
+    d.sz2 = (float)((double)p->sigma_depth * p->sigma_depth);
+    d.guide = s->dn_guide.p;
+    d.estimated = s->sv_count.p;
+    Staging sg(st);
+    HIP_OR_FAIL(sg.in(s->dn_rad, radiance_in, 3 * npix, &d.radiance_in));
+    HIP_OR_FAIL(sg.in(s->dn_f3[0], demod ? guides->albedo : nullptr, 3 * npix, &d.albedo));
+    HIP_OR_FAIL(sg.in(s->dn_f3[1], guides->normal, 3 * npix, &d.normal));
+    HIP_OR_FAIL(sg.in(s->dn_depth, guides->depth, npix, &d.depth));
+    HIP_OR_FAIL(sg.in(s->sv_var, variance_in, npix, &d.variance_in));
+    HIP_OR_FAIL(sg.in(s->sv_len, history_len_in, npix, &d.history_len));
+    // radiance in and out share dn_rad, variance in and out sv_var: pack has read them by
+    // the time resolve writes them (iterations 0: resolve's lane reads its pixel, then writes it)
+    HIP_OR_FAIL(sg.out(s->dn_rad, radiance_out, 3 * npix, &d.radiance_out));
+    HIP_OR_FAIL(sg.out(s->sv_var, variance_out, npix, &d.variance_out));
+    // alpha is untouched: the caller's bytes go up first
+    HIP_OR_FAIL(sg.inout(s->dn_bgra, bgra_out, 4 * npix, &d.bgra));
+    HIP_OR_FAIL(hipMemsetAsync(s->sv_count.p, 0, kCountWords * sizeof(unsigned long long), st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
+    d.dst = s->dn_color[0].p;
+    HIP_OR_FAIL(tpt::launch_svgf_pack(d, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
+    int cur = 0;   // the plane that holds (c_i, v_i)
+    if (!(variance_in && !history_len_in)) {
+        d.src = s->dn_color[0].p;
+        d.dst = s->dn_color[1].p;
+        HIP_OR_FAIL(tpt::launch_svgf_estimate(d, st));
+        cur = 1;
+    }
+    HIP_OR_FAIL(hipEventRecord(s->ev[2], st));
+    tpt::SvgfFilterArgs f{};
+    f.guide = s->dn_guide.p;
+    f.width = W;
+    f.height = H;
+    f.sigma_lum = p->sigma_lum;
+    f.inv_sn2 = d.inv_sn2;
+    f.sz2 = d.sz2;
+    const bool use_lds = !(p->flags & TPT_SVGF_DIRECT);
+    for (int i = 0; i < p->iterations; ++i) {
+        f.src = s->dn_color[cur].p;
+        f.dst = s->dn_color[cur ^ 1].p;
+        f.step = 1 << i;
+        HIP_OR_FAIL(tpt::launch_svgf_filter(f, use_lds, st));
+        cur ^= 1;
+    }
+    HIP_OR_FAIL(hipEventRecord(s->ev[3], st));
+    d.src = s->dn_color[cur].p;
+    HIP_OR_FAIL(tpt::launch_svgf_resolve(d, st));
+    HIP_OR_FAIL(hipEventRecord(s->sv_ev, st));
+    HIP_OR_FAIL(sg.finish());
+    HIP_OR_FAIL(hipMemcpyAsync(s->sv_h_count.p, s->sv_count.p, kCountWords * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    if (stats) {
+        unsigned long long found = 0;
+        for (int k = 0; k < tpt::kTemporalSlots; ++k) found += s->sv_h_count.p[(size_t)k * tpt::kTemporalSlotStride];
+        float ms = 0.0f;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        stats->pack_ms = ms;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
+        stats->estimate_ms = ms;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+        stats->filter_ms = ms;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[3], s->sv_ev));
+        stats->resolve_ms = ms;
+        stats->estimated = found;
     }
     return TPT_OK;
 }

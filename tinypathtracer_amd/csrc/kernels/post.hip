@@ -13,6 +13,10 @@
 //    between two colour planes, no atomics.  Each tap is two 16-B loads per lane;
 //    a wave of the direct kernel is a 64-pixel row segment, so its lanes read
 //    1 KiB of contiguous addresses per plane at every step size.
+//  * k_temporal: reprojection and accumulation across frames (tpt_temporal).
+//  * k_svgf_pack / k_svgf_estimate / k_svgf_atrous / k_svgf_atrous_lds /
+//    k_svgf_resolve: the variance-guided filter (tpt_denoise_svgf) on the same two
+//    planes, the variance in the colour plane's fourth component.
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"   // trace_dev.hpp's env helpers, unused here
 #include "trace_dev.hpp"
 
@@ -432,6 +436,344 @@ hipError_t launch_temporal(const TemporalArgs& a, hipStream_t s) {
         const dim3 grid((a.width + 63) / 64, (a.height + 3) / 4);
         hipLaunchKernelGGL(k_temporal<false>, grid, dim3(64, 4), 0, s, a);
     }
+    return hipGetLastError();
+}
+
+// ---- the variance-guided a-trous filter (Schied et al. 2017; DESIGN.md section 5 "Post-pass" holds the definition) ----
+//
+// tpt_denoise's two float4 planes per pixel, the colour plane's fourth component
+// carrying the variance of the luminance: a tap is still two 16-B loads, and the
+// variance is filtered without memory traffic of its own.  Pack, the spatial variance
+// estimate of the pixels with a short history (plane 0 -> plane 1), one launch per
+// iteration between the two colour planes, resolve.  A tap outside the frame is not
+// skipped by a branch but given the weight 0, its loads sent to the lane's own pixel
+// (the LDS variant reads its zero-filled halo): the same sums, and a row's loads are
+// unconditional, so they are issued together ahead of their use.
+
+__device__ __forceinline__ float svgf_lum(float r, float g, float b) {   // k_temporal's L
+    return (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+}
+
+// tpt_denoise's two guide factors as one exponent: |dn|^2 / sigma_n^2 + dz^2 kz
+__device__ __forceinline__ float guide_kz(float z, float sz2) {   // 1 / (sigma_z^2 max(z^2, 1e-12)), finite as Taps::kz
+    return fminf(1.0f / (sz2 * fmaxf(z * z, 1e-12f)), kRealMax);
+}
+__device__ __forceinline__ float guide_arg(float4 gp, float4 gq, float inv_sn2, float kz) {
+    const float nx = gq.x - gp.x, ny = gq.y - gp.y, nz = gq.z - gp.z, dz = gq.w - gp.w;
+    return (nx * nx + ny * ny + nz * nz) * inv_sn2 + (dz * dz) * kz;
+}
+
+__global__ __launch_bounds__(256) void k_svgf_pack(SvgfArgs a) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.npix) return;
+    float r = a.radiance_in[3 * p], g = a.radiance_in[3 * p + 1], b = a.radiance_in[3 * p + 2];
+    if (a.demodulate) {
+        r = r / fmaxf(a.albedo[3 * p], kAlbedoFloor);
+        g = g / fmaxf(a.albedo[3 * p + 1], kAlbedoFloor);
+        b = b / fmaxf(a.albedo[3 * p + 2], kAlbedoFloor);
+    }
+    const float v = a.variance_in ? fmaxf(a.variance_in[p], 0.0f) : 0.0f;
+    a.dst[p] = make_float4(r, g, b, v);
+    a.guide[p] = make_float4(a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2], a.depth[p]);
+}
+
+// The spatial estimate: 16x16 tiles; a pixel with N < min_history replaces its
+// variance by that of L over its 7x7 window under the guide weight, times min_history
+// / N; every other pixel is copied.  The tile and its halo of 3 pixels are staged in
+// LDS as the luminance and the guide (22^2 x 20 B = 9.5 KB: L is computed once per
+// staged pixel, not once per tap), and only short lanes walk the 49 taps.  A block
+// without a short pixel copies its pixels and leaves before staging anything.  The
+// moments are taken about the centre's luminance: the same variance, without the
+// cancellation of mu2 - mu1^2 at a large mean, and exactly 0 on a constant window.
+__global__ __launch_bounds__(256) void k_svgf_estimate(SvgfArgs a) {
+    constexpr int T = 16 + 2 * 3;
+    __shared__ float sl[T * T];
+    __shared__ LdsF4 sg_[T * T];
+    TPT_LDS LdsF4* sg = (TPT_LDS LdsF4*)sg_;
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int x = (int)blockIdx.x * 16 + tx, y = (int)blockIdx.y * 16 + ty;
+    const bool inside = x < a.width && y < a.height;
+    const size_t p = inside ? (size_t)y * (size_t)a.width + (size_t)x : 0;
+    float N = 1.0f;
+    bool is_short = false;
+    if (inside) {
+        if (!a.variance_in) is_short = true;
+        else if (a.history_len) {
+            N = fmaxf(a.history_len[p], 1.0f);
+            is_short = N < a.min_history;
+        }
+    }
+    // the statistic, as k_temporal's: one integer atomic per wave over the spread counters
+    const unsigned long long found = __ballot(is_short);
+    if ((tid & 63) == 0 && found) {
+        const unsigned slot = ((unsigned)blockIdx.y * gridDim.x + (unsigned)blockIdx.x) % (unsigned)kTemporalSlots;
+        atomicAdd(a.estimated + (size_t)slot * kTemporalSlotStride, (unsigned long long)__popcll(found));
+    }
+    if (!__syncthreads_or(is_short ? 1 : 0)) {
+        if (inside) a.dst[p] = a.src[p];
+        return;
+    }
+    const int x0 = (int)blockIdx.x * 16 - 3, y0 = (int)blockIdx.y * 16 - 3;
+    for (int i = tid; i < T * T; i += 256) {
+        const int gx = x0 + i % T, gy = y0 + i / T;
+        float l = 0.0f;
+        float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) {   // (outside the frame: weight 0 below)
+            const size_t q = (size_t)gy * (size_t)a.width + (size_t)gx;
+            const float4 c = a.src[q];
+            l = svgf_lum(c.x, c.y, c.z);
+            g = a.guide[q];
+        }
+        sl[i] = l;
+        sg[i].x = g.x;
+        sg[i].y = g.y;
+        sg[i].z = g.z;
+        sg[i].w = g.w;
+    }
+    __syncthreads();
+    if (!inside) return;
+    float4 c = a.src[p];
+    if (is_short) {
+        const int c0 = (ty + 3) * T + tx + 3;
+        const float lp = sl[c0];
+        const float4 gp = lds_f4(sg + c0);
+        const float kz = guide_kz(gp.w, a.sz2);
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+        for (int dy = -3; dy <= 3; ++dy) {
+            const bool row_in = y + dy >= 0 && y + dy < a.height;
+#pragma unroll
+            for (int dx = -3; dx <= 3; ++dx) {
+                const bool in = row_in && x + dx >= 0 && x + dx < a.width;
+                const int q = c0 + dy * T + dx;
+                const float d = sl[q] - lp;
+                const float w = in ? __expf(-guide_arg(gp, lds_f4(sg + q), a.inv_sn2, kz)) : 0.0f;
+                s0 += w;
+                s1 += w * d;
+                s2 += w * (d * d);
+            }
+        }
+        const float m1 = s1 / s0, m2 = s2 / s0;   // the centre tap: s0 >= 1
+        c.w = fmaxf(m2 - m1 * m1, 0.0f) * (a.min_history / N);
+    }
+    a.dst[p] = c;
+}
+
+// One pixel's accumulation over its taps, as Taps: the mean kept as c(p) + sum w dc /
+// sum w, one exponential per tap.  The luminance factor's scale comes from the
+// prefiltered variance at p; the variance summed is the unprefiltered one at q.
+struct SvgfTaps {
+    float4 cp, gp;
+    float lp, kl, kz;   // L(c(p)); 1 / (sigma_l sqrt(vbar + 1e-10)); 1 / (sigma_z^2 max(z(p)^2, 1e-12))
+    float sw, ar, ag, ab, av;
+    __device__ __forceinline__ void begin(float4 c, float4 g, float vbar, float sigma_lum, float sz2) {
+        cp = c;
+        gp = g;
+        lp = svgf_lum(c.x, c.y, c.z);
+        kl = fminf(1.0f / (sigma_lum * fsqrt(vbar + 1e-10f)), kRealMax);   // (finite: the centre tap's 0 * kl is 0)
+        kz = guide_kz(g.w, sz2);
+        sw = 0.0f;
+        ar = ag = ab = av = 0.0f;
+    }
+    // hh: h(dx) h(dy), or 0 for a tap outside the frame (cq, gq then hold any finite values)
+    __device__ __forceinline__ void tap(float hh, float4 cq, float4 gq, float inv_sn2) {
+        const float dr = cq.x - cp.x, dg = cq.y - cp.y, db = cq.z - cp.z;
+        const float e = fabsf(svgf_lum(cq.x, cq.y, cq.z) - lp) * kl + guide_arg(gp, gq, inv_sn2, kz);
+        const float w = hh * __expf(-e);
+        sw += w;
+        ar += w * dr;
+        ag += w * dg;
+        ab += w * db;
+        av += (w * w) * cq.w;
+    }
+    __device__ __forceinline__ float4 end() const {
+        const float inv = 1.0f / sw;   // the centre tap: sw >= h(0)^2 > 0
+        return make_float4(cp.x + ar * inv, cp.y + ag * inv, cp.z + ab * inv, av * (inv * inv));
+    }
+};
+
+// The 3x3 binomial prefilter of the variance, g = [1/4, 1/2, 1/4], over the taps inside
+// the frame (bit k = 3 (dy + 1) + dx + 1 of `in`).  Both filter kernels call it with
+// the same nine values.
+__device__ __forceinline__ float svgf_prefilter(const float (&v)[9], unsigned in) {
+    float s = 0.0f, sw = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const float g = (k / 3 == 1 ? 0.5f : 0.25f) * (k % 3 == 1 ? 0.5f : 0.25f);
+        const float w = ((in >> k) & 1u) ? g : 0.0f;
+        s += w * v[k];
+        sw += w;
+    }
+    return s / sw;   // the centre: sw >= 1/4
+}
+
+// Direct version: every tap from global memory (L1 / L2).  Block (64, 4), a wave a
+// 64-pixel row segment as k_atrous.  The eight prefilter taps around p read the .w
+// words only.  A row's ten loads are issued before its five taps are summed.
+__global__ __launch_bounds__(256) void k_svgf_atrous(SvgfFilterArgs a) {
+    const int x = (int)blockIdx.x * 64 + (int)threadIdx.x, y = (int)blockIdx.y * 4 + (int)threadIdx.y;
+    if (x >= a.width || y >= a.height) return;
+    const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
+    const float4 cp = a.src[p], gp = a.guide[p];
+    const float* vw = (const float*)a.src + 3;
+    float v9[9];
+    unsigned in9 = 0;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int k = 3 * (dy + 1) + dx + 1;
+            const int qx = x + dx, qy = y + dy;
+            const bool in = qx >= 0 && qx < a.width && qy >= 0 && qy < a.height;
+            const size_t q = in ? (size_t)qy * (size_t)a.width + (size_t)qx : p;
+            v9[k] = (dx == 0 && dy == 0) ? cp.w : vw[4 * q];
+            in9 |= in ? 1u << k : 0u;
+        }
+    SvgfTaps t;
+    t.begin(cp, gp, svgf_prefilter(v9, in9), a.sigma_lum, a.sz2);
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = y + dy * a.step;
+        const bool row_in = qy >= 0 && qy < a.height;
+        const size_t row = (size_t)(row_in ? qy : y) * (size_t)a.width;
+        float4 cq[5], gq[5];
+        float hh[5];
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * a.step;
+            const bool in = row_in && qx >= 0 && qx < a.width;
+            const size_t q = in ? row + (size_t)qx : p;
+            cq[dx + 2] = a.src[q];
+            gq[dx + 2] = a.guide[q];
+            hh[dx + 2] = in ? atrous_h(dx) * atrous_h(dy) : 0.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) t.tap(hh[k], cq[k], gq[k], a.inv_sn2);
+    }
+    a.dst[p] = t.end();
+}
+
+// LDS version for steps 1 and 2, as k_atrous_lds: a 16x16 tile and its halo of 2 S
+// pixels staged once, zero-filled outside the frame; the halo holds the prefilter's
+// taps too.  The same taps in the same order as k_svgf_atrous: bit-identical output.
+template <int S>
+__global__ __launch_bounds__(256) void k_svgf_atrous_lds(SvgfFilterArgs a) {
+    constexpr int T = 16 + 4 * S;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    TPT_LDS LdsF4* sc = (TPT_LDS LdsF4*)lds;
+    TPT_LDS LdsF4* sg = sc + T * T;
+    const int tid = threadIdx.x;
+    const int x0 = (int)blockIdx.x * 16 - 2 * S, y0 = (int)blockIdx.y * 16 - 2 * S;
+    for (int i = tid; i < T * T; i += 256) {
+        const int gx = x0 + i % T, gy = y0 + i / T;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g = c;
+        if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) {   // (outside the frame: weight 0 below)
+            const size_t q = (size_t)gy * (size_t)a.width + (size_t)gx;
+            c = a.src[q];
+            g = a.guide[q];
+        }
+        sc[i].x = c.x;
+        sc[i].y = c.y;
+        sc[i].z = c.z;
+        sc[i].w = c.w;
+        sg[i].x = g.x;
+        sg[i].y = g.y;
+        sg[i].z = g.z;
+        sg[i].w = g.w;
+    }
+    __syncthreads();
+    const int tx = tid & 15, ty = tid >> 4;
+    const int x = (int)blockIdx.x * 16 + tx, y = (int)blockIdx.y * 16 + ty;
+    if (x >= a.width || y >= a.height) return;
+    const int c0 = (ty + 2 * S) * T + tx + 2 * S;
+    const float4 cp = lds_f4(sc + c0);
+    float v9[9];
+    unsigned in9 = 0;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int k = 3 * (dy + 1) + dx + 1;
+            const int qx = x + dx, qy = y + dy;
+            const bool in = qx >= 0 && qx < a.width && qy >= 0 && qy < a.height;
+            v9[k] = (dx == 0 && dy == 0) ? cp.w : sc[c0 + dy * T + dx].w;
+            in9 |= in ? 1u << k : 0u;
+        }
+    SvgfTaps t;
+    t.begin(cp, lds_f4(sg + c0), svgf_prefilter(v9, in9), a.sigma_lum, a.sz2);
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = y + dy * S;
+        const bool row_in = qy >= 0 && qy < a.height;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * S;
+            const bool in = row_in && qx >= 0 && qx < a.width;
+            const int q = c0 + dy * S * T + dx * S;
+            t.tap(in ? atrous_h(dx) * atrous_h(dy) : 0.0f, lds_f4(sc + q), lds_f4(sg + q), a.inv_sn2);
+        }
+    }
+    a.dst[(size_t)y * (size_t)a.width + (size_t)x] = t.end();
+}
+
+// Re-modulation and the outputs, with k_dn_resolve's conventions; passthrough
+// (iterations 0): the radiance is the input bit for bit.
+__global__ __launch_bounds__(256) void k_svgf_resolve(SvgfArgs a) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.npix) return;
+    const float4 c = a.src[p];
+    float r = c.x, g = c.y, b = c.z;
+    if (a.passthrough) {
+        r = a.radiance_in[3 * p];
+        g = a.radiance_in[3 * p + 1];
+        b = a.radiance_in[3 * p + 2];
+    } else if (a.demodulate) {
+        r = r * fmaxf(a.albedo[3 * p], kAlbedoFloor);
+        g = g * fmaxf(a.albedo[3 * p + 1], kAlbedoFloor);
+        b = b * fmaxf(a.albedo[3 * p + 2], kAlbedoFloor);
+    }
+    if (a.radiance_out) {
+        a.radiance_out[3 * p] = r;
+        a.radiance_out[3 * p + 1] = g;
+        a.radiance_out[3 * p + 2] = b;
+    }
+    if (a.variance_out) a.variance_out[p] = c.w;
+    if (a.bgra) {
+        const size_t y = p / (size_t)a.width, x = p - y * (size_t)a.width;
+        uint8_t* px = a.bgra + 4 * (((size_t)a.height - y - 1) * (size_t)a.width + x);
+        px[0] = to_uchar(b);
+        px[1] = to_uchar(g);
+        px[2] = to_uchar(r);
+    }
+}
+
+hipError_t launch_svgf_pack(const SvgfArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_svgf_pack, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_svgf_estimate(const SvgfArgs& a, hipStream_t s) {
+    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+    hipLaunchKernelGGL(k_svgf_estimate, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_svgf_filter(const SvgfFilterArgs& a, bool use_lds, hipStream_t s) {
+    if (use_lds && (a.step == 1 || a.step == 2)) {
+        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+        const int T = 16 + 4 * a.step;
+        const size_t lds = (size_t)T * T * 32;
+        if (a.step == 1) hipLaunchKernelGGL(k_svgf_atrous_lds<1>, grid, dim3(256), lds, s, a);
+        else hipLaunchKernelGGL(k_svgf_atrous_lds<2>, grid, dim3(256), lds, s, a);
+    } else {
+        const dim3 grid((a.width + 63) / 64, (a.height + 3) / 4);
+        hipLaunchKernelGGL(k_svgf_atrous, grid, dim3(64, 4), 0, s, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_svgf_resolve(const SvgfArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_svgf_resolve, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

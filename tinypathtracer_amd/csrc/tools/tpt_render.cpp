@@ -6,13 +6,17 @@
 //   tpt_render scene.gltf [--width W] [--height H] [--spp N] [--depth D]
 //              [--seed S] [--env equirect.jpg|.ppm|--sky] [--out prefix] [--device i]
 //              [--frames F [--progressive]] [--aov] [--denoise [iterations]]
-//              [--temporal] [--yaw DEG]
+//              [--temporal] [--yaw DEG] [--svgf [iterations]]
 // --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
 // <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
 // a-trous filter of the written frame (tpt_denoise, the hosts' defaults; with
 // --progressive the written frame is the accumulated one).  --temporal runs every
 // frame (frame i with seed S + i) and its feature buffers through tpt_temporal and
 // writes <out>_temporal.pfm / .ppm for the last one; --denoise then filters that.
+// --svgf writes <out>_svgf.pfm / .ppm, the variance-guided filter (tpt_denoise_svgf, the
+// hosts' defaults): with --temporal of the accumulated frame, by that pass's variance
+// and history length; without it of the written frame, on the spatial variance
+// estimate alone.  --denoise and --svgf may be combined: both files are written.
 // --yaw DEG turns the camera about its own origin and up axis by DEG per frame.
 #include <cmath>
 #include <cstdio>
@@ -71,7 +75,7 @@ void write_pfm(const std::string& path, const std::vector<float>& v, int W, int 
 const char* kUsage =
     "usage: %s scene.gltf [--width W] [--height H] [--spp N] [--depth D] [--seed S] "
     "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]] "
-    "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG]\n";
+    "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]]\n";
 
 // The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
 tpt::Camera yawed(const tpt::Camera& base, double deg) {
@@ -94,9 +98,10 @@ int main(int argc, char** argv) {
     }
     std::string scene_file = argv[1], env_file, out = "out";
     int W = 1920, H = 1080, spp = 64, depth = 8, device = 0, frames = 1;
-    bool progressive = false, aov = false, denoise = false, temporal = false;
+    bool progressive = false, aov = false, denoise = false, temporal = false, svgf = false;
     double yaw = 0.0;
     int dn_iterations = tpt::defaultDenoise().iterations;
+    int sv_iterations = tpt::defaultSVGF().iterations;
     uint64_t seed = 0;
     bool sky = false;
     for (int i = 2; i < argc; ++i) {
@@ -123,6 +128,10 @@ int main(int argc, char** argv) {
             denoise = true;   // an optional iteration count follows
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn_iterations = std::stoi(argv[++i]);
         }
+        else if (a == "--svgf") {
+            svgf = true;   // an optional iteration count follows
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') sv_iterations = std::stoi(argv[++i]);
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (temporal && progressive) {   // progressive is already the exact accumulation of an unmoving camera
@@ -148,18 +157,21 @@ int main(int argc, char** argv) {
         f.bgra.assign((size_t)W * H * 4, 255);
         f.radiance.assign((size_t)W * H * 3, 0.0f);
         tpt::Camera cam = scene.m_camera;
-        std::vector<float> acc;       // --temporal: the accumulated frame
+        std::vector<float> acc;       // --temporal: the accumulated frame,
+        std::vector<float> var, len;  //   its luminance variance and history length
         tpt::AOV g;
         if (temporal) {
             tpt::History hist(d, W, H);
             acc.resize((size_t)W * H * 3);
+            var.resize((size_t)W * H);
+            len.resize((size_t)W * H);
             std::vector<uint8_t> fb((size_t)W * H * 4, 255);
             const uint64_t base = seed ? seed : (uint64_t)std::time(nullptr);
             for (int i = 0; i < frames; ++i) {
                 cam = yawed(scene.m_camera, yaw * i);
                 f.stats = pt.doTrace(d, cam, f.bgra.data(), spp, base + (uint64_t)i, depth, f.radiance.data());
                 g = pt.renderAOV(d, cam);
-                pt.temporal(hist, cam, f.radiance.data(), g.view(), acc.data(), nullptr, nullptr, fb.data());
+                pt.temporal(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(), fb.data());
             }
             write_pfm(out + "_temporal.pfm", acc, W, H, 3);
             write_ppm(out + "_temporal.ppm", fb, W, H);
@@ -172,7 +184,7 @@ int main(int argc, char** argv) {
         }
         write_ppm(out + ".ppm", f.bgra, W, H);
         write_pfm(out + ".pfm", f.radiance, W, H, 3);
-        if (aov || denoise) {
+        if (aov || denoise || svgf) {
             if (!temporal) g = pt.renderAOV(d, cam);
             if (aov) {
                 write_pfm(out + "_albedo.pfm", g.albedo, W, H, 3);
@@ -186,6 +198,15 @@ int main(int argc, char** argv) {
                            tpt::defaultDenoise(dn_iterations));
                 write_pfm(out + "_denoised.pfm", clean, W, H, 3);
                 write_ppm(out + "_denoised.ppm", fb, W, H);
+            }
+            if (svgf) {   // of the temporal output, by its variance and history length, when there is one
+                std::vector<float> clean((size_t)W * H * 3);
+                std::vector<uint8_t> fb((size_t)W * H * 4, 255);
+                pt.denoiseSVGF(d, temporal ? acc.data() : f.radiance.data(), g.view(), temporal ? var.data() : nullptr,
+                               temporal ? len.data() : nullptr, clean.data(), nullptr, fb.data(),
+                               tpt::defaultSVGF(sv_iterations));
+                write_pfm(out + "_svgf.pfm", clean, W, H, 3);
+                write_ppm(out + "_svgf.ppm", fb, W, H);
             }
         }
         const tpt_stats& s = f.stats;
