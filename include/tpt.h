@@ -243,6 +243,20 @@ tpt_status tpt_scene_build_async(tpt_scene* scene);
  * Every setting builds the same tree.  Processes sharing a host (one per GPU)
  * pass their share of the cores. */
 tpt_status tpt_scene_set_build_threads(tpt_scene* scene, int32_t threads);
+/* New local-to-world matrices for objects [first_object, first_object + n_objects): each
+ * 16 floats, column-major, host memory, as tpt_scene_desc's.  normal_trans: nullable; null:
+ * computed from vert_trans as the glTF loader computes it (the inverse transpose of the
+ * linear part).  The vertices stay on the device; the matrices are uploaded on the scene's
+ * stream, a pending tpt_scene_build_async is joined and superseded, and the scene is
+ * unbuilt afterwards: call tpt_scene_build or tpt_scene_build_async before the next
+ * render.  The rebuilt scene is the scene tpt_scene_create + tpt_scene_build make of a
+ * desc with these matrices, bit for bit (world vertices, BVH, rendered frames).  A
+ * progressive accumulation (TPT_FLAG_ACCUMULATE) does not survive it: its sums belong to
+ * the scene as it was, so render the next frame without the flag.
+ * TPT_ERR_INVALID_ARG (nothing changes): null scene or vert_trans, n_objects == 0, a
+ * range past the scene's object count. */
+tpt_status tpt_scene_set_transforms(tpt_scene* scene, uint32_t first_object, uint32_t n_objects,
+                                    const float* vert_trans, const float* normal_trans);
 void tpt_scene_destroy(tpt_scene* scene);
 
 /* Equirect environment, RGBA8, row 0 = bottom (FreeImage order), already in
@@ -357,8 +371,9 @@ tpt_status tpt_denoise(tpt_scene* scene, int32_t width, int32_t height, const fl
  * supplies the device and the stream and need not be built; destroy the history
  * before its scene.  It holds two sets of three float4 planes (accumulated colour +
  * history length; normal + depth; luminance moments + material id), 96 B per pixel,
- * and up to 56 B per pixel more to stage host buffers.  After tpt_history_create and
- * after tpt_history_reset there is no state: the next tpt_temporal starts over. */
+ * and up to 56 B per pixel more to stage host buffers (tpt_temporal_motion: 68 B), 4 B
+ * per face and 96 B per object.  After tpt_history_create and after tpt_history_reset
+ * there is no state: the next tpt_temporal starts over. */
 typedef struct tpt_history tpt_history;
 tpt_status tpt_history_create(tpt_scene* scene, int32_t width, int32_t height, tpt_history** out);
 tpt_status tpt_history_reset(tpt_history* h);
@@ -390,7 +405,7 @@ typedef struct {
  * colour and the luminance moments move a of the way from the weighted history to
  * this frame.  Otherwise it is disoccluded: N = 1 and the output is the input bit
  * for bit.  The new state and `camera` then replace the old.  Only the camera may
- * move between frames, not the scene.
+ * move between frames, not the scene (tpt_temporal_motion follows objects that moved).
  *   guides: normal, depth and material (tpt_render_aov) are required, albedo only with
  *     TPT_TEMPORAL_DEMODULATE; face is ignored.
  *   radiance_in / radiance_out: W*H*3 floats, row 0 = bottom; may be the same pointer.
@@ -410,6 +425,32 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* camera, const float* r
                         const tpt_aov* guides, const tpt_temporal_params* params,
                         float* radiance_out, float* variance_out, float* history_len_out,
                         uint8_t* bgra_out, tpt_temporal_stats* stats);
+
+/* tpt_temporal for a scene whose objects moved (tpt_scene_set_transforms) since the
+ * previous call on this history, by either entry point: both record the transforms of the
+ * scene the history was created from.  The caller has rebuilt that scene and rendered
+ * `guides` from it.  A hit pixel's face id names its object; with M' the object's previous
+ * matrix and M its current one (tpt_motion_matrices), the first hit X is taken to
+ * X' = M' M^-1 X, where that point of the object was in the previous frame, and X' is what is
+ * projected into the previous camera and measured against the previous origin; the normal
+ * test compares the previous frame's normals with normalize((M' M^-1)_lin^-T n).  An object
+ * whose matrices are bit-equal takes tpt_temporal's path bit for bit: with nothing moved the
+ * outputs and the new state are tpt_temporal's.  A hit pixel is disoccluded when its face id
+ * is outside [0, n_faces) or its object is untracked (tpt_motion_matrices).  Misses reproject
+ * their direction as before.  DESIGN.md section 5 "Moving objects" holds the definition.
+ *   guides: as tpt_temporal's, and face is required.
+ *   motion_out: nullable, W*H*2: the reprojected (after the snap) minus the pixel's own
+ *     coordinates, (fx - x, fy - y) in pixels, wherever the reprojection lies in front of the
+ *     previous camera and is finite -- whether or not its taps were accepted, inside the frame
+ *     or not; (0, 0) elsewhere, for untracked pixels and when there is no previous state.
+ * Everything else is tpt_temporal's, the refusals too (and a missing face guide).
+ * Not tracked: shading that changes because something else moved -- a moved object's shadow
+ * or its reflection on a wall that stood still is reprojected as if nothing had happened,
+ * and `alpha` is what bounds that lag.  Lights do not move and meshes do not deform. */
+tpt_status tpt_temporal_motion(tpt_history* h, const tpt_camera* camera, const float* radiance_in,
+                               const tpt_aov* guides, const tpt_temporal_params* params,
+                               float* radiance_out, float* variance_out, float* history_len_out,
+                               float* motion_out, uint8_t* bgra_out, tpt_temporal_stats* stats);
 
 #define TPT_SVGF_DEMODULATE 0x1   /* filter radiance / max(albedo, 1e-3), multiply back afterwards */
 #define TPT_SVGF_DIRECT     0x2   /* A/B: steps 1 and 2 through the direct kernel too instead of the
@@ -512,6 +553,17 @@ tpt_status tpt_debug_step_latency(tpt_scene* scene, uint32_t n, const float* ori
  * not written), or -1.  threads as in tpt_scene_set_build_threads. */
 int32_t tpt_wide_tree_build(int32_t n, const float* leaf_box, const uint32_t* leaf_emit, float* nodes,
                             int32_t cap, int32_t* stack_need, int32_t threads);
+
+/* Host-only: for each of n_objects the way from this frame's world back into the previous
+ * one's, from the objects' local-to-world matrices then (prev16) and now (cur16; 16 floats
+ * each, column-major), computed in double and rounded to float once.  out24, 24 floats per
+ * object: D = M' M^-1 as three rows of four (the translation last), G = (D_lin)^-T as three
+ * rows of three, the flag as an int32, two floats of padding.  Flag 1 (identity): the 16
+ * floats of M' and M are bit-equal; D and G are exact unit matrices.  Flag 2 (untracked): M
+ * is singular, either matrix's last row is not (0, 0, 0, 1), or an entry of D or G is not
+ * finite.  Flag 0 (tracked) otherwise.  Returns the number of untracked objects, or -1 for a
+ * null pointer with n_objects > 0. */
+int32_t tpt_motion_matrices(uint32_t n_objects, const float* prev16, const float* cur16, float* out24);
 
 /* ---- host-side glTF loader (mesh.cu:80-397 semantics) -------------------- */
 typedef struct tpt_gltf tpt_gltf;

@@ -80,6 +80,15 @@ public:
         built_ = true;
         return *this;
     }
+    // New local-to-world matrices for objects first, first + 1, ... (tpt_scene_set_transforms:
+    // 16 floats each, column-major; normal_trans null: the loader's inverse transpose).  The
+    // scene is unbuilt afterwards: build() comes next.
+    DeviceScene& setTransforms(uint32_t first, uint32_t n_objects, const float* vert_trans,
+                               const float* normal_trans = nullptr) {
+        check(tpt_scene_set_transforms(scene_.get(), first, n_objects, vert_trans, normal_trans));
+        built_ = false;
+        return *this;
+    }
     bool built() const { return built_; }
     tpt_scene* handle() const { return scene_.get(); }
     uint32_t nFaces() const { return n_faces_; }
@@ -315,6 +324,21 @@ public:
         tpt_temporal_stats st{};
         check(tpt_temporal(history.handle(), &camera.c, radiance_in, &guides, &params, radiance_out, variance,
                            history_len, framebuffer, &st));
+        return st;
+    }
+
+    // temporal() for a scene whose objects moved since the previous call on `history`
+    // (tpt_temporal_motion: setTransforms + build, then this frame's render and feature
+    // buffers, `face` included).  motion (W*H*2, nullable) receives each pixel's
+    // reprojected minus its own coordinates.
+    tpt_temporal_stats temporalMotion(History& history, const Camera& camera, const float* radiance_in,
+                                      const tpt_aov& guides, float* radiance_out, float* variance = nullptr,
+                                      float* history_len = nullptr, float* motion = nullptr,
+                                      uint8_t* framebuffer = nullptr,
+                                      const tpt_temporal_params& params = defaultTemporal()) {
+        tpt_temporal_stats st{};
+        check(tpt_temporal_motion(history.handle(), &camera.c, radiance_in, &guides, &params, radiance_out, variance,
+                                  history_len, motion, framebuffer, &st));
         return st;
     }
 

@@ -24,7 +24,7 @@ from ._lib import TPTError, build_identity, check, lib
 
 __all__ = ["Camera", "Scene", "DeviceScene", "BVH", "EnvLight", "PathTracer", "Frame", "TPTError",
            "procedural_sky", "version", "device_count", "build_identity", "NODE_DTYPE", "DENOISE_DEFAULTS",
-           "History", "TEMPORAL_DEFAULTS"]
+           "History", "TEMPORAL_DEFAULTS", "motion_matrices"]
 
 # BVHNode (include/bvh.cuh:52-58): parent, info{left,right | fid,placeHolder}, box
 NODE_DTYPE = np.dtype([("parent", "<u4"), ("a", "<i4"), ("b", "<i4"), ("bmin", "<f4", 3), ("bmax", "<f4", 3)])
@@ -216,6 +216,20 @@ class DeviceScene:
         enqueues its RNG initialisation; that render waits for them."""
         check(lib().tpt_scene_build_async(self.handle) if asynchronous else lib().tpt_scene_build(self.handle))
         self.built = True
+        return self
+
+    def set_transforms(self, first: int, vert_trans, normal_trans=None):
+        """New local-to-world matrices for objects first, first + 1, ... (tpt_scene_set_transforms):
+        vert_trans [n, 16] float32, column-major like Scene.vert_trans; normal_trans likewise, or
+        None for the loader's inverse transpose.  The vertices stay on the device; the scene
+        is unbuilt afterwards, so build() comes next.  A progressive accumulation does not
+        survive it."""
+        vt = np.ascontiguousarray(vert_trans, np.float32).reshape(-1, 16)
+        nt = None if normal_trans is None else np.ascontiguousarray(normal_trans, np.float32).reshape(-1, 16)
+        if nt is not None and nt.shape != vt.shape:
+            raise ValueError(f"normal_trans: need {vt.shape[0]} matrices, got {nt.shape[0]}")
+        check(lib().tpt_scene_set_transforms(self.handle, int(first), len(vt), _ptr(vt), _ptr(nt)))
+        self.built = False
         return self
 
     def read_bvh(self):
@@ -415,7 +429,22 @@ def _check_plane(name, buf, width, height):
 
 # Temporal-accumulation defaults of the hosts and the CLI (tpt.hpp defaultTemporal)
 TEMPORAL_DEFAULTS = {"alpha": 0.1, "depth_tol": 0.1, "normal_min": 0.9, "max_history": 32, "demodulate": True}
-_PLANES.update(variance=(1, "float32"), history_len=(1, "float32"))
+_PLANES.update(variance=(1, "float32"), history_len=(1, "float32"), motion_out=(2, "float32"))
+
+
+def motion_matrices(prev, cur):
+    """tpt_motion_matrices: from the objects' local-to-world matrices of the previous frame
+    and of this one ([n, 16] float32, column-major) the records tpt_temporal_motion works
+    with.  Returns (D [n, 3, 4], G [n, 3, 3] float32, flags [n] int32: _lib.MOTION_*, the
+    number of untracked objects)."""
+    p = np.ascontiguousarray(prev, np.float32).reshape(-1, 16)
+    c = np.ascontiguousarray(cur, np.float32).reshape(-1, 16)
+    if p.shape != c.shape:
+        raise ValueError(f"{p.shape[0]} previous matrices, {c.shape[0]} current ones")
+    out = np.zeros((len(p), 24), np.float32)
+    untracked = int(lib().tpt_motion_matrices(len(p), _ptr(p), _ptr(c), _ptr(out)))
+    return (out[:, :12].reshape(-1, 3, 4).copy(), out[:, 12:21].reshape(-1, 3, 3).copy(),
+            out[:, 21].copy().view(np.int32), untracked)
 
 # Defaults of the variance-guided filter of the hosts and the CLI (tpt.hpp defaultSVGF;
 # DESIGN.md section 5 "Post-pass": sigma_lum by the sweep there, not the paper's phi_l = 4, which blurs
@@ -614,7 +643,7 @@ class PathTracer:
                  normal_min: float = TEMPORAL_DEFAULTS["normal_min"],
                  max_history: int = TEMPORAL_DEFAULTS["max_history"],
                  demodulate: bool = TEMPORAL_DEFAULTS["demodulate"], out=None, variance=None, history_len=None,
-                 framebuffer=None, flags: int = 0, stats=None):
+                 framebuffer=None, flags: int = 0, stats=None, motion: bool = False, motion_out=None):
         """Temporal reprojection and accumulation (tpt_temporal, DESIGN.md section 5
         "Post-pass"): this frame's `radiance` [H, W, 3] and its feature buffers
         aov["normal"], aov["depth"], aov["material"] (and aov["albedo"] with
@@ -624,13 +653,20 @@ class PathTracer:
         array); variance / history_len: optional [H, W] float32 buffers for the
         luminance variance and the history length; framebuffer: optional [H, W, 4]
         uint8 as doTrace writes it.  Buffers are numpy arrays or torch CUDA tensors.
-        Returns `out`; stats: a dict that receives kernel_ms and reprojected."""
+        Returns `out`; stats: a dict that receives kernel_ms and reprojected.
+        motion=True (tpt_temporal_motion): objects of the history's scene may have moved
+        since the previous call (DeviceScene.set_transforms + build, then this frame's
+        render and feature buffers); aov["face"] is needed too, and motion_out, an
+        optional [H, W, 2] float32 buffer, receives each pixel's reprojected minus its own
+        coordinates in pixels."""
         W, H = self.m_width, self.m_height
+        if motion_out is not None and not motion:
+            raise ValueError("motion_out needs motion=True")
         if (history.width, history.height) != (W, H):
             raise ValueError(f"the history is {history.width} x {history.height}, the frame {W} x {H}")
         _check_plane("radiance", radiance, W, H)
         g = _lib.Aov()
-        for k in ("albedo", "normal", "depth", "material") if demodulate else ("normal", "depth", "material"):
+        for k in (("albedo",) if demodulate else ()) + ("normal", "depth", "material") + (("face",) if motion else ()):
             buf = aov.get(k)
             if buf is not None:
                 _check_plane(k, buf, W, H)
@@ -638,15 +674,21 @@ class PathTracer:
         if out is None:
             out = np.zeros((H, W, 3), np.float32)
         _check_plane("radiance", out, W, H)
-        for name, buf in (("variance", variance), ("history_len", history_len), ("framebuffer", framebuffer)):
+        for name, buf in (("variance", variance), ("history_len", history_len), ("framebuffer", framebuffer),
+                          ("motion_out", motion_out)):
             if buf is not None:
                 _check_plane(name, buf, W, H)
         p = _lib.TemporalParams(float(alpha), float(depth_tol), float(normal_min), int(max_history),
                                 int(flags) | (_lib.TEMPORAL_DEMODULATE if demodulate else 0))
         st = _lib.TemporalStats()
         cam = camera.to_c()
-        check(lib().tpt_temporal(history.handle, C.byref(cam), _addr(radiance), C.byref(g), C.byref(p), _addr(out),
-                                 _addr(variance), _addr(history_len), _addr(framebuffer), C.byref(st)))
+        if motion:
+            check(lib().tpt_temporal_motion(history.handle, C.byref(cam), _addr(radiance), C.byref(g), C.byref(p),
+                                            _addr(out), _addr(variance), _addr(history_len), _addr(motion_out),
+                                            _addr(framebuffer), C.byref(st)))
+        else:
+            check(lib().tpt_temporal(history.handle, C.byref(cam), _addr(radiance), C.byref(g), C.byref(p), _addr(out),
+                                     _addr(variance), _addr(history_len), _addr(framebuffer), C.byref(st)))
         if stats is not None:
             stats.update(st.as_dict())
         return out

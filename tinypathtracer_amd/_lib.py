@@ -26,6 +26,7 @@ DENOISE_DEMODULATE = 0x1
 DENOISE_DIRECT = 0x2
 TEMPORAL_DEMODULATE = 0x1
 TEMPORAL_TILES = 0x2
+MOTION_TRACKED, MOTION_IDENTITY, MOTION_UNTRACKED = 0, 1, 2   # tpt_motion_matrices' flags
 SVGF_DEMODULATE = 0x1
 SVGF_DIRECT = 0x2
 
@@ -135,6 +136,7 @@ SIGNATURES = [
     ("tpt_scene_build", C.c_int, [C.c_void_p]),
     ("tpt_scene_build_async", C.c_int, [C.c_void_p]),
     ("tpt_scene_set_build_threads", C.c_int, [C.c_void_p, C.c_int32]),
+    ("tpt_scene_set_transforms", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("tpt_scene_destroy", None, [C.c_void_p]),
     ("tpt_env_create", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
     ("tpt_env_destroy", None, [C.c_void_p]),
@@ -157,6 +159,10 @@ SIGNATURES = [
     ("tpt_temporal", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(Aov),
                                C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(TemporalStats)]),
+    ("tpt_temporal_motion", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(Aov),
+                                      C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(TemporalStats)]),
+    ("tpt_motion_matrices", C.c_int32, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_denoise_svgf", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Aov), C.c_void_p,
                                    C.c_void_p, C.POINTER(SvgfParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(SvgfStats)]),

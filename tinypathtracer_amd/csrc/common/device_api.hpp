@@ -333,6 +333,21 @@ constexpr int kTemporalSlots = 256;
 constexpr int kTemporalSlotStride = 16;  // 128 B: one counter per cache line
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t s);
 
+// post.hip: what the motion-aware variant (tpt_temporal_motion) reads and writes on top of
+// TemporalArgs.  A record is tpt_motion_matrices' 24 floats, read as six float4:
+//   0..2 = the rows of D (D[r][0..2], translation), 3..5 = G row-major, then the flag's bits
+//   (kMotionTracked / kMotionIdentity / kMotionUntracked) and two words of padding.
+struct MotionArgs {
+    const int32_t* face;                 // W*H: this frame's face ids (-1 on a miss)
+    const int32_t* face_object;          // n_faces: the object whose lut interval holds the face
+    const float4* records;               // 6 float4 per object
+    float* motion_out;                   // nullable, W*H*2
+    int32_t n_faces;
+};
+constexpr int kMotionRecordFloats = 24;
+constexpr int32_t kMotionTracked = 0, kMotionIdentity = 1, kMotionUntracked = 2;
+hipError_t launch_temporal_motion(const TemporalArgs& a, const MotionArgs& mo, hipStream_t s);
+
 // post.hip: the variance-guided a-trous filter (tpt_denoise_svgf; DESIGN.md section 5
 // "Post-pass").  tpt_denoise's planes, the colour plane's fourth component carrying the
 // variance: colour = (r, g, b, v), guide = (n.xyz, z).

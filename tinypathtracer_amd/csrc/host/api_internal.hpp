@@ -321,6 +321,10 @@ struct tpt_scene {
     DevBuf<float4> mtl;
     DevBuf<tpt::DevLight> lights;
     DevBuf<uint32_t> jumps;
+    // host copies: every object's local-to-world matrix as the device holds it (tpt_scene_create,
+    // tpt_scene_set_transforms) and the objects' first faces, for the histories' motion records
+    std::vector<float> h_vert_trans;
+    std::vector<int32_t> h_lut_begin;
     // world + BVH
     DevBuf<float> wverts, wnorms, leaf_box, node_box;
     DevBuf<unsigned long long> keys, keys_sorted, bfs_keys, bfs_keys_sorted;
@@ -424,8 +428,9 @@ struct tpt_scene {
     }
 };
 
-// tpt_temporal's state (post.hip k_temporal): two sets of three float4 planes that
-// ping-pong, the previous call's camera, device staging of host buffers.
+// tpt_temporal's and tpt_temporal_motion's state (post.hip k_temporal, k_temporal_motion): two
+// sets of three float4 planes that ping-pong, the previous call's camera and object
+// transforms, device staging of host buffers.
 struct tpt_history {
     tpt_scene* scene = nullptr;             // the stream; outlives the history's last tpt_temporal
     int device = 0;
@@ -440,6 +445,15 @@ struct tpt_history {
     DevBuf<uint8_t> st_bgra;
     DevBuf<unsigned long long> count;       // the reprojected-pixel counters (TemporalArgs::reprojected)
     HostPinned<unsigned long long> h_count;
+    // tpt_temporal_motion: the scene's vert_trans as they were at the previous call (empty: no
+    // state), the face -> object table (built once from the lut), the objects' records
+    // (tpt_motion_matrices) on both sides, device staging of the face guide and of motion_out
+    std::vector<float> prev_vert_trans;
+    DevBuf<int32_t> face_object;
+    DevBuf<float> records;
+    HostPinned<float> h_records;
+    DevBuf<int32_t> st_face;
+    DevBuf<float> st_motion;
     hipEvent_t ev[2] = {nullptr, nullptr};
 
     ~tpt_history() {

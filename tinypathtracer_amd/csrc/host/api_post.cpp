@@ -1,5 +1,5 @@
 // api_post.cpp -- the post-pass entry points of the C-ABI (post.hip): tpt_render_aov,
-// tpt_denoise, tpt_history_*, tpt_temporal and tpt_denoise_svgf.  Each takes its buffers from either
+// tpt_denoise, tpt_history_*, tpt_temporal, tpt_temporal_motion and tpt_denoise_svgf.  Each takes its buffers from either
 // side: host buffers go through the device staging the scene / history keeps
 // (api_internal.hpp Staging).
 #include <cmath>
@@ -181,6 +181,17 @@ tpt_status tpt_history_create(tpt_scene* s, int32_t W, int32_t H, tpt_history** 
         for (auto& plane : set) HIP_OR_FAIL(plane.alloc(npix));
     HIP_OR_FAIL(h->count.alloc(kCountWords));
     HIP_OR_FAIL(h->h_count.alloc(kCountWords));
+    {   // tpt_temporal_motion: which object each face belongs to, and room for the objects' records
+        std::vector<int32_t> fo((size_t)s->n_faces);
+        for (int32_t o = 0; o < s->n_objects; ++o) {
+            const int32_t end = o + 1 < s->n_objects ? s->h_lut_begin[o + 1] : s->n_faces;
+            for (int32_t f = std::max(s->h_lut_begin[o], 0); f < std::min(end, s->n_faces); ++f) fo[f] = o;
+        }
+        HIP_OR_FAIL(h->face_object.upload(fo.data(), fo.size(), s->stream));
+        HIP_OR_FAIL(hipStreamSynchronize(s->stream));   // (fo is freed below)
+        HIP_OR_FAIL(h->records.alloc((size_t)s->n_objects * tpt::kMotionRecordFloats));
+        HIP_OR_FAIL(h->h_records.alloc((size_t)s->n_objects * tpt::kMotionRecordFloats));
+    }
     for (auto& e : h->ev) HIP_OR_FAIL(hipEventCreate(&e));
     *out = h.release();
     return TPT_OK;
@@ -189,14 +200,17 @@ tpt_status tpt_history_create(tpt_scene* s, int32_t W, int32_t H, tpt_history** 
 tpt_status tpt_history_reset(tpt_history* h) {
     if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
     h->valid = false;
+    h->prev_vert_trans.clear();
     return TPT_OK;
 }
 
 void tpt_history_destroy(tpt_history* h) { delete h; }
 
-tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radiance_in, const tpt_aov* guides,
-                        const tpt_temporal_params* p, float* radiance_out, float* variance_out,
-                        float* history_len_out, uint8_t* bgra_out, tpt_temporal_stats* stats) {
+// tpt_temporal (motion false: face guide and motion_out unused) and tpt_temporal_motion
+static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const float* radiance_in,
+                                const tpt_aov* guides, const tpt_temporal_params* p, float* radiance_out,
+                                float* variance_out, float* history_len_out, float* motion_out, uint8_t* bgra_out,
+                                tpt_temporal_stats* stats, bool motion) {
     if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
     if (!cam) return fail(TPT_ERR_INVALID_ARG, "null camera");
     if (!radiance_in) return fail(TPT_ERR_INVALID_ARG, "null radiance_in");
@@ -206,6 +220,8 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radi
     const bool demod = (p->flags & TPT_TEMPORAL_DEMODULATE) != 0;
     if (!guides->normal || !guides->depth || !guides->material)
         return fail(TPT_ERR_INVALID_ARG, "temporal accumulation needs the normal, depth and material guides");
+    if (motion && !guides->face)
+        return fail(TPT_ERR_INVALID_ARG, "motion-aware accumulation needs the face guides too");
     if (demod && !guides->albedo)
         return fail(TPT_ERR_INVALID_ARG, "TPT_TEMPORAL_DEMODULATE needs the albedo guides");
     if (!(p->alpha > 0.0f && p->alpha <= 1.0f)) return fail(TPT_ERR_INVALID_ARG, "alpha must be in (0, 1]");
@@ -246,6 +262,21 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radi
     HIP_OR_FAIL(sg.in(h->st_f3[1], guides->normal, 3 * npix, &a.normal));
     HIP_OR_FAIL(sg.in(h->st_depth, guides->depth, npix, &a.depth));
     HIP_OR_FAIL(sg.in(h->st_mtl, guides->material, npix, &a.material));
+    tpt::MotionArgs mo{};
+    if (motion) {
+        // every object's way back into the previous frame's world; without a previous frame the
+        // kernel reads none of it
+        const size_t nrec = (size_t)s->n_objects * tpt::kMotionRecordFloats;
+        const float* now = s->h_vert_trans.data();
+        (void)tpt_motion_matrices((uint32_t)s->n_objects, h->valid ? h->prev_vert_trans.data() : now, now,
+                                  h->h_records.p);
+        HIP_OR_FAIL(hipMemcpyAsync(h->records.p, h->h_records.p, nrec * sizeof(float), hipMemcpyHostToDevice, st));
+        mo.records = reinterpret_cast<const float4*>(h->records.p);
+        mo.face_object = h->face_object.p;
+        mo.n_faces = s->n_faces;
+        HIP_OR_FAIL(sg.in(h->st_face, guides->face, npix, &mo.face));
+        HIP_OR_FAIL(sg.out(h->st_motion, motion_out, 2 * npix, &mo.motion_out));
+    }
     // radiance in and out share st_rad: a lane reads its pixel before it writes it
     HIP_OR_FAIL(sg.out(h->st_rad, radiance_out, 3 * npix, &a.radiance_out));
     HIP_OR_FAIL(sg.out(h->st_var, variance_out, npix, &a.variance_out));
@@ -260,7 +291,7 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radi
     a.reprojected = h->count.p;
     HIP_OR_FAIL(hipMemsetAsync(h->count.p, 0, kCountWords * sizeof(unsigned long long), st));
     HIP_OR_FAIL(hipEventRecord(h->ev[0], st));
-    HIP_OR_FAIL(tpt::launch_temporal(a, st));
+    HIP_OR_FAIL(motion ? tpt::launch_temporal_motion(a, mo, st) : tpt::launch_temporal(a, st));
     HIP_OR_FAIL(hipEventRecord(h->ev[1], st));
     HIP_OR_FAIL(sg.finish());
     HIP_OR_FAIL(hipMemcpyAsync(h->h_count.p, h->count.p, kCountWords * sizeof(unsigned long long),
@@ -268,7 +299,8 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radi
     HIP_OR_FAIL(hipStreamSynchronize(st));
     unsigned long long found = 0;
     for (int k = 0; k < tpt::kTemporalSlots; ++k) found += h->h_count.p[(size_t)k * tpt::kTemporalSlotStride];
-    // the new state and this camera replace the old
+    // the new state, this camera and the scene's object transforms replace the old
+    h->prev_vert_trans = s->h_vert_trans;
     h->cur = to;
     h->valid = true;
     if (!invert4(cam->c2w, h->prev_inv)) h->valid = false;   // a singular c2w: nothing can be reprojected into it
@@ -280,6 +312,21 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radi
         stats->reprojected = found;
     }
     return TPT_OK;
+}
+
+tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radiance_in, const tpt_aov* guides,
+                        const tpt_temporal_params* p, float* radiance_out, float* variance_out,
+                        float* history_len_out, uint8_t* bgra_out, tpt_temporal_stats* stats) {
+    return temporal_pass(h, cam, radiance_in, guides, p, radiance_out, variance_out, history_len_out, nullptr, bgra_out,
+                         stats, false);
+}
+
+tpt_status tpt_temporal_motion(tpt_history* h, const tpt_camera* cam, const float* radiance_in, const tpt_aov* guides,
+                               const tpt_temporal_params* p, float* radiance_out, float* variance_out,
+                               float* history_len_out, float* motion_out, uint8_t* bgra_out,
+                               tpt_temporal_stats* stats) {
+    return temporal_pass(h, cam, radiance_in, guides, p, radiance_out, variance_out, history_len_out, motion_out,
+                         bgra_out, stats, true);
 }
 
 // The variance-guided a-trous filter (post.hip k_svgf_*; DESIGN.md section 5

@@ -620,7 +620,37 @@ tpt_status tpt_scene_create(const tpt_scene_desc* d_in, int device, tpt_scene** 
     if (e != hipSuccess)
         return cleanup(fail(e == hipErrorOutOfMemory ? TPT_ERR_OOM : TPT_ERR_HIP,
                             std::string("scene upload: ") + hipGetErrorString(e)));
+    s->h_vert_trans.assign(d->vert_trans, d->vert_trans + 16 * (size_t)d->n_objects);
+    s->h_lut_begin.resize(d->n_objects);
+    for (uint32_t i = 0; i < d->n_objects; ++i) s->h_lut_begin[i] = d->lut[i].begin;
     *out = s;
+    return TPT_OK;
+}
+
+// New local-to-world matrices for some objects.  The vertices stay on the device: the next
+// build transforms them again (scene_build starts from vert_trans / normal_trans every time).
+tpt_status tpt_scene_set_transforms(tpt_scene* s, uint32_t first, uint32_t n, const float* vert_trans,
+                                    const float* normal_trans) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (!vert_trans) return fail(TPT_ERR_INVALID_ARG, "null vert_trans");
+    if (n == 0) return fail(TPT_ERR_INVALID_ARG, "n_objects must be > 0");
+    if ((uint64_t)first + (uint64_t)n > (uint64_t)s->n_objects)
+        return fail(TPT_ERR_INVALID_ARG, "object range past the scene's object count");
+    std::vector<float> nt;
+    if (!normal_trans) {
+        nt.resize(16 * (size_t)n);
+        for (uint32_t i = 0; i < n; ++i) tpt::normal_to_world16(vert_trans + 16 * (size_t)i, nt.data() + 16 * (size_t)i);
+        normal_trans = nt.data();
+    }
+    if (s->trees) s->trees->join();   // a pending asynchronous build is superseded, as by the next build
+    s->pending = false;
+    s->built = false;
+    DeviceGuard g(s->device);
+    const size_t off = 16 * (size_t)first, bytes = 16 * (size_t)n * sizeof(float);
+    HIP_OR_FAIL(hipMemcpyAsync(s->vert_trans.p + off, vert_trans, bytes, hipMemcpyHostToDevice, s->stream));
+    HIP_OR_FAIL(hipMemcpyAsync(s->normal_trans.p + off, normal_trans, bytes, hipMemcpyHostToDevice, s->stream));
+    HIP_OR_FAIL(hipStreamSynchronize(s->stream));   // (the caller's matrices and nt are only read during the call)
+    std::memcpy(s->h_vert_trans.data() + off, vert_trans, bytes);
     return TPT_OK;
 }
 

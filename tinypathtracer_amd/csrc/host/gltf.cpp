@@ -245,6 +245,13 @@ struct MeshData {
 
 }  // namespace
 
+void normal_to_world16(const float* l2w, float* out) {
+    M4 m{};
+    for (int c = 0; c < 4; ++c)
+        for (int r = 0; r < 4; ++r) m[c][r] = l2w[4 * c + r];
+    flatten(normal_to_world(m), out);
+}
+
 // Accessor view (tightly packed; the reference ignores byteStride, mesh.cu:165-222)
 static const uint8_t* accessor_ptr(const json::Value& model, const std::vector<std::vector<uint8_t>>& bufs,
                                    long long acc_idx, long long* count, long long* ctype, int* ncomp) {

@@ -43,6 +43,9 @@ struct HostScene {
 };
 
 void load_gltf(const std::string& path, HostScene& hs);
+// The loader's normal_to_world of a local-to-world matrix (16 floats, column-major), with its
+// float operations: what tpt_scene_set_transforms computes when it is given no normal_trans.
+void normal_to_world16(const float* l2w, float* out);
 
 // Env-map image (JPEG / binary PPM) decoded as FreeImage + Texture would hand it
 // to the GPU: RGBA8, row 0 = bottom, RGB order, alpha 255 (image.cpp).

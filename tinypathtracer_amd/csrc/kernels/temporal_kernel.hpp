@@ -1,0 +1,221 @@
+// temporal_kernel.hpp -- the text of k_temporal, included by post.hip once as it is and once
+// with TPT_TEMPORAL_MOTION as k_temporal_motion.  No include guard: it is meant to be read twice.
+
+// One lane per pixel, one launch per frame.  The lane reads its pixel of the caller's
+// planes (3-float planes directly: a pack step would write and read them once more),
+// gathers four taps of the previous state (three 16-B loads each, all issued before
+// the first is used) and writes its pixel of the new state.  TILES = false: a wave is a 64-pixel row segment (block (64, 4)),
+// so its own-pixel accesses are 1 KiB contiguous per float4 plane and its taps, which
+// neighbouring lanes reproject to neighbouring addresses, nearly so; TILES = true:
+// 16x16 tiles, each wave an 8x8 sub-tile as k_aov.  No LDS, no floating-point atomics.
+//
+// TPT_TEMPORAL_MOTION (k_temporal_motion; DESIGN.md section 5 "Moving objects"): a hit pixel
+// also reads its face id, the face's object id and the object's record (MotionArgs), moves
+// its world position by the object's D into the previous frame's world and turns its normal
+// by G before the rules are applied.  Lanes of a wave mostly share an object, so the record's
+// six 16-B loads are a broadcast from L2.  An object that did not move (kMotionIdentity) skips
+// both products under its flag instead of multiplying by the unit matrix: 1 x + 0 y + 0 z + 0
+// turns -0 into +0 and an infinite coordinate into NaN, while the skipped path leaves X and n
+// as they are for every input, so that case is k_temporal's bit for bit.
+template <bool TILES>
+#if TPT_TEMPORAL_MOTION
+__global__ __launch_bounds__(256) void k_temporal_motion(TemporalArgs a, MotionArgs mo) {
+#else
+__global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
+#endif
+    int x, y, tid;
+    if (TILES) {
+        tid = (int)threadIdx.x;
+        const int lane = tid & 63, wave = tid >> 6;
+        x = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+        y = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    } else {
+        tid = (int)threadIdx.y * 64 + (int)threadIdx.x;
+        x = (int)blockIdx.x * 64 + (int)threadIdx.x;
+        y = (int)blockIdx.y * 4 + (int)threadIdx.y;
+    }
+    bool reproj = false;
+    if (x < a.width && y < a.height) {
+        const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
+        // what the reprojection needs first, so that the taps' loads start early
+        const float z = a.depth[p];
+        const int m = a.material[p];
+#if TPT_TEMPORAL_MOTION
+        const int face = mo.face[p];
+        float mvx = 0.0f, mvy = 0.0f;                      // where the pixel came from, minus where it is
+#endif
+        const V3 n = v3(a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2]);
+        const V3 in = v3(a.radiance_in[3 * p], a.radiance_in[3 * p + 1], a.radiance_in[3 * p + 2]);
+        V3 alb = v3(1.0f, 1.0f, 1.0f);
+        if (a.demodulate) alb = v3(a.albedo[3 * p], a.albedo[3 * p + 1], a.albedo[3 * p + 2]);
+        const bool hit = m >= 0;
+        float4 hc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // history: colour, N
+        float hm1 = 0.0f, hm2 = 0.0f;
+        if (a.has_prev) {
+            // the pixel-centre ray of the current camera: k_aov's text
+            float lx = 0.5f * 1.0f, lyf = 0.5f * 1.0f;
+            lx = lx + (float)x;
+            lyf = lyf + (float)y;
+            lx = lx * a.inv_w;
+            lyf = lyf * a.inv_h;
+            lx = lx * a.sensor_w;
+            lyf = lyf * a.sensor_h;
+            float r4[4];
+            mat4_vec4(a.c2w, lx - a.half_sw, lyf - a.half_sh, 0.0f - 1.0f, 0.0f, r4);
+            const V3 rd = normalize(v3(r4[0], r4[1], r4[2]));
+            const V3 ro = v3(a.origin[0], a.origin[1], a.origin[2]);
+            // a hit reprojects its world position, a miss its direction (a point at infinity)
+#if TPT_TEMPORAL_MOTION
+            V3 X = hit ? ro + (z * rd) : rd;
+            V3 ne = n;                                     // the normal as the previous frame held it
+            bool tracked = true;
+            if (hit) {
+                tracked = (unsigned)face < (unsigned)mo.n_faces;   // compared before it indexes anything
+                if (tracked) {
+                    const float4* rec = mo.records + 6 * (size_t)mo.face_object[face];
+                    const float4 d0 = rec[0], d1 = rec[1], d2 = rec[2], g0 = rec[3], g1 = rec[4], g2 = rec[5];
+                    const int flag = __float_as_int(g2.y);
+                    tracked = flag != kMotionUntracked;
+                    if (flag == kMotionTracked) {
+                        X = v3(((d0.x * X.x + d0.y * X.y) + d0.z * X.z) + d0.w,
+                               ((d1.x * X.x + d1.y * X.y) + d1.z * X.z) + d1.w,
+                               ((d2.x * X.x + d2.y * X.y) + d2.z * X.z) + d2.w);
+                        const V3 gn = v3((g0.x * n.x + g0.y * n.y) + g0.z * n.z, (g0.w * n.x + g1.x * n.y) + g1.y * n.z,
+                                         (g1.z * n.x + g1.w * n.y) + g2.x * n.z);
+                        // a square root and divisions, not frsqrt: its 2e-3 would decide the normal rule
+                        const float len = fsqrt(norm2(gn));
+                        ne = v3(gn.x / len, gn.y / len, gn.z / len);
+                    }
+                }
+            }
+#else
+            const V3 X = hit ? ro + (z * rd) : rd;
+#endif
+            float loc[4];
+            mat4_vec4(a.prev_inv, X.x, X.y, X.z, hit ? 1.0f : 0.0f, loc);
+            float dist = 0.0f;
+            if (hit) dist = fsqrt(norm2(X - v3(a.prev_origin[0], a.prev_origin[1], a.prev_origin[2])));
+#if TPT_TEMPORAL_MOTION
+            if (loc[2] < 0.0f && tracked) {
+#else
+            if (loc[2] < 0.0f) {
+#endif
+                const float s = -1.0f / loc[2];
+                float fx = (loc[0] * s + a.prev_half_sw) / a.prev_sensor_w * (float)a.width - 0.5f;
+                float fy = (loc[1] * s + a.prev_half_sh) / a.prev_sensor_h * (float)a.height - 0.5f;
+                const float rx = rintf(fx), ry = rintf(fy);
+                if (fabsf(fx - rx) < kSnap) fx = rx;
+                if (fabsf(fy - ry) < kSnap) fy = ry;
+#if TPT_TEMPORAL_MOTION
+                if (__builtin_isfinite(fx) && __builtin_isfinite(fy)) {
+                    mvx = fx - (float)x;
+                    mvy = fy - (float)y;
+                }
+#endif
+                // some tap of positive weight inside the frame (false for NaN and out-of-range values too)
+                if (fx > -1.0f && fx < (float)a.width && fy > -1.0f && fy < (float)a.height) {
+                    const float x0f = floorf(fx), y0f = floorf(fy);
+                    const float tx = fx - x0f, ty = fy - y0f;
+                    const int x0 = (int)x0f, y0 = (int)y0f;
+                    // The four taps' weights and addresses first, then all twelve loads, then the
+                    // tests: the loads are in flight together (a chain of dependent, conditional
+                    // loads measured 0.40 ms at 1080p, latency-bound).  A tap of weight 0 or outside
+                    // the frame is never read: its loads go to the lane's own pixel instead.
+                    float w[4];
+                    size_t q[4];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const int qx = x0 + (t & 1), qy = y0 + (t >> 1);
+                        w[t] = ((t & 1) ? tx : 1.0f - tx) * ((t >> 1) ? ty : 1.0f - ty);
+                        if (!(w[t] > 0.0f) || qx < 0 || qx >= a.width || qy < 0 || qy >= a.height) w[t] = 0.0f;
+                        q[t] = w[t] > 0.0f ? (size_t)qy * (size_t)a.width + (size_t)qx : p;
+                    }
+                    float4 s0[4], s1[4], s2[4];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        s2[t] = a.prev[2][q[t]];
+                        s1[t] = a.prev[1][q[t]];
+                        s0[t] = a.prev[0][q[t]];
+                    }
+                    float wsum = 0.0f;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        bool ok = w[t] > 0.0f && __float_as_int(s2[t].z) == m;
+                        if (hit) {
+                            const float4 g = s1[t];
+                            ok = ok && fabsf(g.w - dist) <= a.depth_tol * dist &&
+#if TPT_TEMPORAL_MOTION
+                                 (g.x * ne.x + g.y * ne.y) + g.z * ne.z >= a.normal_min;
+#else
+                                 (g.x * n.x + g.y * n.y) + g.z * n.z >= a.normal_min;
+#endif
+                        }
+                        if (!ok) continue;
+                        wsum += w[t];
+                        hc.x += w[t] * s0[t].x;
+                        hc.y += w[t] * s0[t].y;
+                        hc.z += w[t] * s0[t].z;
+                        hc.w += w[t] * s0[t].w;
+                        hm1 += w[t] * s2[t].x;
+                        hm2 += w[t] * s2[t].y;
+                    }
+                    if (wsum >= kMinWsum) {
+                        reproj = true;
+                        // divisions, not a reciprocal: taps of one history length N' give N' exactly
+                        hc = make_float4(hc.x / wsum, hc.y / wsum, hc.z / wsum, hc.w / wsum);
+                        hm1 = hm1 / wsum;
+                        hm2 = hm2 / wsum;
+                    }
+                }
+            }
+        }
+        V3 c = in;
+        if (a.demodulate) {
+            alb = v3(fmaxf(alb.x, kAlbedoFloor), fmaxf(alb.y, kAlbedoFloor), fmaxf(alb.z, kAlbedoFloor));
+            c = v3(in.x / alb.x, in.y / alb.y, in.z / alb.z);
+        }
+        const float L = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+        // disoccluded: selected, not blended -- the colour and the output are the input bit for bit
+        float N = 1.0f, m1 = L, m2 = L * L;
+        V3 C = c, out = in;
+        if (reproj) {
+            N = fminf(hc.w + 1.0f, a.max_history);
+            const float k = fmaxf(a.alpha, 1.0f / N);
+            C = v3(hc.x + k * (c.x - hc.x), hc.y + k * (c.y - hc.y), hc.z + k * (c.z - hc.z));
+            m1 = hm1 + k * (m1 - hm1);
+            m2 = hm2 + k * (m2 - hm2);
+            out = a.demodulate ? C * alb : C;
+        }
+        a.next[0][p] = make_float4(C.x, C.y, C.z, N);
+        a.next[1][p] = make_float4(n.x, n.y, n.z, z);
+        a.next[2][p] = make_float4(m1, m2, __int_as_float(m), 0.0f);
+        if (a.radiance_out) {
+            a.radiance_out[3 * p] = out.x;
+            a.radiance_out[3 * p + 1] = out.y;
+            a.radiance_out[3 * p + 2] = out.z;
+        }
+        if (a.variance_out) a.variance_out[p] = fmaxf(m2 - m1 * m1, 0.0f);
+        if (a.history_out) a.history_out[p] = N;
+#if TPT_TEMPORAL_MOTION
+        if (mo.motion_out) {
+            mo.motion_out[2 * p] = mvx;
+            mo.motion_out[2 * p + 1] = mvy;
+        }
+#endif
+        if (a.bgra) {   // k_dn_resolve's conventions
+            uint8_t* px = a.bgra + 4 * (((size_t)a.height - (size_t)y - 1) * (size_t)a.width + (size_t)x);
+            px[0] = to_uchar(out.z);
+            px[1] = to_uchar(out.y);
+            px[2] = to_uchar(out.x);
+        }
+    }
+    // the statistic: one integer atomic per wave, spread over kTemporalSlots counters a cache
+    // line apart (the host adds them up): every wave of a 1080p frame adding to one address
+    // would queue 32,400 atomics on it
+    const unsigned long long found = __ballot(reproj);
+    if ((tid & 63) == 0 && found) {
+        const unsigned slot = ((unsigned)blockIdx.y * gridDim.x + (unsigned)blockIdx.x) % (unsigned)kTemporalSlots;
+        atomicAdd(a.reprojected + (size_t)slot * kTemporalSlotStride, (unsigned long long)__popcll(found));
+    }
+}
+

@@ -7,6 +7,7 @@
 //              [--seed S] [--env equirect.jpg|.ppm|--sky] [--out prefix] [--device i]
 //              [--frames F [--progressive]] [--aov] [--denoise [iterations]]
 //              [--temporal] [--yaw DEG] [--svgf [iterations]]
+//              [--move OBJ DX DY DZ] [--spin OBJ DEG]
 // --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
 // <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
 // a-trous filter of the written frame (tpt_denoise, the hosts' defaults; with
@@ -18,6 +19,13 @@
 // and history length; without it of the written frame, on the spatial variance
 // estimate alone.  --denoise and --svgf may be combined: both files are written.
 // --yaw DEG turns the camera about its own origin and up axis by DEG per frame.
+// --move OBJ DX DY DZ translates object OBJ (its index in the scene's object order: the
+// mesh nodes of the glTF file in node order) by (DX, DY, DZ) world units per frame; --spin
+// OBJ DEG turns it by DEG per frame about world +y through the centre of its frame-0 world
+// bounding box (with both, it turns first).  Either needs --frames and --temporal: every
+// frame sets the transforms (tpt_scene_set_transforms), rebuilds, renders, and goes
+// through tpt_temporal_motion, which follows the moved objects.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -75,7 +83,8 @@ void write_pfm(const std::string& path, const std::vector<float>& v, int W, int 
 const char* kUsage =
     "usage: %s scene.gltf [--width W] [--height H] [--spp N] [--depth D] [--seed S] "
     "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]] "
-    "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]]\n";
+    "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]] "
+    "[--move OBJ DX DY DZ] [--spin OBJ DEG]\n";
 
 // The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
 tpt::Camera yawed(const tpt::Camera& base, double deg) {
@@ -89,6 +98,52 @@ tpt::Camera yawed(const tpt::Camera& base, double deg) {
     return cam;
 }
 
+// --move / --spin: what one object does per frame
+struct ObjectMotion {
+    uint32_t object = 0;
+    double move[3] = {0.0, 0.0, 0.0};
+    double spin = 0.0;          // degrees about world +y
+    double centre[3] = {0.0, 0.0, 0.0};   // of the frame-0 world bounding box
+};
+
+// The centre of object o's world bounding box under its matrix in the desc
+void world_box_centre(const tpt_scene_desc& d, uint32_t o, double* centre) {
+    const uint32_t begin = (uint32_t)d.lut[o].begin, end = o + 1 < d.n_objects ? (uint32_t)d.lut[o + 1].begin : d.n_faces;
+    const float* m = d.vert_trans + 16 * (size_t)o;
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    for (uint32_t i = 3 * begin; i < 3 * end; ++i) {
+        const float* v = d.vertices + 3 * (size_t)d.indices[i];
+        for (int r = 0; r < 3; ++r) {
+            const double w = (double)m[r] * v[0] + (double)m[4 + r] * v[1] + (double)m[8 + r] * v[2] + (double)m[12 + r];
+            lo[r] = std::min(lo[r], w);
+            hi[r] = std::max(hi[r], w);
+        }
+    }
+    for (int r = 0; r < 3; ++r) centre[r] = 0.5 * (lo[r] + hi[r]);
+}
+
+// Frame `frame`'s matrix of a moving object: T(frame * move) T(c) R_y(frame * spin) T(-c) M0,
+// in double, rounded to float once; frame 0 is M0 itself
+void moved_matrix(const ObjectMotion& om, const float* m0, int frame, float* out) {
+    if (frame == 0) {
+        std::memcpy(out, m0, 16 * sizeof(float));
+        return;
+    }
+    const double t = om.spin * frame * M_PI / 180.0, c = std::cos(t), s = std::sin(t);
+    const double rot[3][3] = {{c, 0.0, s}, {0.0, 1.0, 0.0}, {-s, 0.0, c}};
+    for (int col = 0; col < 4; ++col) {
+        double v[3] = {m0[4 * col], m0[4 * col + 1], m0[4 * col + 2]};
+        if (col == 3)
+            for (int r = 0; r < 3; ++r) v[r] -= om.centre[r];
+        for (int r = 0; r < 3; ++r) {
+            double w = rot[r][0] * v[0] + rot[r][1] * v[1] + rot[r][2] * v[2];
+            if (col == 3) w += om.centre[r] + om.move[r] * frame;
+            out[4 * col + r] = (float)w;
+        }
+        out[4 * col + 3] = m0[4 * col + 3];
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -100,6 +155,14 @@ int main(int argc, char** argv) {
     int W = 1920, H = 1080, spp = 64, depth = 8, device = 0, frames = 1;
     bool progressive = false, aov = false, denoise = false, temporal = false, svgf = false;
     double yaw = 0.0;
+    std::vector<ObjectMotion> motions;   // --move / --spin, one entry per object named
+    auto motion_of = [&](uint32_t object) -> ObjectMotion& {
+        for (auto& om : motions)
+            if (om.object == object) return om;
+        motions.emplace_back();
+        motions.back().object = object;
+        return motions.back();
+    };
     int dn_iterations = tpt::defaultDenoise().iterations;
     int sv_iterations = tpt::defaultSVGF().iterations;
     uint64_t seed = 0;
@@ -124,6 +187,14 @@ int main(int argc, char** argv) {
         else if (a == "--aov") aov = true;
         else if (a == "--temporal") temporal = true;
         else if (a == "--yaw") yaw = std::stod(next());
+        else if (a == "--move") {
+            ObjectMotion& om = motion_of((uint32_t)std::stoul(next()));
+            for (double& v : om.move) v = std::stod(next());
+        }
+        else if (a == "--spin") {
+            ObjectMotion& om = motion_of((uint32_t)std::stoul(next()));
+            om.spin = std::stod(next());
+        }
         else if (a == "--denoise") {
             denoise = true;   // an optional iteration count follows
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn_iterations = std::stoi(argv[++i]);
@@ -133,6 +204,14 @@ int main(int argc, char** argv) {
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') sv_iterations = std::stoi(argv[++i]);
         }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
+    }
+    if (!motions.empty() && progressive) {   // the accumulated samples belong to the scene as it was
+        std::fprintf(stderr, "--move and --spin cannot be combined with --progressive\n");
+        return 2;
+    }
+    if (!motions.empty() && (!temporal || frames < 2)) {
+        std::fprintf(stderr, "--move and --spin need --frames F (F > 1) and --temporal\n");
+        return 2;
     }
     if (temporal && progressive) {   // progressive is already the exact accumulation of an unmoving camera
         std::fprintf(stderr, "--temporal cannot be combined with --progressive\n");
@@ -151,6 +230,10 @@ int main(int argc, char** argv) {
         tpt::Scene scene(scene_file, "gltf");
         tpt::DeviceScene d = scene.copySceneToDevice(device);
         d.build();
+        for (auto& om : motions) {
+            if (om.object >= scene.desc().n_objects) throw std::runtime_error("--move / --spin: no such object");
+            world_box_centre(scene.desc(), om.object, om.centre);
+        }
         tpt::Frame f;
         f.width = W;
         f.height = H;
@@ -169,9 +252,19 @@ int main(int argc, char** argv) {
             const uint64_t base = seed ? seed : (uint64_t)std::time(nullptr);
             for (int i = 0; i < frames; ++i) {
                 cam = yawed(scene.m_camera, yaw * i);
+                for (const auto& om : motions) {   // (frame 0 keeps the loaded matrices)
+                    float m[16];
+                    moved_matrix(om, scene.desc().vert_trans + 16 * (size_t)om.object, i, m);
+                    if (i > 0) d.setTransforms(om.object, 1, m);
+                }
+                if (!d.built()) d.build();
                 f.stats = pt.doTrace(d, cam, f.bgra.data(), spp, base + (uint64_t)i, depth, f.radiance.data());
                 g = pt.renderAOV(d, cam);
-                pt.temporal(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(), fb.data());
+                if (motions.empty())
+                    pt.temporal(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(), fb.data());
+                else
+                    pt.temporalMotion(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(),
+                                      nullptr, fb.data());
             }
             write_pfm(out + "_temporal.pfm", acc, W, H, 3);
             write_ppm(out + "_temporal.ppm", fb, W, H);
