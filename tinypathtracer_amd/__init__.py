@@ -107,6 +107,43 @@ class Scene:
             lib().tpt_gltf_free(h)
         self.filename = filename
 
+    @classmethod
+    def from_arrays(cls, indices, vertices, normals, lut, vert_trans, normal_trans, materials=(), lights=(),
+                    camera: "Camera | None" = None) -> "Scene":
+        """A scene from packed arrays in the layouts the loader produces (the
+        attributes above): indices uint32 [3F], vertices / normals float32 [V, 3],
+        lut int32 [O, 2] (first face, material id), vert_trans / normal_trans
+        float32 [O, 16] column-major, materials float32 [M, 15].  lights: _lib.Light
+        structs, or dicts with their field names.  camera None: Camera() of the
+        reference (identity, vfov 60, aspect 1.77778)."""
+        s = cls.__new__(cls)
+        s.indices = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        s.vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        s.normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        s.lut = np.ascontiguousarray(lut, np.int32).reshape(-1, 2)
+        s.vert_trans = np.ascontiguousarray(vert_trans, np.float32).reshape(-1, 16)
+        s.normal_trans = np.ascontiguousarray(normal_trans, np.float32).reshape(-1, 16)
+        s.materials = np.ascontiguousarray(materials, np.float32).reshape(-1, 15)
+        if len(s.indices) % 3 or len(s.normals) != len(s.vertices) or len(s.vert_trans) != len(s.lut) or \
+                len(s.normal_trans) != len(s.lut):
+            raise ValueError("from_arrays: 3 indices per face, a normal per vertex, two matrices per object")
+        if len(s.indices) and int(s.indices.max()) >= len(s.vertices):
+            raise ValueError("from_arrays: an index past the vertices")
+        s.lights = []
+        for L in lights:
+            if not isinstance(L, _lib.Light):
+                d, L = L, _lib.Light()
+                L.type, L.intensity = int(d["type"]), float(d["intensity"])
+                L.cos_outer, L.inv_cos_cone_diff = float(d["cos_outer"]), float(d["inv_cos_cone_diff"])
+                for k in ("color", "pos", "direction"):
+                    getattr(L, k)[:] = [float(v) for v in d[k]]
+            s.lights.append(L)
+        s.missing_material = len(s.materials) == 0
+        s.m_camera = camera if camera is not None else \
+            Camera(np.eye(4, dtype=np.float32).reshape(16), 60.0, 1.77778, 0.1)
+        s.filename = ""
+        return s
+
     @property
     def n_faces(self):
         return len(self.indices) // 3
