@@ -196,7 +196,8 @@ typedef struct {
     double resolve_ms;            /* copyToFB equivalent */
     double total_ms;              /* whole tpt_render, host wall */
     int32_t trace_launches;
-    int32_t pad;
+    int32_t wg_waves;             /* waves per trace workgroup the launches ran (1, 2 or 4: the build's shape
+                                     for the variant family; 0 with TPT_FLAG_WAVEFRONT) */
     uint64_t wide_visits;         /* 4-wide internal nodes popped (ordered traversal) */
     uint64_t accumulated_spp;     /* samples per pixel in the output (> spp with TPT_FLAG_ACCUMULATE) */
     double trace_kernel_ms;       /* sum of the trace launches' own durations (HIP events per launch);
@@ -536,6 +537,10 @@ tpt_status tpt_debug_trace_rays(tpt_scene* scene, uint32_t n, const float* origi
  *        inv_cos_cone_diff p3)                              out 6 (dir3, radiance3)
  *   op 3 Spectrum::toUChar in 3                             out 3 (bytes as floats) */
 tpt_status tpt_debug_hot_kat(int device, int32_t op, uint32_t n, const float* in, float* out);
+/* Diagnostics: the waves per trace workgroup this build declares for a kernel family (tpt_stats.wg_waves
+ * reports what a call ran): 0 one lane per pixel, 1 the same on drained launches, 2 pair mode, 3 env
+ * importance sampling, 4 four lanes per pixel, 5 the reference's visit order; another family: 0 */
+int32_t tpt_debug_trace_wg_waves(int32_t family);
 /* Diagnostics: the per-step latency of ONE 64-lane wave walking n <= 64 closest-hit rays
  * with the render's traversal ("The drained chain"); mode 0 reads the
  * 4-wide nodes from global memory as the render does, 1 from a copy of the whole main tree

@@ -89,13 +89,13 @@ class Stats(C.Structure):
     _fields_ = [("traversals", C.c_uint64), ("internal_visits", C.c_uint64), ("leaf_tests", C.c_uint64),
                 ("shade_hits", C.c_uint64), ("pixels", C.c_uint64), ("samples", C.c_uint64),
                 ("rng_init_ms", C.c_double), ("trace_ms", C.c_double), ("resolve_ms", C.c_double),
-                ("total_ms", C.c_double), ("trace_launches", C.c_int32), ("pad", C.c_int32),
+                ("total_ms", C.c_double), ("trace_launches", C.c_int32), ("wg_waves", C.c_int32),
                 ("wide_visits", C.c_uint64), ("accumulated_spp", C.c_uint64), ("trace_kernel_ms", C.c_double),
                 ("local_rays", C.c_uint64), ("tree_wait_ms", C.c_double), ("resident_lanes", C.c_uint64),
                 ("lanes_per_pixel", C.c_int32), ("drained", C.c_int32)]
 
     def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Aov(C.Structure):
@@ -172,6 +172,7 @@ SIGNATURES = [
     ("tpt_debug_trace_rays", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_debug_hot_kat", C.c_int, [C.c_int, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("tpt_debug_trace_wg_waves", C.c_int32, [C.c_int32]),
     ("tpt_debug_step_latency", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_void_p]),
     ("tpt_wide_tree_build", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,

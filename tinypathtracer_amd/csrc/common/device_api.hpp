@@ -241,10 +241,17 @@ struct WfArgs {
 hipError_t launch_wavefront(WfArgs w, uint32_t* h_count, hipEvent_t ev[2], int32_t* iterations, hipStream_t s);
 
 // trace.hip
-hipError_t launch_trace(const TraceArgs& a, hipStream_t s);
+// shape (optional, kTraceShapeWords ints): what the launch ran as -- the waves per
+// workgroup of the variant's family (WGW), the workgroups of that size and LDS the
+// runtime says a CU holds, the number that fills the CU's wave slots (4 SIMDs x the
+// variant's waves per SIMD / WGW; the LDS layout shrinks until it is met), the
+// workgroup's LDS bytes, its LDS stack slots and record levels
+constexpr int kTraceShapeWords = 6;
+hipError_t launch_trace(const TraceArgs& a, hipStream_t s, int32_t* shape = nullptr);
 bool trace_quad_fits(const TraceArgs& a);   // lanes_per_pixel 4: one-lane records, the quads' stacks fit in LDS
+int trace_family_wgw(int family);           // tpt_debug_trace_wg_waves
 int trace_waves_per_simd();                 // the one-lane variants' __launch_bounds__ waves per SIMD
-hipError_t launch_trace_ptr(const void* a, hipStream_t s);   // a: const TraceArgs*
+hipError_t launch_trace_ptr(const void* a, hipStream_t s, int32_t* shape);   // a: const TraceArgs*
 // lone-wave step latency probe (tpt_debug_step_latency), a: const TraceArgs*
 hipError_t launch_step_latency_ptr(const void* a, uint32_t n, const float* o, const float* d, int nodes_lds,
                                    unsigned long long* out, hipStream_t s);
@@ -395,7 +402,7 @@ hipError_t launch_svgf_resolve(const SvgfArgs& a, hipStream_t s);
 // The tolerance-mode build of trace.hip (TPT_FLAG_FAST; Makefile trace_fast.hip.o):
 // the same kernels in namespace tpt_fast, reached with a tpt::TraceArgs.
 namespace tpt_fast {
-hipError_t launch_trace_ptr(const void* a, hipStream_t s);
+hipError_t launch_trace_ptr(const void* a, hipStream_t s, int32_t* shape);
 hipError_t launch_step_latency_ptr(const void* a, uint32_t n, const float* o, const float* d, int nodes_lds,
                                    unsigned long long* out, hipStream_t s);
 }

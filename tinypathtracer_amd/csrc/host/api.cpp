@@ -160,6 +160,8 @@ tpt_status tpt_debug_step_latency(tpt_scene* s, uint32_t n, const float* o, cons
     return TPT_OK;
 }
 
+int32_t tpt_debug_trace_wg_waves(int32_t family) { return tpt::trace_family_wgw(family); }
+
 tpt_status tpt_debug_hot_kat(int device, int32_t op, uint32_t n, const float* in, float* out) {
     static const int kIn[4] = {12, 15, 16, 3}, kOut[4] = {2, 4, 6, 3};
     if (op < 0 || op > 3) return fail(TPT_ERR_INVALID_ARG, "unknown KAT op");

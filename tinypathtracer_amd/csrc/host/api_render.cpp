@@ -140,7 +140,8 @@ struct WaveDump {
 // run their chunks on streams of their own and join it again.  `a` holds the
 // whole call (all its rows, the call's deal); list_len is its explicit deal's length.
 tpt_status render_planned(tpt_scene* s, const tpt::TraceArgs& a, const tpt_params* p, const tpt::LaunchPlan& plan,
-                          size_t list_len, WaveDump& dump, double& trace_ms, double& kernel_ms, int& launches) {
+                          size_t list_len, WaveDump& dump, double& trace_ms, double& kernel_ms, int& launches,
+                          int32_t* shape) {
     hipStream_t st = s->stream;
     const int nset = plan.nset;
     const size_t nf = (size_t)a.n_frames;
@@ -148,7 +149,7 @@ tpt_status render_planned(tpt_scene* s, const tpt::TraceArgs& a, const tpt_param
 #if defined(TPT_PROFILE_PHASES) || defined(TPT_VERIFY_CULL)
     dump.path = std::getenv("TPT_DEBUG_WAVES");
 #endif
-    // one record per wave of the largest grid: 8x8-pixel workgroups (four lanes per
+    // one record per wave of the largest grid: 8x8-pixel tiles (four lanes per
     // pixel; pair mode 16x8, one lane 16x16), 4 waves each, 8 words per wave
     const size_t dbg_launch =
         8ull * 4 * (size_t)((a.width + 7) / 8) * (size_t)((std::max(a.band_height, 1) + 7) / 8) * nf;
@@ -209,7 +210,8 @@ tpt_status render_planned(tpt_scene* s, const tpt::TraceArgs& a, const tpt_param
         if (dump.path) ak.debug_waves = s->debug.p + oi * dbg_launch;
 #endif
         SET_OR_FAIL(hipEventRecord(s->lev[2 * j], qs[k]));
-        SET_OR_FAIL((p->flags & TPT_FLAG_FAST) ? tpt_fast::launch_trace_ptr(&ak, qs[k]) : tpt::launch_trace(ak, qs[k]));
+        SET_OR_FAIL((p->flags & TPT_FLAG_FAST) ? tpt_fast::launch_trace_ptr(&ak, qs[k], shape)
+                                               : tpt::launch_trace(ak, qs[k], shape));
         SET_OR_FAIL(hipEventRecord(s->lev[2 * j + 1], qs[k]));
     }
     for (int k = 0; nset > 1 && k < nset; ++k) {   // join
@@ -395,12 +397,18 @@ tpt_status tpt_render_frames(tpt_scene* s, const tpt_env* env, const tpt_camera*
     double trace_ms = 0.0, kernel_ms = 0.0;
     int launches = 0;
     WaveDump dump;
+    int32_t shape[tpt::kTraceShapeWords] = {};   // (all zero: the wavefront variant)
     if ((p->flags & TPT_FLAG_WAVEFRONT) && (p->flags & (TPT_FLAG_FAST | TPT_FLAG_APPROX_CULL)))
         return fail(TPT_ERR_INVALID_ARG, "TPT_FLAG_WAVEFRONT runs the exact traversal only");
     const tpt_status ts = (p->flags & TPT_FLAG_WAVEFRONT)
                               ? render_wavefront(s, a, p, n_frames, bh, trace_ms, kernel_ms, launches)
-                              : render_planned(s, a, p, plan, list.size(), dump, trace_ms, kernel_ms, launches);
+                              : render_planned(s, a, p, plan, list.size(), dump, trace_ms, kernel_ms, launches, shape);
     if (ts != TPT_OK) return ts;
+    if (std::getenv("TPT_DEBUG_SHAPE"))   // the k_trace workgroups this call ran, and the runtime's residency answer
+        std::fprintf(stderr,
+                     "tpt trace shape: wg_waves %d resident_blocks %d need_blocks %d lds_bytes %d stack_slots %d "
+                     "rec_levels %d\n",
+                     shape[0], shape[1], shape[2], shape[3], shape[4], shape[5]);
 
     // copyToFB (:553) + radiance readout, per frame
     HIP_OR_FAIL(hipEventRecord(s->ev[2], st));
@@ -479,6 +487,7 @@ tpt_status tpt_render_frames(tpt_scene* s, const tpt_env* env, const tpt_camera*
         (void)hipEventElapsedTime(&ms, s->ev[2], s->ev[3]);
         stats->resolve_ms = ms;
         stats->trace_launches = launches;
+        stats->wg_waves = shape[0];
         stats->resident_lanes = s->resident_lanes;
         stats->lanes_per_pixel = plan.quad ? 4 : (plan.pair_kernel ? 2 : 1);
         stats->drained = a.drained;

@@ -27,6 +27,9 @@
 //    LDS or not, 16/32-bit stack ids, record depth 8/64; the reference order
 //    and the opt-in env importance sampling have one general variant each;
 //  * triangles are pre-gathered (v0, e1, e2, fid: three 16-B loads).
+#include <array>
+#include <map>
+#include <mutex>
 #include <type_traits>
 
 #include "trace_dev.hpp"
@@ -102,20 +105,26 @@ __device__ __noinline__ void verify_ray(const TraceArgs& a, const Trav& r, int p
 // instead of 1 + lights, which is what bounds tail-heavy frames (C3).
 template <int MAXD, bool ORDERED, bool LIGHTS, bool MTL_LDS, typename StackT, bool ENVIS = false, bool PAIR = false,
           bool DRAIN = false, bool QUAD = false, bool NOEMIT = false>
-__global__ __launch_bounds__(256, ENVIS ? TPT_TRACE_WAVES_IS
-                                        : (PAIR ? TPT_TRACE_WAVES_PAIR
-                                                : (QUAD ? TPT_TRACE_WAVES_QUAD
-                                                        : (DRAIN ? TPT_TRACE_WAVES_DRAIN : TPT_TRACE_WAVES))))
+__global__ __launch_bounds__((64 * trace_wgw<ORDERED, ENVIS, PAIR, DRAIN, QUAD>()),
+                             ENVIS ? TPT_TRACE_WAVES_IS
+                                   : (PAIR ? TPT_TRACE_WAVES_PAIR
+                                           : (QUAD ? TPT_TRACE_WAVES_QUAD
+                                                   : (DRAIN ? TPT_TRACE_WAVES_DRAIN : TPT_TRACE_WAVES))))
 void k_trace(TraceArgs a) {
     static_assert(!PAIR || (ORDERED && LIGHTS), "pair mode: ordered variants with 5-word records");
     static_assert(!QUAD || (ORDERED && !LIGHTS && !PAIR && !ENVIS && !DRAIN), "four lanes per pixel: one-lane logic");
+    // A tile is four waves (2 x 2 sub-tiles), rendered by 4 / WGW workgroups of WGW
+    // waves each, adjacent in grid x: block x = tile * (4 / WGW) + part.  The tiles
+    // are dispatched in the order 4-wave workgroups were.
+    constexpr int WGW = trace_wgw<ORDERED, ENVIS, PAIR, DRAIN, QUAD>(), NB = 4 / WGW, ROW = 64 * WGW;
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     // grid y interleaves the frames of a batch: consecutive workgroups render the
     // same screen rows of successive frames, so the resident tiles keep the
     // screen locality of a single frame (node reuse in L1/L2)
     const int nfr = a.n_frames > 0 ? a.n_frames : 1;
-    int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    int bx = (int)blockIdx.x / NB, part = (int)blockIdx.x % NB;
+    const int by = (int)blockIdx.y;
     // XCD runs (scenes larger than an XCD's 4 MiB L2): blocks b and b + 8 share
     // an XCD.  Within each row of workgroups XCD k gets runs of xcd_run
     // adjacent tiles instead of every 8th tile, so its resident tiles see less
@@ -128,10 +137,16 @@ void k_trace(TraceArgs a) {
     // rotation, and its heavy columns would load the same XCDs in every chunk of
     // the set's spp: the host rotates each chunk by one more (xcd_rot), so over 8
     // chunks every XCD takes every tile once.
+    // Runs are counted in tiles (16-pixel columns) whatever WGW is: an XCD's
+    // blocks of a row, in its dispatch order, are its tiles' parts, tile by tile.
+    [[maybe_unused]] int tile_id = bx;   // the tile's place in the row's dispatch order (the debug dump's id)
     if (a.xcd_run > 0) {
-        const int g = a.xcd_run, k = ((bx & 7) + by + a.xcd_rot) & 7, m = bx >> 3;
+        const int b = (int)blockIdx.x, g = a.xcd_run, k = ((b & 7) + by + a.xcd_rot) & 7, m = (b >> 3) / NB;
+        part = (b >> 3) % NB;
+        tile_id = m * 8 + (b & 7);
         bx = ((m / g) * 8 + k) * g + m % g;
     }
+    const int wave = part * WGW + (tid >> 6);   // the wave's sub-tile of its tile, 0..3
     const int frame = by % nfr;
     // pair mode: lane 2q (path) and 2q + 1 (side) serve pixel q of the wave's 8x4 tile
     const bool side = PAIR && (lane & 1);
@@ -163,7 +178,7 @@ void k_trace(TraceArgs a) {
     TPT_LDS char* slds = (TPT_LDS char*)lds;
     TPT_LDS LdsF4* smtl = (TPT_LDS LdsF4*)(slds + a.lds_mtl_offset);
     if constexpr (MTL_LDS) {
-        for (int i = tid; i < 2 * (a.n_materials + 1); i += 256) {
+        for (int i = tid; i < 2 * (a.n_materials + 1); i += ROW) {
             const float4 m = a.mtl[i];
             smtl[i].x = m.x;
             smtl[i].y = m.y;
@@ -173,14 +188,23 @@ void k_trace(TraceArgs a) {
     }
     // a.lds_nodes is always 0 (device_api.hpp says why this loop is still here)
     TPT_LDS LdsF4* snodes = (TPT_LDS LdsF4*)(slds + a.lds_nodes_offset);
-    for (int i = tid; i < 8 * a.lds_nodes; i += 256) {
+    for (int i = tid; i < 8 * a.lds_nodes; i += ROW) {
         const float4 m = a.inner4[i];
         snodes[i].x = m.x;
         snodes[i].y = m.y;
         snodes[i].z = m.z;
         snodes[i].w = m.w;
     }
-    if (MTL_LDS || a.lds_nodes > 0) __syncthreads();
+    if (MTL_LDS || a.lds_nodes > 0) {
+        if constexpr (WGW == 1) {
+            // one wave: its LDS accesses execute in program order, the compiler only
+            // has to keep the other lanes' reads behind this copy
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        } else {
+            __syncthreads();
+        }
+    }
     auto MT = [&](int i) -> float4 {
         if constexpr (MTL_LDS) {
             return make_float4(smtl[i].x, smtl[i].y, smtl[i].z, smtl[i].w);
@@ -189,11 +213,12 @@ void k_trace(TraceArgs a) {
         }
     };
     // (QUAD: one stack per quad in its four lanes' columns; the host keeps it all in LDS)
-    LaneStack<StackT, QUAD> stk;
+    // (tid counts the workgroup's own lanes: rows of ROW = 64 * WGW columns)
+    LaneStack<StackT, QUAD, ROW> stk;
     stk.lds = (TPT_LDS StackT*)(slds + a.lds_stack_offset) + (QUAD ? (tid & ~3) : tid);
     stk.nlds = a.stack_lds_slots;
-    PathRecords<MAXD, PAIR ? 128 : 256> rec;
-    rec.lds = (TPT_LDS float*)(slds + a.lds_rec_offset) + (PAIR ? wave * 32 + pl : tid);
+    PathRecords<MAXD, PAIR ? ROW / 2 : ROW> rec;
+    rec.lds = (TPT_LDS float*)(slds + a.lds_rec_offset) + (PAIR ? (tid >> 6) * 32 + pl : tid);
     rec.nlds = a.rec_lds_levels;
     rec.words = LIGHTS ? 5 : 2;
 
@@ -872,8 +897,9 @@ void k_trace(TraceArgs a) {
         atomicAdd(&a.counters[14], life);
         atomicAdd(&a.counters[15], 1ull);
         if (a.debug_waves) {   // per-wave record: start, life, steps, shading passes, rays, wide, max lane rays, done-time
+            // tile * 4 + sub-tile, whatever the workgroup shape
             const unsigned long long wid =
-                ((unsigned long long)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave;
+                ((unsigned long long)blockIdx.y * (gridDim.x / NB) + tile_id) * 4 + wave;
             unsigned long long* o = a.debug_waves + 8 * wid;
             o[0] = t_wave0;
             o[1] = life;
@@ -1046,74 +1072,46 @@ hipError_t launch_hot_kat(int op, uint32_t n, const float* in, float* out, hipSt
     return hipGetLastError();
 }
 
-template <int MAXD, bool ORDERED, bool LIGHTS, bool MTL_LDS, typename StackT, bool ENVIS = false, bool PAIR = false,
-          bool DRAIN = false, bool QUAD = false, bool NOEMIT = false>
-static void launch_one(const TraceArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((k_trace<MAXD, ORDERED, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, QUAD, NOEMIT>), grid,
-                       dim3(256), lds, s, a);
-}
-// four lanes per pixel (a.quad): one-lane logic without delta lights
-template <bool MTL_LDS, typename StackT>
-static void launch_quad(const TraceArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    if (a.max_depth <= 8) launch_one<8, true, false, MTL_LDS, StackT, false, false, false, true>(a, grid, lds, s);
-    else launch_one<64, true, false, MTL_LDS, StackT, false, false, false, true>(a, grid, lds, s);
-}
-
-// PAIR: pair mode (delta-light scenes only).  NOEMIT (pair variants): no triangle
-// emits, so every direct probe ends in the shading pass and the probe's
-// traversal phases are compiled out -- the pair kernel's registers for C3's and
-// C3 + IS's ball.
-template <bool LIGHTS, bool MTL_LDS, typename StackT, bool PAIR = false, bool ENVIS = false, bool DRAIN = false>
-static void launch_ordered_d(const TraceArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    if constexpr (PAIR) {
-        if (!a.any_emitter) {
-            if (a.max_depth <= 8)
-                launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, false, true>(a, grid, lds, s);
-            else
-                launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, false, true>(a, grid, lds, s);
-            return;
-        }
-    }
-    if (a.max_depth <= 8) launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN>(a, grid, lds, s);
-    else launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN>(a, grid, lds, s);
-}
-// DRAIN variants (parked triangles prefetched) for launches that cannot fill the
-// chip (a.drained), one-lane-per-pixel ordered kernels only
-template <bool LIGHTS, bool MTL_LDS, typename StackT, bool PAIR = false, bool ENVIS = false>
-static void launch_ordered(const TraceArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    if constexpr (!PAIR && !ENVIS) {
-        if (a.drained) {
-            launch_ordered_d<LIGHTS, MTL_LDS, StackT, PAIR, ENVIS, true>(a, grid, lds, s);
-            return;
-        }
-    }
-    launch_ordered_d<LIGHTS, MTL_LDS, StackT, PAIR, ENVIS, false>(a, grid, lds, s);
-}
-
-// LDS per 256-lane workgroup: [material table][traversal stack][path records],
-// within kLdsBudget (TPT_TRACE_WAVES workgroups per CU share the 160 KiB).
-constexpr size_t kLdsBudget = (163840 / TPT_TRACE_WAVES) & ~(size_t)255;
-constexpr size_t kLdsBudgetIS = (163840 / TPT_TRACE_WAVES_IS) & ~(size_t)255;
-constexpr size_t kLdsBudgetPair = (163840 / TPT_TRACE_WAVES_PAIR) & ~(size_t)255;
-constexpr size_t kLdsBudgetQuad = (163840 / TPT_TRACE_WAVES_QUAD) & ~(size_t)255;
 #ifndef TPT_MTL_LDS_MAX
 #define TPT_MTL_LDS_MAX 2048
 #endif
 constexpr size_t kLdsMtlMax = TPT_MTL_LDS_MAX;   // material tables up to 64 entries go to LDS
+constexpr size_t kLdsSlack = 512;   // bytes per wave left free in workgroups of fewer than four waves
 
-size_t trace_lds_bytes(TraceArgs& a, int words, size_t elem, bool mtl_lds, int rec_cols = 256,
-                       size_t lds_budget = kLdsBudget, bool quad = false) {
-    // [material table][traversal stack][path records].
+// A launch's LDS layout request: the record words per level, the stack's id size,
+// where the material table lives, the lane mode, the variant's waves per SIMD.
+struct LdsSpec {
+    int words;
+    size_t elem;
+    bool mtl_lds;
+    bool pair;
+    bool quad;
+    int waves;
+};
+
+// LDS per workgroup of `wgw` waves: [material table][traversal stack][path records],
+// within the workgroup's share of the CU's 160 KiB when the CU holds `waves` waves
+// per SIMD (a 4-wave workgroup's share rounded down to 256 B, times wgw / 4).
+// max_slots / max_levels cap the stack slots and record levels (fit_lds).
+size_t trace_lds_bytes(TraceArgs& a, const LdsSpec& sp, int wgw, size_t max_slots = (size_t)-1,
+                       size_t max_levels = (size_t)-1) {
     // Priorities (measured on box): the whole stack (a
     // stack capped at 23 of its 40 slots cost 7 %), then path records up to
     // max_depth (records of long paths in private memory slow the heaviest
     // tiles).
-    const size_t mtl_bytes = mtl_lds ? ((size_t)(a.n_materials + 1) * 2 * 16 + 127) / 128 * 128 : 0;
-    a.mtl_in_lds = mtl_lds ? 1 : 0;
+    size_t lds_budget = ((163840 / (size_t)sp.waves) & ~(size_t)255) * (size_t)wgw / 4;
+    // Smaller workgroups leave kLdsSlack bytes per wave unused.  A layout that fills the
+    // CU's LDS exactly (box at one wave: 20 x 8,192 B) was resident only four waves per
+    // SIMD deep on the device although the runtime's occupancy query (fit_lds) answered
+    // five: C2 -2.8 %; with 512 B per wave of slack +2.6 % ("Workgroup shape").
+    if (wgw < 4) lds_budget -= kLdsSlack * (size_t)wgw;
+    const size_t row = 64 * (size_t)wgw;   // the workgroup's lanes
+    const size_t mtl_bytes = sp.mtl_lds ? ((size_t)(a.n_materials + 1) * 2 * 16 + 127) / 128 * 128 : 0;
+    a.mtl_in_lds = sp.mtl_lds ? 1 : 0;
     a.lds_mtl_offset = 0;
     const size_t budget = lds_budget - mtl_bytes;
-    const size_t slot = quad ? 64 * elem : 256 * elem;   // (quad: four slots per 256-lane row)
-    const size_t level = (size_t)words * (size_t)rec_cols * sizeof(float);
+    const size_t slot = sp.quad ? row / 4 * sp.elem : row * sp.elem;   // (quad: four slots per row of lanes)
+    const size_t level = (size_t)sp.words * (sp.pair ? row / 2 : row) * sizeof(float);
     // The whole stack (capacity + 3 spare slots for the unconditional 4-wide
     // pushes) when the path records of max_depth levels fit beside it.  Else
     // the records first: the ordered walk rarely goes deep (C5: 99 % of visits
@@ -1121,15 +1119,15 @@ size_t trace_lds_bytes(TraceArgs& a, int words, size_t elem, bool mtl_lds, int r
     // at least 12, and deeper entries spill to private memory.  Measured on C5
     // (44 slots of 32-bit ids): 27 stack slots + 2 record levels 7.63 Grays/s,
     // 19 + 6: 7.97, 12 + 8: 8.20.
-    size_t slots = (size_t)a.stack_depth + 3;
-    const size_t want = std::min<size_t>((size_t)a.max_depth, (budget - 12 * slot) / level);
+    size_t slots = std::min((size_t)a.stack_depth + 3, max_slots);
+    const size_t want = std::min(std::min<size_t>((size_t)a.max_depth, (budget - 12 * slot) / level), max_levels);
     if (slots * slot + want * level > budget)
         slots = std::min(slots, std::max<size_t>(12, ((budget - want * level) / slot) & ~(size_t)1));   // even
     // the region holds a whole number of slot pairs (quad: of 4-slot rows), rounded to 16 bytes
-    const size_t stack = quad ? ((slots + 3) / 4 * 4 * slot + 15) / 16 * 16
-                              : ((slots + 1) / 2 * 2 * slot + 15) / 16 * 16;
+    const size_t stack = sp.quad ? ((slots + 3) / 4 * 4 * slot + 15) / 16 * 16
+                                 : ((slots + 1) / 2 * 2 * slot + 15) / 16 * 16;
     size_t levels = (budget - stack) / level;
-    if (levels > (size_t)a.max_depth) levels = (size_t)a.max_depth;
+    levels = std::min(std::min(levels, (size_t)a.max_depth), max_levels);
     a.lds_nodes = 0;
     a.lds_nodes_offset = (int)mtl_bytes;
     a.stack_lds_slots = (int)slots;
@@ -1139,16 +1137,141 @@ size_t trace_lds_bytes(TraceArgs& a, int words, size_t elem, bool mtl_lds, int r
     return mtl_bytes + stack + levels * level;
 }
 
+// One launch_trace call: the grid in tiles, the LDS request, and whether it only
+// asks what would run (dry: trace_quad_fits).
+struct LaunchCtx {
+    dim3 tiles;
+    LdsSpec lds;
+    hipStream_t s;
+    bool dry;
+    int32_t* shape;
+    hipError_t err;
+};
+
+// The layout of a variant at one scene / depth, settled once: the caps under which
+// the runtime holds a CU's full set of workgroups, and its answer.
+struct LdsFit {
+    size_t max_slots, max_levels;
+    int resident, need;
+};
+
+// The budget arithmetic assumes the device allocates LDS in granules that divide a
+// workgroup's share exactly (box at one wave: 8,192 B = 163,840 / 20, no slack), and
+// the compiler's occupancy remark rounds, so the runtime is asked: workgroups of
+// this kernel, size and LDS per CU.  Fewer than fill the CU's wave slots: the layout
+// shrinks by trace_lds_bytes' priority -- stack slots (never below 12), then record
+// levels -- until they fit.
+template <typename K>
+static LdsFit fit_lds(K kern, const TraceArgs& a_in, const LdsSpec& sp, int wgw, int waves) {
+    LdsFit f{(size_t)-1, (size_t)-1, 0, 4 * waves / wgw};
+    int regs = 0;   // what registers alone allow (never more than the launch bounds asked for)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&regs, kern, 64 * wgw, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return f;
+    }
+    const int target = std::min(f.need, regs);
+    for (;;) {
+        TraceArgs a = a_in;
+        const size_t lds = trace_lds_bytes(a, sp, wgw, f.max_slots, f.max_levels);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&f.resident, kern, 64 * wgw, lds) != hipSuccess) {
+            (void)hipGetLastError();
+            return f;
+        }
+        if (f.resident >= target) return f;
+        if (a.stack_lds_slots > 12) f.max_slots = std::max<size_t>(12, (size_t)(a.stack_lds_slots - 1) & ~(size_t)1);
+        else if (a.rec_lds_levels > 0) f.max_levels = (size_t)a.rec_lds_levels - 1;
+        else return f;
+    }
+}
+
+template <int MAXD, bool ORDERED, bool LIGHTS, bool MTL_LDS, typename StackT, bool ENVIS = false, bool PAIR = false,
+          bool DRAIN = false, bool QUAD = false, bool NOEMIT = false>
+static void launch_one(const TraceArgs& a_in, LaunchCtx& c) {
+    constexpr int WGW = trace_wgw<ORDERED, ENVIS, PAIR, DRAIN, QUAD>();
+    // the variant's waves per SIMD (k_trace's __launch_bounds__)
+    constexpr int kWaves = ENVIS ? TPT_TRACE_WAVES_IS
+                                 : (PAIR ? TPT_TRACE_WAVES_PAIR
+                                         : (QUAD ? TPT_TRACE_WAVES_QUAD
+                                                 : (DRAIN ? TPT_TRACE_WAVES_DRAIN : TPT_TRACE_WAVES)));
+    const auto kern = k_trace<MAXD, ORDERED, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, QUAD, NOEMIT>;
+    // once per variant and layout input, not per launch
+    static std::mutex mu;
+    static std::map<std::array<int, 3>, LdsFit> fits;
+    const std::array<int, 3> key{a_in.stack_depth, a_in.max_depth, a_in.n_materials};
+    LdsFit f;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = fits.find(key);
+        if (it == fits.end()) it = fits.emplace(key, fit_lds(kern, a_in, c.lds, WGW, kWaves)).first;
+        f = it->second;
+    }
+    TraceArgs a = a_in;
+    const size_t lds = trace_lds_bytes(a, c.lds, WGW, f.max_slots, f.max_levels);
+    if (c.shape) {
+        c.shape[0] = WGW;
+        c.shape[1] = f.resident;
+        c.shape[2] = f.need;
+        c.shape[3] = (int32_t)lds;
+        c.shape[4] = a.stack_lds_slots;
+        c.shape[5] = a.rec_lds_levels;
+    }
+    // four lanes per pixel: the quads' stacks must lie in LDS whole
+    if (QUAD && a.stack_lds_slots < a.stack_depth + 3) {
+        c.err = hipErrorInvalidValue;
+        return;
+    }
+    if (c.dry) return;
+    hipLaunchKernelGGL(kern, dim3(c.tiles.x * (4 / WGW), c.tiles.y), dim3(64 * WGW), lds, c.s, a);
+    c.err = hipGetLastError();
+}
+// four lanes per pixel (a.quad): one-lane logic without delta lights
+template <bool MTL_LDS, typename StackT>
+static void launch_quad(const TraceArgs& a, LaunchCtx& c) {
+    if (a.max_depth <= 8) launch_one<8, true, false, MTL_LDS, StackT, false, false, false, true>(a, c);
+    else launch_one<64, true, false, MTL_LDS, StackT, false, false, false, true>(a, c);
+}
+
+// PAIR: pair mode (delta-light scenes only).  NOEMIT (pair variants): no triangle
+// emits, so every direct probe ends in the shading pass and the probe's
+// traversal phases are compiled out -- the pair kernel's registers for C3's and
+// C3 + IS's ball.
+template <bool LIGHTS, bool MTL_LDS, typename StackT, bool PAIR = false, bool ENVIS = false, bool DRAIN = false>
+static void launch_ordered_d(const TraceArgs& a, LaunchCtx& c) {
+    if constexpr (PAIR) {
+        if (!a.any_emitter) {
+            if (a.max_depth <= 8)
+                launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, false, true>(a, c);
+            else
+                launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, false, true>(a, c);
+            return;
+        }
+    }
+    if (a.max_depth <= 8) launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN>(a, c);
+    else launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN>(a, c);
+}
+// DRAIN variants (parked triangles prefetched) for launches that cannot fill the
+// chip (a.drained), one-lane-per-pixel ordered kernels only
+template <bool LIGHTS, bool MTL_LDS, typename StackT, bool PAIR = false, bool ENVIS = false>
+static void launch_ordered(const TraceArgs& a, LaunchCtx& c) {
+    if constexpr (!PAIR && !ENVIS) {
+        if (a.drained) {   // (the one-lane variants' LDS budget: the layout does not depend on the launch size)
+            launch_ordered_d<LIGHTS, MTL_LDS, StackT, PAIR, ENVIS, true>(a, c);
+            return;
+        }
+    }
+    launch_ordered_d<LIGHTS, MTL_LDS, StackT, PAIR, ENVIS, false>(a, c);
+}
+
 // waves per SIMD the one-lane trace variants are built for (__launch_bounds__):
 // with the device's CU count, the resident lanes the host's launch rules use
 int trace_waves_per_simd() { return TPT_TRACE_WAVES; }
 
-bool trace_quad_fits(const TraceArgs& a_in) {
-    TraceArgs a = a_in;
-    const bool small = (2 * (size_t)a.n_faces - 1) <= 65535;
-    const bool mtl_lds = (size_t)(a.n_materials + 1) * 2 * sizeof(float4) <= kLdsMtlMax;
-    trace_lds_bytes(a, 2, small ? 2 : 4, mtl_lds, 256, kLdsBudgetQuad, true);
-    return rec_words(a.n_lights, a.n_materials) == 2 && a.stack_lds_slots >= a.stack_depth + 3;
+// the build's workgroup shape per family, in tpt_debug_trace_wg_waves' order
+int trace_family_wgw(int family) {
+    static const int kWgw[6] = {trace_wgw<true, false, false, false, false>(), trace_wgw<true, false, false, true, false>(),
+                                trace_wgw<true, false, true, false, false>(),  trace_wgw<true, true, false, false, false>(),
+                                trace_wgw<true, false, false, false, true>(),  trace_wgw<false, false, false, false, false>()};
+    return family >= 0 && family < 6 ? kWgw[family] : 0;
 }
 
 // f(MTL_LDS as std::bool_constant, StackT as a value) for the launch's material-table
@@ -1164,63 +1287,78 @@ static void for_mtl_stack(bool mtl_lds, bool small, F f) {
     }
 }
 
-hipError_t launch_trace(const TraceArgs& a_in, hipStream_t s) {
+static hipError_t launch_trace_impl(const TraceArgs& a_in, hipStream_t s, bool dry, int32_t* shape) {
     TraceArgs a = a_in;
-    dim3 grid((a.width + 15) / 16, ((a.band_height + 15) / 16) * (a.n_frames > 0 ? a.n_frames : 1));
-    // the XCD-run remap is a permutation of a row's tiles only if runs tile gridDim.x / 8
-    if (a.xcd_run > 0 && (grid.x % 8 != 0 || (grid.x / 8) % (unsigned)a.xcd_run != 0)) a.xcd_run = 0;
+    const unsigned nfr = (unsigned)(a.n_frames > 0 ? a.n_frames : 1);
+    // the grid in tiles of four waves: 16x16 pixels (pair mode 16x8, four lanes per pixel 8x8)
+    LaunchCtx c{dim3((a.width + 15) / 16, ((a.band_height + 15) / 16) * nfr), LdsSpec{}, s, dry, shape, hipSuccess};
+    // the XCD-run remap is a permutation of a row's tiles only if runs tile the row's tiles / 8
+    if (a.xcd_run > 0 && (c.tiles.x % 8 != 0 || (c.tiles.x / 8) % (unsigned)a.xcd_run != 0)) a.xcd_run = 0;
     if (a.flags & TPT_FLAG_REF_ORDER) {
         // the reference's visit order (tests, diagnostics): one general variant
-        const size_t lds = trace_lds_bytes(a, 5, sizeof(int), false);
-        if (a.env_is) launch_one<64, false, true, false, int, true>(a, grid, lds, s);
-        else launch_one<64, false, true, false, int>(a, grid, lds, s);
-        return hipGetLastError();
+        c.lds = LdsSpec{5, sizeof(int), false, false, false, TPT_TRACE_WAVES};
+        if (a.env_is) launch_one<64, false, true, false, int, true>(a, c);
+        else launch_one<64, false, true, false, int>(a, c);
+        return c.err;
     }
     const bool small = (2 * (size_t)a.n_faces - 1) <= 65535;
     const bool mtl_lds = (size_t)(a.n_materials + 1) * 2 * sizeof(float4) <= kLdsMtlMax;
+    const size_t elem = small ? 2 : 4;
     if (a.env_is) {
         // opt-in env next-event estimation (A15): variants of their own (the
         // delta-light machinery: 5-word records), so the others stay lean; pair
         // mode hands each diffuse bounce's env shadow ray (and its delta lights'
         // rays) to the side lane
         const bool pair_is = a.pair && (a.n_materials + 1) < (int)kNoProbe;
-        if (pair_is) grid.y = ((a.band_height + 7) / 8) * (a.n_frames > 0 ? a.n_frames : 1);
-        const size_t lds = trace_lds_bytes(a, 5, small ? 2 : 4, mtl_lds, pair_is ? 128 : 256, kLdsBudgetIS);
+        if (pair_is) c.tiles.y = ((a.band_height + 7) / 8) * nfr;
+        c.lds = LdsSpec{5, elem, mtl_lds, pair_is, false, TPT_TRACE_WAVES_IS};
         for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
-            if (pair_is) launch_ordered<true, decltype(m)::value, decltype(st), true, true>(a, grid, lds, s);
-            else launch_ordered<true, decltype(m)::value, decltype(st), false, true>(a, grid, lds, s);
+            if (pair_is) launch_ordered<true, decltype(m)::value, decltype(st), true, true>(a, c);
+            else launch_ordered<true, decltype(m)::value, decltype(st), false, true>(a, c);
         });
-        return hipGetLastError();
+        return c.err;
     }
     const bool lights = rec_words(a.n_lights, a.n_materials) == 5;
     if (a.quad) {
-        // four lanes per pixel: 8x8-pixel workgroups; the quads' stacks must lie in
-        // LDS whole (the host checked lights == 0)
-        grid = dim3((a.width + 7) / 8, ((a.band_height + 7) / 8) * (a.n_frames > 0 ? a.n_frames : 1));
+        // four lanes per pixel: 8x8-pixel tiles (the host checked lights == 0)
+        if (lights) return hipErrorInvalidValue;
+        c.tiles = dim3((a.width + 7) / 8, ((a.band_height + 7) / 8) * nfr);
         a.xcd_run = 0;
-        const size_t lds = trace_lds_bytes(a, 2, small ? 2 : 4, mtl_lds, 256, kLdsBudgetQuad, true);
-        if (lights || a.stack_lds_slots < a.stack_depth + 3) return hipErrorInvalidValue;
+        c.lds = LdsSpec{2, elem, mtl_lds, false, true, TPT_TRACE_WAVES_QUAD};
         for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
-            launch_quad<decltype(m)::value, decltype(st)>(a, grid, lds, s);
+            launch_quad<decltype(m)::value, decltype(st)>(a, c);
         });
-        return hipGetLastError();
+        return c.err;
     }
     // pair mode: delta lights (shadow rays to hand off), packed probe ids
     const bool pair = a.pair && lights && a.n_lights > 0 && (a.n_materials + 1) < (int)kNoProbe;
     if (pair) {
-        grid.y = ((a.band_height + 7) / 8) * (a.n_frames > 0 ? a.n_frames : 1);   // 16x8 pixels per workgroup
-        const size_t lds = trace_lds_bytes(a, 5, small ? 2 : 4, mtl_lds, 128, kLdsBudgetPair);
+        c.tiles.y = ((a.band_height + 7) / 8) * nfr;   // 16x8 pixels per tile
+        c.lds = LdsSpec{5, elem, mtl_lds, true, false, TPT_TRACE_WAVES_PAIR};
         for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
-            launch_ordered<true, decltype(m)::value, decltype(st), true>(a, grid, lds, s);
+            launch_ordered<true, decltype(m)::value, decltype(st), true>(a, c);
         });
-        return hipGetLastError();
+        return c.err;
     }
-    const size_t lds = trace_lds_bytes(a, lights ? 5 : 2, small ? 2 : 4, mtl_lds);
+    c.lds = LdsSpec{lights ? 5 : 2, elem, mtl_lds, false, false, TPT_TRACE_WAVES};
     for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
-        if (lights) launch_ordered<true, decltype(m)::value, decltype(st)>(a, grid, lds, s);
-        else launch_ordered<false, decltype(m)::value, decltype(st)>(a, grid, lds, s);
+        if (lights) launch_ordered<true, decltype(m)::value, decltype(st)>(a, c);
+        else launch_ordered<false, decltype(m)::value, decltype(st)>(a, c);
     });
-    return hipGetLastError();
+    return c.err;
+}
+
+hipError_t launch_trace(const TraceArgs& a, hipStream_t s, int32_t* shape) {
+    return launch_trace_impl(a, s, false, shape);
+}
+
+bool trace_quad_fits(const TraceArgs& a_in) {
+    if (rec_words(a_in.n_lights, a_in.n_materials) != 2) return false;
+    TraceArgs a = a_in;
+    a.quad = 1;
+    a.env_is = 0;
+    a.flags &= ~TPT_FLAG_REF_ORDER;
+    return launch_trace_impl(a, nullptr, true, nullptr) == hipSuccess;
 }
 
 // Lone-wave step latency (tpt_debug_step_latency; DESIGN.md section 6, "The
@@ -1373,7 +1511,9 @@ hipError_t launch_step_latency_ptr(const void* a, uint32_t n, const float* o, co
 
 // The host calls the tolerance-mode build (namespace tpt_fast, the same TraceArgs
 // layout) through this entry point.
-hipError_t launch_trace_ptr(const void* a, hipStream_t s) { return launch_trace(*static_cast<const TraceArgs*>(a), s); }
+hipError_t launch_trace_ptr(const void* a, hipStream_t s, int32_t* shape) {
+    return launch_trace(*static_cast<const TraceArgs*>(a), s, shape);
+}
 
 hipError_t launch_resolve(const ResolveArgs& a, hipStream_t s) {
     dim3 grid((a.width + 255) / 256, a.band_height);

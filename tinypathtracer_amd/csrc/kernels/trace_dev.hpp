@@ -56,7 +56,42 @@
 #define TPT_TRACE_WAVES_QUAD 4   // four lanes per pixel (k_trace QUAD)
 #endif
 
+// WGW: the waves of a k_trace workgroup (1, 2 or 4; block size 64 * WGW), one
+// shape per variant family ("Workgroup shape").  A wave's
+// tile does not depend on it.  A workgroup's LDS and its waves' slots are handed
+// on only when its last wave ends, so a smaller workgroup returns the slots of
+// waves that end before their tile's siblings sooner.
+// -DTPT_WG_WAVES=N (EXTRA) builds every family at N waves: 4 is the shape before
+// WGW existed, for an A/B library from the same tree.
+#ifdef TPT_WG_WAVES
+#define TPT_WGW_LANE TPT_WG_WAVES
+#define TPT_WGW_DRAIN TPT_WG_WAVES
+#define TPT_WGW_PAIR TPT_WG_WAVES
+#define TPT_WGW_IS TPT_WG_WAVES
+#define TPT_WGW_QUAD TPT_WG_WAVES
+#define TPT_WGW_REF TPT_WG_WAVES
+#else
+// Measured: one lane per pixel at one wave, C2 +2.6 %; the other families
+// keep four waves until their own configurations are measured.
+#define TPT_WGW_LANE 1    // one lane per pixel, ordered traversal
+#define TPT_WGW_DRAIN 1   // the same, drained launches
+#define TPT_WGW_PAIR 4    // pair mode
+#define TPT_WGW_IS 4      // env importance sampling (pair mode or one lane)
+#define TPT_WGW_QUAD 4    // four lanes per pixel
+#define TPT_WGW_REF 4     // the reference's visit order
+#endif
+
 namespace tpt {
+
+// the workgroup shape of a k_trace variant's family
+template <bool ORDERED, bool ENVIS, bool PAIR, bool DRAIN, bool QUAD>
+constexpr int trace_wgw() {
+    constexpr int w = !ORDERED ? TPT_WGW_REF
+                               : (ENVIS ? TPT_WGW_IS
+                                        : (PAIR ? TPT_WGW_PAIR : (QUAD ? TPT_WGW_QUAD : (DRAIN ? TPT_WGW_DRAIN : TPT_WGW_LANE))));
+    static_assert(w == 1 || w == 2 || w == 4, "waves per k_trace workgroup: 1, 2 or 4");
+    return w;
+}
 
 // LDS-typed pointers: the compiler then always emits ds_* accesses; a plain
 // (generic) pointer that may meet a private or global one in a select is
@@ -290,17 +325,18 @@ __device__ __forceinline__ void slab_minmax(const V3& o, const V3& inv, float nx
 // the LDS fast path for all but the deepest moments.
 constexpr int kMaxStackSlots = 160 + 3;
 
-// LDS slot addressing: [slot][lane], a 256-lane row per slot.
+// LDS slot addressing: [slot][lane], a row of ROW lanes per slot (the
+// workgroup's lanes: 256, or 64 * WGW in k_trace).
 // QS (four lanes per ray): one stack per quad, in its four lanes' columns --
 // slot i at row i / 4, column 4q + i % 4 -- a quarter of the rows
-template <typename StackT, bool QS = false>
+template <typename StackT, bool QS = false, int ROW = 256>
 struct LaneStack {
     TPT_LDS StackT* lds;   // this lane's (QS: its quad's first lane's) base: slot i at lds[off(i)]
     int nlds;
     StackT deep[kMaxStackSlots];
     __device__ static __forceinline__ int off(int i) {
-        if constexpr (QS) return (i >> 2) * 256 + (i & 3);
-        else return i * 256;
+        if constexpr (QS) return (i >> 2) * ROW + (i & 3);
+        else return i * ROW;
     }
     __device__ __forceinline__ void put(int i, int v) {
         if (i < nlds) lds[off(i)] = (StackT)v;
@@ -321,9 +357,9 @@ struct LaneStack {
 // stack region has 3 spare slots so all three writes are unconditional.
 // The visit's arithmetic on the node's seven float4 (k_step_latency also feeds
 // it from its LDS copy of the tree).
-template <typename StackT, bool QS>
+template <typename StackT, bool QS, int ROW>
 __device__ __forceinline__ int inner_visit4_q(const Trav& r, float4 q0, float4 q1, float4 q2, float4 q3, float4 q4,
-                                              float4 q5, float4 q6, LaneStack<StackT, QS>& stk, int& sp) {
+                                              float4 q5, float4 q6, LaneStack<StackT, QS, ROW>& stk, int& sp) {
     float k0, k1, k2, k3, e0, e1, e2, e3;
     slab_minmax(r.o, r.inv, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, k0, e0);
     slab_minmax(r.o, r.inv, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, k1, e1);
@@ -387,9 +423,9 @@ __device__ __forceinline__ int inner_visit4_q(const Trav& r, float4 q0, float4 q
 // eight ordered env-IS variants without an LDS material table compile to other code (PAIR: 7089 ->
 // 6968 instructions, 12 -> 8 spilled VGPRs; tolerance build 23 -> 26).  It goes with k_trace's
 // staging loop (device_api.hpp, lds_nodes), in a change measured on its own.
-template <typename StackT, bool QS>
+template <typename StackT, bool QS, int ROW>
 __device__ __forceinline__ int inner_visit4(const Trav& r, const float4* __restrict__ inner4, int nlds_nodes,
-                                            LaneStack<StackT, QS>& stk, int& sp) {
+                                            LaneStack<StackT, QS, ROW>& stk, int& sp) {
     const float4* nd = inner4 + 8 * r.node;
     return inner_visit4_q(r, nd[0], nd[1], nd[2], nd[3], nd[4], nd[5], nd[6], stk, sp);
 }
@@ -476,10 +512,10 @@ __device__ __forceinline__ void quad_best(Trav& r) {
 }
 // The split visit of 4-wide node r.node (finite rays): returns the child to
 // descend into (-1: none); stop when a leaf test ends an any-hit / occlusion walk.
-template <typename StackT, bool QS>
+template <typename StackT, bool QS, int ROW>
 __device__ __forceinline__ int inner_visit4_quad(Trav& r, const float4* __restrict__ inner4,
                                                  const float4* __restrict__ tri, int nint, float cull_eps,
-                                                 LaneStack<StackT, QS>& stk, int& sp, bool& stop, uint32_t& c_leaf) {
+                                                 LaneStack<StackT, QS, ROW>& stk, int& sp, bool& stop, uint32_t& c_leaf) {
     const int lane = (int)__lane_id(), k = lane & 3;
     const float* nf = (const float*)(inner4 + 8 * (size_t)r.node);
     const float2 b0 = *(const float2*)(nf + 6 * k), b1 = *(const float2*)(nf + 6 * k + 2),
@@ -913,8 +949,8 @@ __device__ __forceinline__ uint32_t p_kind(float prob) {
     return pb == 0x80000000u ? 1u : (pb == 0u ? 2u : 0u);
 }
 
-// RS: LDS columns per workgroup (256: one per lane; 128 in pair mode, one per
-// pixel -- the side lanes keep no records).
+// RS: LDS columns per workgroup (one per lane: 256, or 64 * WGW in k_trace; half
+// that in pair mode, one per pixel -- the side lanes keep no records).
 template <int MAXD, int RS = 256>
 struct PathRecords {
     TPT_LDS float* lds;                        // this lane's column: word at lds[(level*words + w) * RS]
