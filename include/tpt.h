@@ -537,6 +537,24 @@ tpt_status tpt_debug_trace_rays(tpt_scene* scene, uint32_t n, const float* origi
  *        inv_cos_cone_diff p3)                              out 6 (dir3, radiance3)
  *   op 3 Spectrum::toUChar in 3                             out 3 (bytes as floats) */
 tpt_status tpt_debug_hot_kat(int device, int32_t op, uint32_t n, const float* in, float* out);
+/* Known-answer evaluation of the env paths, the parity trig and getNewDirection as the device
+ * compiles them, one case per lane (tests compare them bit for bit with the CPU oracle's hooks).
+ * env: the map of ops 3 and 4 (its texels and its real importance-sampling tables), null otherwise;
+ * state: op 5 only, 6 words per case {v0..v4, d}, advanced in place.
+ *   op 0 fsincos_2pi       in 1 (x)                        out 2 (sin, cos)
+ *   op 1 atan2, double path in 2 (y, x)                     out 1
+ *   op 2 acos, double path  in 1 (y)                        out 1
+ *   op 3 env lookup        in 3 (dir)                      out 10 (fast column, fast row: -1 when the
+ *        fp32 bounds do not decide; exact column, exact row; the lookup's rgb out of line as
+ *        the variants without env IS call it; rgb inlined as the env-IS variants do)
+ *   op 4 env sample        in 5 (incident-side normal3, x1, x2 in [0, 1])
+ *                                                          out 7 (ok, dir3, Le cos / (pi pdf) x3:
+ *        zero when not ok)
+ *   op 5 getNewDirection   in 8 (d3, n3, eta, metallic)    out 5 (next3, attenuation, pdf)
+ * TPT_ERR_INVALID_ARG: an unknown op, a missing env or state, an env on another device, op 4 on
+ * an env whose distribution is empty (all black) or with a uniform outside [0, 1]. */
+tpt_status tpt_debug_env_kat(int device, const tpt_env* env, int32_t op, uint32_t n, const float* in,
+                             uint32_t* state, float* out);
 /* Diagnostics: the waves per trace workgroup this build declares for a kernel family (tpt_stats.wg_waves
  * reports what a call ran): 0 one lane per pixel, 1 the same on drained launches, 2 pair mode, 3 env
  * importance sampling, 4 four lanes per pixel, 5 the reference's visit order; another family: 0 */

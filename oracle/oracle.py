@@ -111,6 +111,19 @@ def lib():
                                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                     C.POINTER(C.c_float)]
         L.orc_trace_ray.restype = C.c_int
+        L.orc_parity_sincos_n.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.orc_parity_sincos_n.restype = None
+        L.orc_kat_env_lookup.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_kat_env_lookup.restype = None
+        L.orc_kat_env_is.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
+        L.orc_kat_env_is.restype = C.c_int
+        L.orc_env_is_tables.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32)]
+        L.orc_env_is_tables.restype = None
+        L.orc_kat_new_direction.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_kat_new_direction.restype = None
         _lib = L
     return _lib
 
@@ -271,3 +284,71 @@ def env_is_samples(rgba_bottom_up, nf, n, seed=7):
     rc = lib().orc_env_is_samples(rgba.ctypes.data, w, h, nfa, seed, n, _ptr(d, C.c_float), _ptr(k, C.c_float))
     assert rc == 0
     return d, k
+
+
+def parity_sincos(x):
+    """orc_parity_sincos over an array: (sin, cos), float32."""
+    x = np.ascontiguousarray(x, np.float32).ravel()
+    s = np.zeros(len(x), np.float32)
+    c = np.zeros(len(x), np.float32)
+    lib().orc_parity_sincos_n(x.ctypes.data, len(x), s.ctypes.data, c.ctypes.data)
+    return s, c
+
+
+def _env_arg(rgba_bottom_up):
+    rgba = np.ascontiguousarray(rgba_bottom_up, np.uint8)
+    assert rgba.ndim == 3 and rgba.shape[2] == 4
+    return rgba, rgba.shape[1], rgba.shape[0]
+
+
+def kat_env_lookup(rgba_bottom_up, dirs):
+    """The miss lookup (trig_mode 1) of directions [n,3]: (rgb [n,3] float32, texel (ix, iy) [n,2] int32)."""
+    rgba, w, h = _env_arg(rgba_bottom_up)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    rgb = np.zeros((len(d), 3), np.float32)
+    ixy = np.zeros((len(d), 2), np.int32)
+    lib().orc_kat_env_lookup(rgba.ctypes.data, w, h, len(d), d.ctypes.data, rgb.ctypes.data, ixy.ctypes.data)
+    return rgb, ixy
+
+
+def kat_env_is(rgba_bottom_up, cases):
+    """One env sample per case (nf3, x1, x2), the uniforms given: (ok [n] int32, dir [n,3],
+    k_le [n,3], zero where not ok)."""
+    rgba, w, h = _env_arg(rgba_bottom_up)
+    a = np.ascontiguousarray(cases, np.float32).reshape(-1, 5)
+    ok = np.zeros(len(a), np.int32)
+    d = np.zeros((len(a), 3), np.float32)
+    k = np.zeros((len(a), 3), np.float32)
+    rc = lib().orc_kat_env_is(rgba.ctypes.data, w, h, len(a), a.ctypes.data, ok.ctypes.data, d.ctypes.data,
+                              k.ctypes.data)
+    if rc != 0:
+        raise ValueError("the map's sampling distribution is empty")
+    return ok, d, k
+
+
+def env_is_tables(rgba_bottom_up):
+    """The env sampler's tables: dict of cond [bh,bw], row [bh], marg [bh] (float32 prefix
+    sums), total (np.float32), b, bw, bh."""
+    rgba, w, h = _env_arg(rgba_bottom_up)
+    total, b, bw, bh = C.c_float(), C.c_int32(), C.c_int32(), C.c_int32()
+    L = lib()
+    L.orc_env_is_tables(rgba.ctypes.data, w, h, None, None, None, C.byref(total), C.byref(b), C.byref(bw),
+                        C.byref(bh))
+    cond = np.zeros((bh.value, bw.value), np.float32)
+    row = np.zeros(bh.value, np.float32)
+    marg = np.zeros(bh.value, np.float32)
+    L.orc_env_is_tables(rgba.ctypes.data, w, h, cond.ctypes.data, row.ctypes.data, marg.ctypes.data,
+                        C.byref(total), C.byref(b), C.byref(bw), C.byref(bh))
+    return {"cond": cond, "row": row, "marg": marg, "total": np.float32(total.value), "b": b.value,
+            "bw": bw.value, "bh": bh.value}
+
+
+def kat_new_direction(cases, states):
+    """getNewDirection per case (d3, n3, eta, metallic) on its RNG state (6 words):
+    (out [n,5] = next3, atten, pdf; states after [n,6])."""
+    a = np.ascontiguousarray(cases, np.float32).reshape(-1, 8)
+    st = np.array(states, np.uint32).reshape(-1, 6).copy()
+    assert len(st) == len(a)
+    out = np.zeros((len(a), 5), np.float32)
+    lib().orc_kat_new_direction(len(a), a.ctypes.data, st.ctypes.data, out.ctypes.data)
+    return out, st

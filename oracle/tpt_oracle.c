@@ -104,6 +104,9 @@ static void parity_sincos(float x, float* s, float* c) {
     }
 }
 void orc_parity_sincos(float x, float* s, float* c) { parity_sincos(x, s, c); }
+void orc_parity_sincos_n(const float* x, int n, float* s, float* c) {
+    for (int i = 0; i < n; ++i) parity_sincos(x[i], &s[i], &c[i]);
+}
 static inline float t_sin(int m, float x) {
     if (!m) return sinf(x);
     float s, c;
@@ -619,15 +622,19 @@ static inline void light_sample(const orc_light* L, v3 p, v3* dir, v3* rad) {
 
 /* sampleEnvLights (:288-294) + Vec2UV (env_light.cuh:72-78) + point/clamp
  * tex2DLod level 0 (texture.cu:156-170). NULL env -> black (defined choice). */
-static inline v3 env_lookup(const orc_env* env, v3 d, int tm) {
-    if (!env || !env->rgba) return V3(0.0f, 0.0f, 0.0f);
+static inline void env_texel(const orc_env* env, v3 d, int tm, int* ix_o, int* iy_o) {
     float u = t_atan2(tm, d.z, d.x) / (2.0f * PI_F);
     if (u < 0.0f) u += 1.0f;
     float v = 1.0f - t_acos(tm, fclamp(d.y, 1.0f, -1.0f)) / PI_F;
     int ix = (int)floorf(u * (float)env->w);
     int iy = (int)floorf(v * (float)env->h);
-    ix = ix < 0 ? 0 : (ix > env->w - 1 ? env->w - 1 : ix);
-    iy = iy < 0 ? 0 : (iy > env->h - 1 ? env->h - 1 : iy);
+    *ix_o = ix < 0 ? 0 : (ix > env->w - 1 ? env->w - 1 : ix);
+    *iy_o = iy < 0 ? 0 : (iy > env->h - 1 ? env->h - 1 : iy);
+}
+static inline v3 env_lookup(const orc_env* env, v3 d, int tm) {
+    if (!env || !env->rgba) return V3(0.0f, 0.0f, 0.0f);
+    int ix, iy;
+    env_texel(env, d, tm, &ix, &iy);
     const uint8_t* px = env->rgba + 4 * ((size_t)iy * (size_t)env->w + (size_t)ix);
     return vscale(1.0f / 255.0f, V3((float)px[0], (float)px[1], (float)px[2]));
 }
@@ -710,9 +717,7 @@ static int lower_bound_f(const float* a, int n, float t) {
  * contribution factor Le * cos / (pi * pdf) with pdf = (p_block * W * H /
  * block texels) / (2 pi^2 sin(theta)), p_block from the CDF steps; 0 when it
  * cannot contribute (the two uniforms are drawn either way). */
-static int env_is_sample(const orc_env* env, const env_is_t* t, v3 nf, uint32_t st[6], int tm, v3* dir, v3* k_le) {
-    const float x1 = orc_uniform(st);
-    const float x2 = orc_uniform(st);
+static int env_is_sample_x(const orc_env* env, const env_is_t* t, v3 nf, float x1, float x2, v3* dir, v3* k_le) {
     const int W = env->w, H = env->h, B = t->b, BW = t->bw, BH = t->bh;
     const float t1 = x1 * t->total;
     const int by = lower_bound_f(t->marg, BH, t1);
@@ -739,7 +744,6 @@ static int env_is_sample(const orc_env* env, const env_is_t* t, v3 nf, uint32_t 
     const float pdf = (pb * (((float)W * (float)H) / (float)(wb * hb))) / ((2.0f * PI_F * PI_F) * sth);
     if (!(sth > 0.0f) || !(c > 0.0f) || !(pdf > 0.0f) || !(pdf < 3.40282347e+38f)) return 0;
     /* Le: the texel the sample lies in (the lookup of dir up to rounding at texel edges) */
-    (void)tm;
     const int fx = (int)(f2 * (float)wb), fy = (int)(f1 * (float)hb);
     const int ix = x0 + (fx < wb - 1 ? fx : wb - 1), iy = y0 + (fy < hb - 1 ? fy : hb - 1);
     const uint8_t* px = env->rgba + 4 * ((size_t)iy * (size_t)W + (size_t)ix);
@@ -747,6 +751,13 @@ static int env_is_sample(const orc_env* env, const env_is_t* t, v3 nf, uint32_t 
     const float k = c / (PI_F * pdf);
     *k_le = vscale(k, le);
     return 1;
+}
+/* the render's sample: the two uniforms from the pixel's stream, x1 first */
+static int env_is_sample(const orc_env* env, const env_is_t* t, v3 nf, uint32_t st[6], int tm, v3* dir, v3* k_le) {
+    (void)tm;
+    const float x1 = orc_uniform(st);
+    const float x2 = orc_uniform(st);
+    return env_is_sample_x(env, t, nf, x1, x2, dir, k_le);
 }
 
 /* Test hook: n env samples for normal nf from stream (seed, subsequence 0):
@@ -1044,3 +1055,64 @@ void orc_kat_to_uchar(const float rgb[3], uint8_t out[3]) {
 }
 
 void orc_kat_default_material(orc_material* m) { *m = k_default_material; }
+
+/* ------------------------------------------------------------------------ */
+/* KAT entry points of the env paths and getNewDirection over arrays of cases: */
+/* the device runs the same cases through tpt_debug_env_kat                   */
+/* (tests/test_gpu_env_maps.py).  trig_mode 1 throughout.                     */
+/* ------------------------------------------------------------------------ */
+void orc_kat_env_lookup(const uint8_t* rgba, int w, int h, int n, const float* dirs, float* rgb, int32_t* ixy) {
+    orc_env env = {rgba, w, h};
+    for (int i = 0; i < n; ++i) {
+        const v3 d = V3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
+        int ix, iy;
+        env_texel(&env, d, 1, &ix, &iy);
+        const v3 c = env_lookup(&env, d, 1);
+        ixy[2 * i] = ix; ixy[2 * i + 1] = iy;
+        rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+    }
+}
+
+int orc_kat_env_is(const uint8_t* rgba, int w, int h, int n, const float* in5, int32_t* ok, float* dirs,
+                   float* k_le) {
+    orc_env env = {rgba, w, h};
+    env_is_t t;
+    env_is_build(&env, &t);
+    if (!(t.total > 0.0f)) { env_is_free(&t); return -1; }
+    for (int i = 0; i < n; ++i) {
+        const float* c = in5 + 5 * i;
+        v3 d = V3(0.0f, 0.0f, 0.0f), k = V3(0.0f, 0.0f, 0.0f);
+        ok[i] = env_is_sample_x(&env, &t, V3(c[0], c[1], c[2]), c[3], c[4], &d, &k);
+        if (!ok[i]) k = V3(0.0f, 0.0f, 0.0f);
+        dirs[3 * i] = d.x; dirs[3 * i + 1] = d.y; dirs[3 * i + 2] = d.z;
+        k_le[3 * i] = k.x; k_le[3 * i + 1] = k.y; k_le[3 * i + 2] = k.z;
+    }
+    env_is_free(&t);
+    return 0;
+}
+
+void orc_env_is_tables(const uint8_t* rgba, int w, int h, float* cond, float* row, float* marg, float* total,
+                       int32_t* b, int32_t* bw, int32_t* bh) {
+    orc_env env = {rgba, w, h};
+    env_is_t t;
+    env_is_build(&env, &t);
+    if (cond) memcpy(cond, t.cond, sizeof(float) * (size_t)t.bw * (size_t)t.bh);
+    if (row) memcpy(row, t.row, sizeof(float) * (size_t)t.bh);
+    if (marg) memcpy(marg, t.marg, sizeof(float) * (size_t)t.bh);
+    *total = t.total; *b = t.b; *bw = t.bw; *bh = t.bh;
+    env_is_free(&t);
+}
+
+void orc_kat_new_direction(int n, const float* in8, uint32_t* states, float* out5) {
+    for (int i = 0; i < n; ++i) {
+        const float* c = in8 + 8 * i;
+        orc_material m = k_default_material;
+        m.eta = c[6];
+        m.metallic = c[7];
+        v3 next = V3(0.0f, 0.0f, 0.0f);
+        float atten = 0.0f;
+        const float pdf = new_direction(V3(c[0], c[1], c[2]), V3(c[3], c[4], c[5]), &m, states + 6 * i, 1, &next, &atten);
+        float* o = out5 + 5 * i;
+        o[0] = next.x; o[1] = next.y; o[2] = next.z; o[3] = atten; o[4] = pdf;
+    }
+}

@@ -142,10 +142,27 @@ void orc_kat_dist_atten(float dist, float rgb[3]);
 void orc_kat_to_uchar(const float rgb[3], uint8_t out[3]);
 void orc_kat_default_material(orc_material* m);
 
+/* KAT entry points of the env paths and getNewDirection (trig_mode 1), the cases
+ * the device runs through tpt_debug_env_kat (tests/test_gpu_env_maps.py):
+ * the miss lookup (sampleEnvLights, path_tracer.cu:288-294): n directions -> rgb (n*3)
+ * and the texel (ix, iy) (n*2); one env sample per case (nf3, x1, x2) with the two
+ * uniforms given -> ok (n), dir (n*3), k_le (n*3, zero where !ok), -1 when the map's
+ * distribution is empty; the sampler's tables (cond [bh*bw], row [bh], marg [bh],
+ * each nullable: a first call reads the sizes); getNewDirection (:187-225) per case
+ * (d3, n3, eta, metallic) on the case's RNG state (6 words, advanced in place) ->
+ * next3, atten, pdf. */
+void orc_kat_env_lookup(const uint8_t* rgba, int w, int h, int n, const float* dirs, float* rgb, int32_t* ixy);
+int orc_kat_env_is(const uint8_t* rgba, int w, int h, int n, const float* in5, int32_t* ok, float* dirs,
+                   float* k_le);
+void orc_env_is_tables(const uint8_t* rgba, int w, int h, float* cond, float* row, float* marg, float* total,
+                       int32_t* b, int32_t* bw, int32_t* bh);
+void orc_kat_new_direction(int n, const float* in8, uint32_t* states, float* out5);
+
 float orc_parity_sinf(float x);
 float orc_parity_cosf(float x);
 /* trig_mode 1 sin/cos of phi in [0, 2pi] (identical to the HIP kernel) */
 void orc_parity_sincos(float x, float* s, float* c);
+void orc_parity_sincos_n(const float* x, int n, float* s, float* c);   /* the same, n values */
 
 #ifdef __cplusplus
 }

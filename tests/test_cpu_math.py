@@ -20,6 +20,8 @@ import pytest
 
 from oracle import oracle as O
 from tests.conftest import ROOT
+from tests.trig_inputs import atan2_acos_vectors, dirs as _dirs, edge_dirs as _edge_dirs, phis as _phis, plain as _plain
+from tests.trig_inputs import ulps as _ulps
 
 HARNESS = r'''
 #include "ptrig.hpp"
@@ -67,15 +69,6 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def _phis(n, seed=1):
-    rng = np.random.default_rng(seed)
-    x = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
-    u = (x.astype(np.float32) * np.float32(2.3283064e-10) + np.float32(2.3283064e-10 / 2.0)).astype(np.float32)
-    phi = (np.float32(2.0 * np.float32(3.141592653589793)) * u).astype(np.float32)
-    edge = np.array([0.0, 1.4629181e-09, 6.2831855, 1.5707964, 3.1415927, 4.712389, 0.7853982], np.float32)
-    return np.concatenate([phi, edge])
-
-
 def test_sincos_kernel_source_equals_oracle(harness):
     phi = _phis(200_000)
     n = len(phi)
@@ -89,14 +82,6 @@ def test_sincos_kernel_source_equals_oracle(harness):
         L.orc_parity_sincos(float(phi[i]), C.byref(os_), C.byref(oc_))
         assert np.float32(os_.value).view(np.uint32) == s[i].view(np.uint32)
         assert np.float32(oc_.value).view(np.uint32) == c[i].view(np.uint32)
-
-
-def _ulps(a, b):
-    ia = a.view(np.int32).astype(np.int64)
-    ib = b.view(np.int32).astype(np.int64)
-    ia = np.where(ia < 0, -(ia & 0x7fffffff), ia)
-    ib = np.where(ib < 0, -(ib & 0x7fffffff), ib)
-    return np.abs(ia - ib)
 
 
 def test_sincos_within_one_ulp(harness):
@@ -113,11 +98,7 @@ def test_sincos_within_one_ulp(harness):
 
 
 def test_env_atan2_acos_match_libm_double(harness):
-    rng = np.random.default_rng(3)
-    v = rng.normal(size=(200_000, 3)).astype(np.float32)
-    v /= np.linalg.norm(v, axis=1, keepdims=True).astype(np.float32)
-    v[::7, 0] = 0.0
-    v[::11, 2] = -0.0
+    v = atan2_acos_vectors()
     y = np.ascontiguousarray(v[:, 2])
     x = np.ascontiguousarray(v[:, 0])
     n = len(x)
@@ -128,36 +109,6 @@ def test_env_atan2_acos_match_libm_double(harness):
     yc = np.ascontiguousarray(np.clip(v[:, 1], -1.0, 1.0))
     harness.h_acos(_p(yc), _p(o), n)
     assert np.array_equal(o.view(np.uint32), np.arccos(yc.astype(np.float64)).astype(np.float32).view(np.uint32))
-
-
-def _dirs(n, seed):
-    rng = np.random.default_rng(seed)
-    v = rng.normal(size=(n, 3)).astype(np.float32)
-    v /= np.linalg.norm(v, axis=1, keepdims=True).astype(np.float32)
-    v[::13, 0] = 0.0
-    v[::17, 2] = -0.0
-    v[::19, 1] = 1.0
-    v[::23, 1] = -1.0
-    return v
-
-
-def _edge_dirs(w, h, seed):
-    """Directions whose (u, v) sit on texel edges (and 1 ulp either side)."""
-    rng = np.random.default_rng(seed)
-    out = []
-    for k in range(0, w + 1, max(1, w // 256)):
-        phi = 2.0 * np.pi * k / w
-        th = rng.uniform(0.05, np.pi - 0.05)
-        out.append((np.sin(th) * np.cos(phi), np.cos(th), np.sin(th) * np.sin(phi)))
-    for k in range(0, h + 1, max(1, h // 256)):
-        th = np.pi * (1.0 - k / h)
-        phi = rng.uniform(0, 2 * np.pi)
-        out.append((np.sin(th) * np.cos(phi), np.cos(th), np.sin(th) * np.sin(phi)))
-    v = np.array(out, np.float32)
-    nb = [v]
-    for d in (-1, 1, -2, 2):   # neighbouring floats of every component
-        nb.append(np.nextafter(v, np.float32(d * np.inf)).astype(np.float32))
-    return np.concatenate(nb)
 
 
 def test_env_fast_trig_error_far_inside_bound(harness):
@@ -190,5 +141,5 @@ def test_env_fast_indices_equal_double_path(harness, w, h):
     # the fast bounds decide almost every random lookup (not the rows _dirs put on
     # an axis -- x = 0 or z = -0 is u on a texel edge -- nor the edge set)
     i = np.arange(300_000)
-    plain = (i % 13 != 0) & (i % 17 != 0) & (i % 19 != 0) & (i % 23 != 0)
+    plain = _plain(300_000)
     assert col[i][plain].mean() > 0.99 and row[i][plain].mean() > 0.99, (col[i][plain].mean(), row[i][plain].mean())

@@ -334,6 +334,35 @@ def hot_kat(op, cases, device=0):
     return out
 
 
+ENV_KAT_OPS = {"sincos": 0, "atan2": 1, "acos": 2, "lookup": 3, "env_is": 4, "new_direction": 5}
+_ENV_KAT_SHAPES = {0: (1, 2), 1: (2, 1), 2: (1, 1), 3: (3, 10), 4: (5, 7), 5: (8, 5)}
+
+
+def env_kat(op, cases, env=None, states=None, device=0):
+    """The device's env paths, parity trig and getNewDirection on `cases`, one per
+    lane (tpt_debug_env_kat; op by number or ENV_KAT_OPS name):
+    sincos (n,1) x -> (n,2) sin, cos of fsincos_2pi; atan2 (n,2) y, x -> (n,1) and
+    acos (n,1) -> (n,1), the double path; lookup (n,3) dir -> (n,10): env_col_fast,
+    env_row_fast (-1: undecided), env_col_exact, env_row_exact, the lookup's rgb out
+    of line and inlined; env_is (n,5) nf, x1, x2 -> (n,7): ok, dir, k_le against the
+    tables of `env` (an EnvLight; lookup and env_is need one); new_direction (n,8)
+    d, n, eta, metallic with `states` (n,6) uint32 -> ((n,5) next, atten, pdf; the
+    states after).  Tests compare them bit for bit with the oracle's hooks."""
+    op = ENV_KAT_OPS.get(op, op)
+    nin, nout = _ENV_KAT_SHAPES[op]
+    a = np.ascontiguousarray(cases, np.float32).reshape(-1, nin)
+    out = np.zeros((len(a), nout), np.float32)
+    st = None
+    if states is not None:
+        st = np.array(states, np.uint32).reshape(-1, 6).copy()
+        if len(st) != len(a):
+            raise ValueError("one RNG state per case")
+    handle = env.handle if env is not None else None
+    check(lib().tpt_debug_env_kat(device, handle, op, len(a), _ptr(a), _ptr(st) if st is not None else None,
+                                  _ptr(out)))
+    return (out, st) if op == 5 else out
+
+
 class BVH:
     """BVH (bvh.cuh:60-68): BVH(size) + construct(vertices, indices) -> m_nodes, m_keys.
     Construction runs on the device (src/bvh.cu:304-331 semantics)."""

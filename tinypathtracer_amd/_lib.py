@@ -172,6 +172,7 @@ SIGNATURES = [
     ("tpt_debug_trace_rays", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_debug_hot_kat", C.c_int, [C.c_int, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("tpt_debug_env_kat", C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_debug_trace_wg_waves", C.c_int32, [C.c_int32]),
     ("tpt_debug_step_latency", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_void_p]),

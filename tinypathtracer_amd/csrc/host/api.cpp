@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <new>
 
+#include "../kernels/kat.hpp"
 #include "api_internal.hpp"
 
 static thread_local std::string g_last_error;
@@ -176,6 +177,38 @@ tpt_status tpt_debug_hot_kat(int device, int32_t op, uint32_t n, const float* in
     HIP_OR_FAIL(tpt::launch_hot_kat(op, n, din.p, dout.p, nullptr));
     HIP_OR_FAIL(hipDeviceSynchronize());
     if (n) HIP_OR_FAIL(hipMemcpy(out, dout.p, sizeof(float) * kOut[op] * (size_t)n, hipMemcpyDeviceToHost));
+    return TPT_OK;
+}
+
+tpt_status tpt_debug_env_kat(int device, const tpt_env* env, int32_t op, uint32_t n, const float* in,
+                             uint32_t* state, float* out) {
+    if (op < 0 || op >= tpt::kEnvKatOps) return fail(TPT_ERR_INVALID_ARG, "unknown KAT op");
+    if (n && (!in || !out)) return fail(TPT_ERR_INVALID_ARG, "null argument");
+    if ((op == 3 || op == 4) && !env) return fail(TPT_ERR_INVALID_ARG, "this op needs an env");
+    if (op == 4 && !(env->is_total > 0.0f)) return fail(TPT_ERR_INVALID_ARG, "the env's distribution is empty");
+    if (op == 5 && n && !state) return fail(TPT_ERR_INVALID_ARG, "this op needs RNG states");
+    if (op == 4)   // the searches index the tables by the uniforms: only (0, 1] (and 0) stays inside them
+        for (uint32_t i = 0; i < n; ++i)
+            for (int k = 3; k < 5; ++k)
+                if (!(in[5 * (size_t)i + k] >= 0.0f && in[5 * (size_t)i + k] <= 1.0f))
+                    return fail(TPT_ERR_INVALID_ARG, "x1 and x2 must lie in [0, 1]");
+    int ndev = tpt_device_count();
+    if (ndev <= 0) return fail(TPT_ERR_NO_DEVICE, "no HIP device available");
+    if (device < 0 || device >= ndev) return fail(TPT_ERR_INVALID_ARG, "bad device index");
+    if (env && env->device != device) return fail(TPT_ERR_INVALID_ARG, "the env lives on another device");
+    DeviceGuard g(device);
+    const size_t nin = (size_t)tpt::kEnvKatIn[op], nout = (size_t)tpt::kEnvKatOut[op];
+    DevBuf<float> din, dout;
+    DevBuf<uint32_t> dst;
+    HIP_OR_FAIL(din.upload(in, nin * n, nullptr));
+    HIP_OR_FAIL(dout.alloc(nout * std::max(n, 1u)));
+    if (op == 5) HIP_OR_FAIL(dst.upload(state, 6 * (size_t)n, nullptr));
+    tpt::TraceArgs a{};
+    fill_env_args(env, a);
+    HIP_OR_FAIL(tpt::launch_env_kat(a, op, n, din.p, dst.p, dout.p, nullptr));
+    HIP_OR_FAIL(hipDeviceSynchronize());
+    if (n) HIP_OR_FAIL(hipMemcpy(out, dout.p, sizeof(float) * nout * n, hipMemcpyDeviceToHost));
+    if (n && op == 5) HIP_OR_FAIL(hipMemcpy(state, dst.p, sizeof(uint32_t) * 6 * (size_t)n, hipMemcpyDeviceToHost));
     return TPT_OK;
 }
 

@@ -266,6 +266,8 @@ std::vector<uint32_t>& host_jumps();
 tpt_status finish_pending(tpt_scene* s, double* wait_ms = nullptr);
 // the scene, the env and (cam non-null) the camera constants of a launch (api_render.cpp)
 void fill_trace_args(tpt_scene* s, const tpt_env* env, const tpt_camera* cam, tpt::TraceArgs& a);
+// the env's part of them alone (nullable env: no map, an empty distribution)
+void fill_env_args(const tpt_env* env, tpt::TraceArgs& a);
 
 }  // namespace host
 }  // namespace tpt

@@ -14,6 +14,23 @@
 #define TPT_XCD_ROT 1   // XCD runs rotate by one per chunk of a set (0: every chunk alike; A/B builds)
 #endif
 
+void tpt::host::fill_env_args(const tpt_env* env, tpt::TraceArgs& a) {
+    a.env = env ? env->texels.p : nullptr;
+    a.env_w = env ? env->w : 0;
+    a.env_h = env ? env->h : 0;
+    a.is_b = env ? env->is_b : 1;
+    a.is_bw = env ? env->is_bw : 0;
+    a.is_bh = env ? env->is_bh : 0;
+    a.is_cond = env ? env->is_cond.p : nullptr;
+    a.is_row = env ? env->is_row.p : nullptr;
+    a.is_marg = env ? env->is_marg.p : nullptr;
+    a.is_total = env ? env->is_total : 0.0f;
+    a.is_guide_r = env ? env->is_guide_r.p : nullptr;
+    a.is_guide_c = env ? env->is_guide_c.p : nullptr;
+    a.is_kr = env ? env->is_kr : 1;
+    a.is_kc = env ? env->is_kc : 1;
+}
+
 void tpt::host::fill_trace_args(tpt_scene* s, const tpt_env* env, const tpt_camera* cam, tpt::TraceArgs& a) {
     a.inner = s->inner.p;
     a.inner4 = s->inner4.p;
@@ -40,20 +57,7 @@ void tpt::host::fill_trace_args(tpt_scene* s, const tpt_env* env, const tpt_came
     a.n_sliver_groups = s->n_sliver_groups;
     a.cull_eps = s->cull_eps;
     a.graze = 1;
-    a.env = env ? env->texels.p : nullptr;
-    a.env_w = env ? env->w : 0;
-    a.env_h = env ? env->h : 0;
-    a.is_b = env ? env->is_b : 1;
-    a.is_bw = env ? env->is_bw : 0;
-    a.is_bh = env ? env->is_bh : 0;
-    a.is_cond = env ? env->is_cond.p : nullptr;
-    a.is_row = env ? env->is_row.p : nullptr;
-    a.is_marg = env ? env->is_marg.p : nullptr;
-    a.is_total = env ? env->is_total : 0.0f;
-    a.is_guide_r = env ? env->is_guide_r.p : nullptr;
-    a.is_guide_c = env ? env->is_guide_c.p : nullptr;
-    a.is_kr = env ? env->is_kr : 1;
-    a.is_kc = env ? env->is_kc : 1;
+    fill_env_args(env, a);
     if (cam) set_camera(a, camera_consts(cam));
 }
 
