@@ -8,6 +8,11 @@
 //   host_check plan CASE...   plan_launches (host/launch_plan.cpp); CASE is key=value,... (plan_case below);
 //                             prints the plan as one JSON object per case
 //   host_check plan-sweep N SEED   N random cases, the plan's invariants checked here
+//   host_check variant CASE...     the k_trace variant space (common/trace_variant.hpp); CASE is "table", or
+//                                  key=value,... with select=1 (select_trace_variant) or layout=1
+//                                  (trace_lds_layout) first (variant_case below); one JSON object per case
+//   host_check variant-sweep N SEED   plan-sweep's cases and more: every plan's lane mode and workgroup rows
+//                                  are those of the variant launch_trace selects for the plan's requests
 //
 // Prints one line per input: "ok", or "error: <message>" for a parse error
 // (the library's exception, which tpt_gltf_load / tpt_env_load turn into a
@@ -169,12 +174,10 @@ static const char* plan_broken(const PlanCase& c, const tpt::LaunchPlan& pl) {
     return nullptr;
 }
 
-static int check_plan_sweep(int n, unsigned seed) {
-    std::mt19937 rng(seed);
+// One random case of the sweeps.
+static void random_case(std::mt19937& rng, PlanCase& c) {
     auto pick = [&](int lo, int hi) { return lo + (int)(rng() % (unsigned)(hi - lo + 1)); };
-    int planned = 0;
-    for (int i = 0; i < n; ++i) {
-        PlanCase c;
+    {
         tpt::PlanInput& in = c.in;
         static const int kRows[] = {1, 4, 8, 16, 32};
         static const int kRes[] = {640, 20480, 327680};
@@ -208,7 +211,16 @@ static int check_plan_sweep(int n, unsigned seed) {
         in.env_is = rng() % 5 == 0;
         in.quad_fits = rng() % 4 != 0;
         c.finish();
-        const tpt::LaunchPlan pl = tpt::plan_launches(in);
+    }
+}
+
+static int check_plan_sweep(int n, unsigned seed) {
+    std::mt19937 rng(seed);
+    int planned = 0;
+    for (int i = 0; i < n; ++i) {
+        PlanCase c;
+        random_case(rng, c);
+        const tpt::LaunchPlan pl = tpt::plan_launches(c.in);
         if (pl.status != TPT_OK) continue;
         ++planned;
         if (const char* what = plan_broken(c, pl)) {
@@ -218,6 +230,135 @@ static int check_plan_sweep(int n, unsigned seed) {
         }
     }
     std::printf("ok plan sweep: %d of %d cases planned\n", planned, n);
+    return 0;
+}
+
+static const char* const kFamilyName[tpt::kTraceFamilies] = {"lane", "drain", "pair", "is", "quad", "ref", "is_pair", "ref_is"};
+
+static void print_key(const tpt::TraceKey& k) {
+    const tpt::TraceFamilyInfo& f = tpt::kTraceFamily[k.family];
+    std::printf("\"family\":\"%s\",\"env_is\":%d,\"lanes\":%d,\"deep\":%d,\"lights\":%d,\"mtl_lds\":%d,\"wide_ids\":%d,"
+                "\"noemit\":%d,\"legal\":%d,\"packed\":%u",
+                kFamilyName[k.family], f.env_is, f.lanes, k.deep, k.lights, k.mtl_lds, k.wide_ids, k.noemit,
+                tpt::trace_key_legal(k), tpt::trace_key_pack(k));
+}
+
+// "table": the family rows and the number of legal keys.  Else key=value,...:
+//   select=1, ref env_is pair quad drained lights mtls faces depth emitter  (what launch_trace sees; default: box-like,
+//             no lights, 5 materials, 1,932 faces, depth 8, an emitter)
+//   layout=1, family (a name above) lights mtl_lds wide_ids wgw (0: the family's) stack depth mtls max_slots max_levels
+static bool variant_case(const std::string& text) {
+    if (text == "table") {
+        std::printf("{\"families\":[");
+        for (int f = 0; f < tpt::kTraceFamilies; ++f) {
+            const tpt::TraceFamilyInfo& r = tpt::kTraceFamily[f];
+            std::printf("%s[\"%s\",%d,%d,%d,%d,%d,%d,%d,%d]", f ? "," : "", kFamilyName[f], r.wgw, r.waves, r.lds_waves, r.lanes,
+                        r.tile_w, r.tile_rows, r.env_is, r.ordered);
+        }
+        int legal = 0, round_trip = 0;
+        for (unsigned p = 0; p < (1u << tpt::kTraceKeyBits); ++p) {
+            legal += tpt::trace_key_legal(tpt::trace_key_unpack(p));
+            round_trip += tpt::trace_key_pack(tpt::trace_key_unpack(p)) == p;
+        }
+        std::printf("],\"public\":%d,\"legal_keys\":%d,\"round_trip\":%d}\n", tpt::kTracePublicFamilies, legal, round_trip);
+        return true;
+    }
+    tpt::TraceSelectIn in{false, false, false, false, false, 0, 5, 1932, 8, true};
+    tpt::TraceKey k{tpt::TF_LANE, false, false, false, false, false};
+    long long mode = 0, wgw = 0, stack = 0, depth = 8, mtls = 5, max_slots = -1, max_levels = -1;
+    size_t at = 0;
+    while (at < text.size()) {
+        const size_t end = std::min(text.find(',', at), text.size()), eq = text.find('=', at);
+        if (eq == std::string::npos || eq >= end) return false;
+        const std::string key = text.substr(at, eq - at), val = text.substr(eq + 1, end - eq - 1);
+        const long long v = std::atoll(val.c_str());
+        if (key == "select") mode = 1;
+        else if (key == "layout") mode = 2;
+        else if (key == "ref") in.ref_order = v != 0;
+        else if (key == "env_is") in.env_is = v != 0;
+        else if (key == "pair") in.pair = v != 0;
+        else if (key == "quad") in.quad = v != 0;
+        else if (key == "drained") in.drained = v != 0;
+        else if (key == "emitter") in.any_emitter = v != 0;
+        else if (key == "faces") in.n_faces = (int)v;
+        else if (key == "depth") in.max_depth = (int)(depth = v);
+        else if (key == "mtls") in.n_materials = (int)(mtls = v);
+        else if (key == "lights") in.n_lights = (int)v, k.lights = v != 0;
+        else if (key == "mtl_lds") k.mtl_lds = v != 0;
+        else if (key == "wide_ids") k.wide_ids = v != 0;
+        else if (key == "wgw") wgw = v;
+        else if (key == "stack") stack = v;
+        else if (key == "max_slots") max_slots = v;
+        else if (key == "max_levels") max_levels = v;
+        else if (key == "family") {
+            int f = 0;
+            while (f < tpt::kTraceFamilies && val != kFamilyName[f]) ++f;
+            if (f == tpt::kTraceFamilies) return false;
+            k.family = (tpt::TraceFamily)f;
+        } else {
+            return false;
+        }
+        at = end + 1;
+    }
+    if (mode == 1) {
+        const tpt::TraceSelection s = tpt::select_trace_variant(in);
+        if (s.error) {
+            std::printf("{\"error\":\"%s\"}\n", s.error);
+            return true;
+        }
+        std::printf("{");
+        print_key(s.key);
+        std::printf("}\n");
+        return true;
+    }
+    if (mode != 2) return false;
+    const tpt::TraceLds l = tpt::trace_lds_layout(k, wgw > 0 ? (int)wgw : tpt::kTraceFamily[k.family].wgw, (int)stack, (int)depth,
+                                                  (int)mtls, (size_t)max_slots, (size_t)max_levels);
+    std::printf("{\"bytes\":%zu,\"mtl_offset\":%d,\"stack_offset\":%d,\"rec_offset\":%d,\"stack_slots\":%d,\"rec_levels\":%d}\n",
+                l.bytes, l.mtl_offset, l.stack_offset, l.rec_offset, l.stack_slots, l.rec_levels);
+    return true;
+}
+
+// The planner and launch_trace agree: for every plan that succeeds, the variant the
+// kernel side selects for the plan's requests runs two lanes per pixel exactly when
+// the plan says so, and its tile has the plan's workgroup rows.
+static int check_variant_sweep(int n, unsigned seed) {
+    std::mt19937 rng(seed);
+    int planned = 0, families[tpt::kTraceFamilies] = {};
+    for (int i = 0; i < n; ++i) {
+        PlanCase c;
+        random_case(rng, c);
+        tpt::PlanInput& in = c.in;
+        static const int kMtls[] = {63, 64, 0x7ffd, 0x7ffe};
+        static const int kFaces[] = {6, 32768, 32769};
+        static const int kDepth[] = {1, 8, 9, 64};
+        if (rng() % 4 == 0) in.n_materials = kMtls[rng() % 4];
+        if (rng() % 4 == 0) in.n_faces = kFaces[rng() % 3];
+        if (rng() % 4 == 0) in.lanes_per_pixel = 4;
+        in.n_lights = in.n_lights ? 1 + (int)(rng() % 16) : 0;
+        in.max_depth = kDepth[rng() % 4];
+        in.any_emitter = rng() % 2 != 0;
+        const tpt::LaunchPlan pl = tpt::plan_launches(in);
+        if (pl.status != TPT_OK) continue;
+        const tpt::TraceSelection s = tpt::select_trace_variant(
+            {(in.flags & TPT_FLAG_REF_ORDER) != 0, in.env_is, pl.pair, pl.quad, pl.drained, in.n_lights, in.n_materials,
+             in.n_faces, in.max_depth, in.any_emitter});
+        // (quad_fits is the planner's word of trace_quad_fits, which refuses what the selection refuses)
+        if (s.error && pl.quad && tpt::rec_words(in.n_lights, in.n_materials) == 5) continue;
+        ++planned;
+        const tpt::TraceFamilyInfo& f = tpt::kTraceFamily[s.key.family];
+        ++families[s.key.family];
+        if (s.error || !tpt::trace_key_legal(s.key) || pl.pair_kernel != (f.lanes == 2) || pl.wg_rows != f.tile_rows ||
+            pl.quad != (f.lanes == 4)) {
+            std::printf("error: case %d: plan pair_kernel %d quad %d wg_rows %d, selected %s (%d lanes, %d rows)%s%s\n", i,
+                        pl.pair_kernel, pl.quad, pl.wg_rows, kFamilyName[s.key.family], f.lanes, f.tile_rows,
+                        s.error ? ": " : "", s.error ? s.error : "");
+            return 1;
+        }
+    }
+    std::printf("ok variant sweep: %d of %d cases planned; families", planned, n);
+    for (int f = 0; f < tpt::kTraceFamilies; ++f) std::printf(" %s=%d", kFamilyName[f], families[f]);
+    std::printf("\n");
     return 0;
 }
 
@@ -284,11 +425,21 @@ static int check_wide(int n, unsigned seed, int threads) {
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: host_check gltf|image FILE... | wide N SEED [THREADS] | plan CASE... | "
-                             "plan-sweep N SEED\n");
+                             "plan-sweep N SEED | variant CASE... | variant-sweep N SEED\n");
         return 2;
     }
     const std::string mode = argv[1];
     if (mode == "plan-sweep") return check_plan_sweep(std::atoi(argv[2]), argc > 3 ? (unsigned)std::atoi(argv[3]) : 1u);
+    if (mode == "variant-sweep")
+        return check_variant_sweep(std::atoi(argv[2]), argc > 3 ? (unsigned)std::atoi(argv[3]) : 1u);
+    if (mode == "variant") {
+        for (int i = 2; i < argc; ++i)
+            if (!variant_case(argv[i])) {
+                std::printf("error: bad case %s\n", argv[i]);
+                return 1;
+            }
+        return 0;
+    }
     if (mode == "plan") {
         for (int i = 2; i < argc; ++i) {
             PlanCase c;

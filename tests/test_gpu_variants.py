@@ -229,7 +229,7 @@ def test_material_ids_in_the_feature_buffers(dev):
 @pytest.mark.parametrize("order,lanes", [("ordered", 1), ("ordered", 0), ("reference", 1), ("reference", 0)])
 @pytest.mark.parametrize("n", V.RECORD_COUNTS)
 def test_record_word_boundary(dev, n, order, lanes):
-    """rec_words (device_api.hpp): the 2-word path records pack the material id in
+    """rec_words (trace_variant.hpp): the 2-word path records pack the material id in
     bits 0-14 and the probe's material in bits 15-29 with kNoProbe = 0x7fff, so
     from n_materials = 0x7ffe on the records have 5 words.  n = 0x7ffd is the last
     packed table: the emitter is id 0x7ffc and the Material() slot 0x7ffd.
@@ -332,7 +332,7 @@ def test_deep_lbvh_feature_buffers(dev, name):
 @pytest.mark.parametrize("order", sorted(ORDERS))
 @pytest.mark.parametrize("name", CHAINS)
 def test_deep_lbvh_frames(dev, name, order):
-    """k_trace on a depth-60 LBVH: trace_lds_bytes sizes the LDS stack from
+    """k_trace on a depth-60 LBVH: trace_lds_layout sizes the LDS stack from
     stack_depth (kRaysLdsSlots' counterpart in the render), the reference order
     defers a node per level, and in the _inf scenes (boxes_finite == 0) the ordered
     walk is the binary one at full depth."""

@@ -9,7 +9,10 @@ undefined behaviour aborts the harness with the sanitizer's report.
 
 The same harness runs the launch planner (host/launch_plan.cpp, the launch rules
 of tpt_render_frames): the test_plan_* cases pin the lane mode, the kernel knobs
-and the launch schedule it decides, which otherwise show only on a GPU.
+and the launch schedule it decides, which otherwise show only on a GPU.  The
+test_variant_* cases do the same for the k_trace variant space
+(common/trace_variant.hpp): the family table, the rule that picks a launch's
+variant, its agreement with the planner and the LDS layout.
 
 CPU only (the sanitizer build never travels to the GPU box)."""
 import base64
@@ -308,6 +311,120 @@ def test_plan_invariants_random_sweep(host_check):
     r = subprocess.run([host_check, "plan-sweep", "500", "20"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.startswith("ok plan sweep"), r.stdout + r.stderr[-3000:]
     assert int(r.stdout.split()[3]) >= 400   # (a few cases may end in an argument error)
+
+
+def _variant(exe, *cases):
+    """The k_trace variant space (common/trace_variant.hpp) through host_check.cpp
+    variant_case: one dict per case."""
+    return [json.loads(x) for x in run(exe, "variant", cases)]
+
+
+def _picked(v):
+    return (v["family"], v["deep"], v["lights"], v["mtl_lds"], v["wide_ids"], v["noemit"])
+
+
+def test_variant_family_table(host_check):
+    """What each family fixes, as the kernels were built before the table existed:
+    (waves per workgroup, waves per SIMD of the launch bounds, waves per SIMD of the
+    LDS budget, lanes per pixel, tile width, tile rows, env IS, ordered).  The first
+    six rows are tpt_debug_trace_wg_waves' families in its order.  The reference
+    order with env IS is compiled for 4 waves and budgets LDS for 5: recorded, not
+    fixed.  82 variants exist per build."""
+    t, = _variant(host_check, "table")
+    assert t["families"] == [["lane", 1, 5, 5, 1, 16, 16, 0, 1], ["drain", 1, 4, 5, 1, 16, 16, 0, 1],
+                             ["pair", 4, 4, 4, 2, 16, 8, 0, 1], ["is", 4, 4, 4, 1, 16, 16, 1, 1],
+                             ["quad", 4, 4, 4, 4, 8, 8, 0, 1], ["ref", 4, 5, 5, 1, 16, 16, 0, 0],
+                             ["is_pair", 4, 4, 4, 2, 16, 8, 1, 1], ["ref_is", 4, 4, 5, 1, 16, 16, 1, 0]]
+    assert (t["public"], t["legal_keys"], t["round_trip"]) == (6, 82, 256)
+
+
+def test_variant_selection(host_check):
+    """select_trace_variant, the one rule launch_trace and the planner share.  A case
+    starts box-like (no lights, 5 materials, 1,932 faces, depth 8, an emitter); the
+    tuples are (family, deep, 5-word records, materials in LDS, 32-bit ids, NOEMIT)."""
+    sel = lambda *cases: _variant(host_check, *("select=1," + c for c in cases))
+    box, drained = sel("pair=0", "drained=1")
+    assert _picked(box) == ("lane", 0, 0, 1, 0, 0) and _picked(drained) == ("drain", 0, 0, 1, 0, 0)
+    assert all(v["legal"] == 1 for v in (box, drained))
+    # ball-like: a delta light, no material table, no emitter / an emitter; pair is granted over drained
+    noemit, emit, one = sel("pair=1,drained=1,lights=1,mtls=0,faces=5000,emitter=0",
+                            "pair=1,lights=1,mtls=0,faces=5000", "pair=0,drained=1,lights=1,mtls=0,faces=5000")
+    assert _picked(noemit) == ("pair", 0, 1, 1, 0, 1) and noemit["lanes"] == 2
+    assert _picked(emit) == ("pair", 0, 1, 1, 0, 0)
+    assert _picked(one) == ("drain", 0, 1, 1, 0, 0)
+    # a pair request without shadow rays to hand off falls back to one lane
+    assert _picked(sel("pair=1")[0]) == ("lane", 0, 0, 1, 0, 0)
+    # env IS: 5-word records without lights, pair by request, never drained, before a quad request
+    is1, is2, isq = sel("env_is=1,drained=1", "env_is=1,pair=1,emitter=0", "env_is=1,quad=1")
+    assert _picked(is1) == ("is", 0, 1, 1, 0, 0) and (is1["env_is"], is1["lanes"]) == (1, 1)
+    assert _picked(is2) == ("is_pair", 0, 1, 1, 0, 1) and (is2["env_is"], is2["lanes"]) == (1, 2)
+    assert _picked(isq) == _picked(is1)
+    # the reference order: one general variant, whatever else is asked
+    ref, ref_is = sel("ref=1,pair=1,quad=1,drained=1,lights=1", "ref=1,env_is=1,pair=1,mtls=0,faces=6,depth=2")
+    assert _picked(ref) == ("ref", 1, 1, 0, 1, 0) and _picked(ref_is) == ("ref_is", 1, 1, 0, 1, 0)
+    # four lanes: one-lane records only
+    quad, quad_lit, quad_m = sel("quad=1,drained=1", "quad=1,lights=1", "quad=1,mtls=32766")
+    assert _picked(quad) == ("quad", 0, 0, 1, 0, 0) and quad["lanes"] == 4
+    assert quad_lit == quad_m == {"error": "four lanes per pixel need 2-word path records"}
+    # n_materials 0x7ffd / 0x7ffe: the packed records' last id; then 5 words and no pair
+    m0, m1, p0, p1, i0, i1 = sel("mtls=32765", "mtls=32766", "mtls=32765,pair=1,lights=1", "mtls=32766,pair=1,lights=1",
+                                 "mtls=32765,pair=1,env_is=1", "mtls=32766,pair=1,env_is=1")
+    assert _picked(m0) == ("lane", 0, 0, 0, 0, 0) and _picked(m1) == ("lane", 0, 1, 0, 0, 0)
+    assert _picked(p0) == ("pair", 0, 1, 0, 0, 0) and _picked(p1) == ("lane", 0, 1, 0, 0, 0)
+    assert _picked(i0) == ("is_pair", 0, 1, 0, 0, 0) and _picked(i1) == ("is", 0, 1, 0, 0, 0)
+    # TPT_MTL_LDS_MAX: 64 entries (n + the Material() slot) fit, 65 do not
+    assert [v["mtl_lds"] for v in sel("mtls=62", "mtls=63", "mtls=64")] == [1, 1, 0]
+    # 16-bit ids up to 65,535 nodes
+    assert [v["wide_ids"] for v in sel("faces=32768", "faces=32769", "faces=32768,pair=1,lights=1",
+                                       "faces=32769,pair=1,lights=1")] == [0, 1, 0, 1]
+    assert [v["deep"] for v in sel("depth=1", "depth=8", "depth=9", "depth=64")] == [0, 0, 1, 1]
+
+
+def test_variant_agrees_with_planner_random_sweep(host_check):
+    """500 seeded random cases (plan-sweep's, plus four-lane requests, material and
+    face counts on both sides of each rule, depths and emitters): for every plan
+    that succeeds, pair_kernel says the selected variant runs two lanes per pixel,
+    quad that it runs four, and wg_rows is its family's tile rows."""
+    r = subprocess.run([host_check, "variant-sweep", "500", "20"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.startswith("ok variant sweep"), r.stdout + r.stderr[-3000:]
+    assert int(r.stdout.split()[3]) >= 350
+    seen = dict(x.split("=") for x in r.stdout.split("families")[1].split())
+    assert all(int(n) > 0 for n in seen.values()), seen   # every family was reached
+
+
+# (case, (bytes, material offset, stack offset, record offset, LDS stack slots, LDS record levels)): rows of
+# the layout the kernels ran with before trace_lds_layout moved out of trace.hip, from a sweep in which the
+# two agreed everywhere (stack depth 1..160, max_depth 1..64, 0..200 materials, every variant, 1 / 2 / 4 waves,
+# with and without caps)
+LAYOUT_PINS = [
+    # box at one wave: the share of 5 waves per SIMD less the 512-byte slack; 26 of its 27 slots
+    ("family=lane,mtl_lds=1,wgw=1,stack=24,depth=8,mtls=5", (7680, 0, 256, 3584, 26, 8)),
+    ("family=lane,mtl_lds=1,wgw=4,stack=24,depth=8,mtls=5", (30976, 0, 256, 14592, 27, 8)),
+    ("family=lane,mtl_lds=1,wgw=1,stack=24,depth=64,mtls=5", (7680, 0, 256, 2048, 14, 11)),
+    ("family=drain,lights=1,mtl_lds=1,wgw=1,stack=24,depth=8,mtls=5", (7680, 0, 256, 2560, 18, 4)),
+    # the 5-word pair layout: records for half the lanes
+    ("family=pair,lights=1,mtl_lds=1,wgw=4,stack=31,depth=8,mtls=0", (38016, 0, 128, 17536, 34, 8)),
+    ("family=pair,lights=1,mtl_lds=1,wide_ids=1,wgw=4,stack=41,depth=32,mtls=0", (40576, 0, 128, 12416, 12, 11)),
+    # a deep tree: the stack's deepest slots spill to private memory
+    ("family=lane,mtl_lds=1,wgw=1,stack=120,depth=8,mtls=1", (7552, 0, 128, 3456, 26, 8)),
+    ("family=lane,mtl_lds=1,wgw=1,stack=120,depth=64,mtls=1", (7552, 0, 128, 1920, 14, 11)),
+    # the reference order with env IS: a fifth of the CU's LDS (32,768 B), though compiled for 4 waves
+    ("family=ref_is,lights=1,wide_ids=1,wgw=4,stack=40,depth=64,mtls=5", (32768, 0, 0, 12288, 12, 4)),
+    ("family=ref,lights=1,wide_ids=1,wgw=4,stack=40,depth=8,mtls=5", (32768, 0, 0, 12288, 12, 4)),
+    ("family=is,lights=1,mtl_lds=1,wgw=4,stack=31,depth=8,mtls=63", (40960, 0, 2048, 10240, 16, 6)),
+    ("family=is_pair,lights=1,wgw=4,stack=31,depth=8,mtls=64", (37888, 0, 0, 17408, 34, 8)),
+    ("family=quad,mtl_lds=1,wgw=4,stack=24,depth=8,mtls=5", (20224, 0, 256, 3840, 27, 8)),
+    ("family=quad,mtl_lds=1,wgw=4,stack=120,depth=64,mtls=5", (39168, 0, 256, 2304, 14, 18)),
+    ("family=lane,wide_ids=1,wgw=1,stack=41,depth=8,mtls=200", (7680, 0, 0, 3584, 14, 8)),
+    ("family=lane,mtl_lds=1,wgw=2,stack=24,depth=8,mtls=5,max_slots=20,max_levels=3", (8448, 0, 256, 5376, 20, 3)),
+]
+
+
+def test_variant_lds_layout_pinned(host_check):
+    got = _variant(host_check, *("layout=1," + c for c, _ in LAYOUT_PINS))
+    for (case, want), g in zip(LAYOUT_PINS, got):
+        assert (g["bytes"], g["mtl_offset"], g["stack_offset"], g["rec_offset"], g["stack_slots"],
+                g["rec_levels"]) == want, case
 
 
 def test_wide_tree_pool_under_tsan():

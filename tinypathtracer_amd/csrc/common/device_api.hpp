@@ -128,13 +128,6 @@ struct TraceArgs {
     unsigned long long* debug_waves;     // phase-profiling builds: 8 words per wave (null: off)
 };
 
-// Path-record words per bounce (k_trace): 2 when the scene has no delta lights
-// (atten; material | probe material | p-kind packed), else 5 (atten; material |
-// p-kind; direct term x3).  The packed form needs material ids below 0x7fff.
-__host__ __device__ inline int rec_words(int n_lights, int n_materials) {
-    return (n_lights > 0 || n_materials >= 0x7ffe) ? 5 : 2;
-}
-
 struct ResolveArgs {
     const float* accum;
     float* radiance;                     // device, W*H*3 (nullable)

@@ -74,7 +74,7 @@ tpt_status render_wavefront(tpt_scene* s, const tpt::TraceArgs& a, const tpt_par
     hipStream_t st = s->stream;
     const bool ordered = !(p->flags & TPT_FLAG_REF_ORDER);
     // the megakernel's record layout: 5 words with delta lights, env IS or the reference order
-    const bool lights = !ordered || a.env_is || tpt::rec_words(s->n_lights, s->n_materials) == 5;
+    const bool lights = tpt::trace_five_words(!ordered, a.env_is != 0, s->n_lights, s->n_materials);
     tpt::WfArgs w{};
     w.t = a;
     w.t.samples = p->spp;
@@ -388,6 +388,8 @@ tpt_status tpt_render_frames(tpt_scene* s, const tpt_env* env, const tpt_camera*
     pin.resident_lanes = s->resident_lanes;
     pin.env_is = a.env_is != 0;
     pin.quad_fits = tpt::trace_quad_fits(a);
+    pin.max_depth = p->max_depth;
+    pin.any_emitter = s->any_emitter != 0;
     const tpt::LaunchPlan plan = tpt::plan_launches(pin);
     if (plan.status != TPT_OK) return fail(plan.status, plan.message);
     a.pair = plan.pair ? 1 : 0;

@@ -40,12 +40,6 @@ LaunchPlan plan_launches(const PlanInput& in) {
     // 4.91 -> 6.65 Grays/s); the kernel falls back to one lane per pixel otherwise
     // (A15 env IS: the env shadow ray of every diffuse bounce is the side lane's job too)
     pl.pair = in.lanes_per_pixel == 2 || (in.lanes_per_pixel == 0 && lit);
-    // Refill: a wave leaves its traversal loop to shade once fewer than this many
-    // lanes still traverse.  A shading pass costs ~5 node steps, so passes are
-    // batched; in pair mode half the lanes (the side lanes) are mostly idle and
-    // the threshold scales down with them (C3 1080p 4096 spp: 24 -> 5.88,
-    // 8 -> 6.44, 2..12 within 6.2-6.6 Grays/s; C2 single-lane: 16-24 best).
-    pl.pair_kernel = pl.pair && lit && (in.n_materials + 1) < 0x7fff && !ref_order;
     // Four lanes per pixel ("Four lanes per ray"): every lane
     // of a quad runs the pixel's path, each 4-wide visit split over them -- the
     // one-lane kernel logic, so no delta lights, env IS or reference order, and the
@@ -63,20 +57,27 @@ LaunchPlan plan_launches(const PlanInput& in) {
     if (in.lanes_per_pixel == 4 && !quad_ok && !wavefront)
         return plan_error("lanes_per_pixel 4: scenes without delta lights, no env IS, ordered traversal, stacks in LDS");
     pl.quad = in.lanes_per_pixel == 4 || (in.lanes_per_pixel == 0 && launch_pix <= resident && quad_ok);
-    // the trace grid's y extent is (band row blocks) x frames: 8-row workgroups in
-    // pair mode, 16 otherwise (launch_trace)
-    pl.wg_rows = (pl.pair_kernel || pl.quad) ? 8 : 16;
-    if (!wavefront && (size_t)((bh + pl.wg_rows - 1) / pl.wg_rows) * nf > 65535)
-        return plan_error("frame batch too large for one launch");
     // A launch with fewer pixels than about twice the chip's resident lanes
     // (resident_lanes; strong-scaled frames, small images) is bound by its
     // heaviest waves' chains, not by throughput: batch the shading passes harder
     // (C2 rank 0 of 8: refill 24 318 ms, 4: 276 ms; rank 0 of 4: flat).
     pl.drained = launch_pix < 2.0 * resident;   // latency-oriented kernel variants (trace.hip DRAIN)
+    // what launch_trace will pick, by its own rule (a request it refuses was reported above)
+    const TraceKey variant = select_trace_variant({ref_order, in.env_is, pl.pair, pl.quad, pl.drained, in.n_lights,
+                                                   in.n_materials, in.n_faces, in.max_depth, in.any_emitter}).key;
+    pl.pair_kernel = kTraceFamily[variant.family].lanes == 2;
+    pl.wg_rows = kTraceFamily[variant.family].tile_rows;   // the trace grid's y extent is (band row blocks) x frames
+    if (!wavefront && (size_t)((bh + pl.wg_rows - 1) / pl.wg_rows) * nf > 65535)
+        return plan_error("frame batch too large for one launch");
     // Shallow trees (few triangles) make a traversal short against a shading
     // pass, so passes are batched harder there: tir (6 triangles) refill 16
     // 84.6 Grays/s vs 24 72.6-78.9; box (1,932) 16 = 24; C5 (131 K) 16 -3 %.
     const int full = in.n_faces <= 4096 ? 16 : 24;
+    // Refill: a wave leaves its traversal loop to shade once fewer than this many
+    // lanes still traverse.  A shading pass costs ~5 node steps, so passes are
+    // batched; in pair mode half the lanes (the side lanes) are mostly idle and
+    // the threshold scales down with them (C3 1080p 4096 spp: 24 -> 5.88,
+    // 8 -> 6.44, 2..12 within 6.2-6.6 Grays/s; C2 single-lane: 16-24 best).
     // Pair mode (round 3, after the 4-wave pair variants and the fp32-bounded env
     // lookup; C3 1080p 4096 spp, Mrays/s): refill 8 7,711, 6 7,720, 4 7,790-7,942,
     // 3 7,911-7,934, 2 7,860-7,983 -> 3; with env IS (the side lane's env sample

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "../common/trace_variant.hpp"
 #include "tpt.h"
 
 namespace tpt {
@@ -38,6 +39,8 @@ struct PlanInput {
     uint64_t resident_lanes = 0;
     bool env_is = false;                // TPT_FLAG_ENV_IS and an env with a non-empty distribution
     bool quad_fits = false;             // tpt::trace_quad_fits of the call's TraceArgs
+    int32_t max_depth = 8;              // tpt_params
+    bool any_emitter = true;            // some triangle of the scene emits
 };
 
 struct PlanLaunch {

@@ -23,9 +23,11 @@
 //    16-bit ids when the tree allows; deepest slots private when it does not
 //    fit) and as many path-record levels as fit (2 words per bounce without
 //    delta lights); deeper records in private memory;
-//  * kernel variants by template: no-lights / delta lights, material table in
-//    LDS or not, 16/32-bit stack ids, record depth 8/64; the reference order
-//    and the opt-in env importance sampling have one general variant each;
+//  * kernel variants by template, one TraceVariant descriptor each
+//    (common/trace_variant.hpp): a family (one lane per pixel, drained, pair,
+//    env IS with one or two lanes, four lanes, the reference order) and in it
+//    record depth 8/64, 2-/5-word records, material table in LDS or not,
+//    16/32-bit stack ids, emitter-free pair kernels; select_trace_variant picks;
 //  * triangles are pre-gathered (v0, e1, e2, fid: three 16-B loads).
 #include <array>
 #include <map>
@@ -103,20 +105,17 @@ __device__ __noinline__ void verify_ray(const TraceArgs& a, const Trav& r, int p
 // each level's direct term is the same sum in the same order: the image is
 // bit-identical.  A pixel's sample chain then pays one traversal per bounce
 // instead of 1 + lights, which is what bounds tail-heavy frames (C3).
-template <int MAXD, bool ORDERED, bool LIGHTS, bool MTL_LDS, typename StackT, bool ENVIS = false, bool PAIR = false,
-          bool DRAIN = false, bool QUAD = false, bool NOEMIT = false>
-__global__ __launch_bounds__((64 * trace_wgw<ORDERED, ENVIS, PAIR, DRAIN, QUAD>()),
-                             ENVIS ? TPT_TRACE_WAVES_IS
-                                   : (PAIR ? TPT_TRACE_WAVES_PAIR
-                                           : (QUAD ? TPT_TRACE_WAVES_QUAD
-                                                   : (DRAIN ? TPT_TRACE_WAVES_DRAIN : TPT_TRACE_WAVES))))
-void k_trace(TraceArgs a) {
-    static_assert(!PAIR || (ORDERED && LIGHTS), "pair mode: ordered variants with 5-word records");
-    static_assert(!QUAD || (ORDERED && !LIGHTS && !PAIR && !ENVIS && !DRAIN), "four lanes per pixel: one-lane logic");
+// V: the variant, a TraceVariant (trace_variant.hpp asserts the legal combinations).
+template <class V>
+__global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
+    constexpr int MAXD = V::MAXD;
+    constexpr bool ORDERED = V::ORDERED, LIGHTS = V::LIGHTS, MTL_LDS = V::MTL_LDS, ENVIS = V::ENVIS, PAIR = V::PAIR,
+                   DRAIN = V::DRAIN, QUAD = V::QUAD, NOEMIT = V::NOEMIT;
+    using StackT = typename V::StackT;
     // A tile is four waves (2 x 2 sub-tiles), rendered by 4 / WGW workgroups of WGW
     // waves each, adjacent in grid x: block x = tile * (4 / WGW) + part.  The tiles
     // are dispatched in the order 4-wave workgroups were.
-    constexpr int WGW = trace_wgw<ORDERED, ENVIS, PAIR, DRAIN, QUAD>(), NB = 4 / WGW, ROW = 64 * WGW;
+    constexpr int WGW = V::WGW, NB = 4 / WGW, ROW = 64 * WGW;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     // grid y interleaves the frames of a batch: consecutive workgroups render the
@@ -1072,80 +1071,11 @@ hipError_t launch_hot_kat(int op, uint32_t n, const float* in, float* out, hipSt
     return hipGetLastError();
 }
 
-#ifndef TPT_MTL_LDS_MAX
-#define TPT_MTL_LDS_MAX 2048
-#endif
-constexpr size_t kLdsMtlMax = TPT_MTL_LDS_MAX;   // material tables up to 64 entries go to LDS
-constexpr size_t kLdsSlack = 512;   // bytes per wave left free in workgroups of fewer than four waves
-
-// A launch's LDS layout request: the record words per level, the stack's id size,
-// where the material table lives, the lane mode, the variant's waves per SIMD.
-struct LdsSpec {
-    int words;
-    size_t elem;
-    bool mtl_lds;
-    bool pair;
-    bool quad;
-    int waves;
-};
-
-// LDS per workgroup of `wgw` waves: [material table][traversal stack][path records],
-// within the workgroup's share of the CU's 160 KiB when the CU holds `waves` waves
-// per SIMD (a 4-wave workgroup's share rounded down to 256 B, times wgw / 4).
-// max_slots / max_levels cap the stack slots and record levels (fit_lds).
-size_t trace_lds_bytes(TraceArgs& a, const LdsSpec& sp, int wgw, size_t max_slots = (size_t)-1,
-                       size_t max_levels = (size_t)-1) {
-    // Priorities (measured on box): the whole stack (a
-    // stack capped at 23 of its 40 slots cost 7 %), then path records up to
-    // max_depth (records of long paths in private memory slow the heaviest
-    // tiles).
-    size_t lds_budget = ((163840 / (size_t)sp.waves) & ~(size_t)255) * (size_t)wgw / 4;
-    // Smaller workgroups leave kLdsSlack bytes per wave unused.  A layout that fills the
-    // CU's LDS exactly (box at one wave: 20 x 8,192 B) was resident only four waves per
-    // SIMD deep on the device although the runtime's occupancy query (fit_lds) answered
-    // five: C2 -2.8 %; with 512 B per wave of slack +2.6 % ("Workgroup shape").
-    if (wgw < 4) lds_budget -= kLdsSlack * (size_t)wgw;
-    const size_t row = 64 * (size_t)wgw;   // the workgroup's lanes
-    const size_t mtl_bytes = sp.mtl_lds ? ((size_t)(a.n_materials + 1) * 2 * 16 + 127) / 128 * 128 : 0;
-    a.mtl_in_lds = sp.mtl_lds ? 1 : 0;
-    a.lds_mtl_offset = 0;
-    const size_t budget = lds_budget - mtl_bytes;
-    const size_t slot = sp.quad ? row / 4 * sp.elem : row * sp.elem;   // (quad: four slots per row of lanes)
-    const size_t level = (size_t)sp.words * (sp.pair ? row / 2 : row) * sizeof(float);
-    // The whole stack (capacity + 3 spare slots for the unconditional 4-wide
-    // pushes) when the path records of max_depth levels fit beside it.  Else
-    // the records first: the ordered walk rarely goes deep (C5: 99 % of visits
-    // find <= 5 entries), so the stack keeps as many slots as the records leave,
-    // at least 12, and deeper entries spill to private memory.  Measured on C5
-    // (44 slots of 32-bit ids): 27 stack slots + 2 record levels 7.63 Grays/s,
-    // 19 + 6: 7.97, 12 + 8: 8.20.
-    size_t slots = std::min((size_t)a.stack_depth + 3, max_slots);
-    const size_t want = std::min(std::min<size_t>((size_t)a.max_depth, (budget - 12 * slot) / level), max_levels);
-    if (slots * slot + want * level > budget)
-        slots = std::min(slots, std::max<size_t>(12, ((budget - want * level) / slot) & ~(size_t)1));   // even
-    // the region holds a whole number of slot pairs (quad: of 4-slot rows), rounded to 16 bytes
-    const size_t stack = sp.quad ? ((slots + 3) / 4 * 4 * slot + 15) / 16 * 16
-                                 : ((slots + 1) / 2 * 2 * slot + 15) / 16 * 16;
-    size_t levels = (budget - stack) / level;
-    levels = std::min(std::min(levels, (size_t)a.max_depth), max_levels);
-    a.lds_nodes = 0;
-    a.lds_nodes_offset = (int)mtl_bytes;
-    a.stack_lds_slots = (int)slots;
-    a.lds_stack_offset = (int)mtl_bytes;
-    a.lds_rec_offset = (int)(mtl_bytes + stack);
-    a.rec_lds_levels = (int)levels;
-    return mtl_bytes + stack + levels * level;
-}
-
-// One launch_trace call: the grid in tiles, the LDS request, and whether it only
-// asks what would run (dry: trace_quad_fits).
+// One launch_trace call; `dry` only asks what would run (trace_quad_fits).
 struct LaunchCtx {
-    dim3 tiles;
-    LdsSpec lds;
     hipStream_t s;
     bool dry;
     int32_t* shape;
-    hipError_t err;
 };
 
 // The layout of a variant at one scene / depth, settled once: the caps under which
@@ -1159,10 +1089,10 @@ struct LdsFit {
 // workgroup's share exactly (box at one wave: 8,192 B = 163,840 / 20, no slack), and
 // the compiler's occupancy remark rounds, so the runtime is asked: workgroups of
 // this kernel, size and LDS per CU.  Fewer than fill the CU's wave slots: the layout
-// shrinks by trace_lds_bytes' priority -- stack slots (never below 12), then record
+// shrinks by trace_lds_layout's priority -- stack slots (never below 12), then record
 // levels -- until they fit.
 template <typename K>
-static LdsFit fit_lds(K kern, const TraceArgs& a_in, const LdsSpec& sp, int wgw, int waves) {
+static LdsFit fit_lds(K kern, const TraceArgs& a, const TraceKey& k, int wgw, int waves) {
     LdsFit f{(size_t)-1, (size_t)-1, 0, 4 * waves / wgw};
     int regs = 0;   // what registers alone allow (never more than the launch bounds asked for)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&regs, kern, 64 * wgw, 0) != hipSuccess) {
@@ -1171,29 +1101,22 @@ static LdsFit fit_lds(K kern, const TraceArgs& a_in, const LdsSpec& sp, int wgw,
     }
     const int target = std::min(f.need, regs);
     for (;;) {
-        TraceArgs a = a_in;
-        const size_t lds = trace_lds_bytes(a, sp, wgw, f.max_slots, f.max_levels);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&f.resident, kern, 64 * wgw, lds) != hipSuccess) {
+        const TraceLds l = trace_lds_layout(k, wgw, a.stack_depth, a.max_depth, a.n_materials, f.max_slots, f.max_levels);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&f.resident, kern, 64 * wgw, l.bytes) != hipSuccess) {
             (void)hipGetLastError();
             return f;
         }
         if (f.resident >= target) return f;
-        if (a.stack_lds_slots > 12) f.max_slots = std::max<size_t>(12, (size_t)(a.stack_lds_slots - 1) & ~(size_t)1);
-        else if (a.rec_lds_levels > 0) f.max_levels = (size_t)a.rec_lds_levels - 1;
+        if (l.stack_slots > 12) f.max_slots = std::max<size_t>(12, (size_t)(l.stack_slots - 1) & ~(size_t)1);
+        else if (l.rec_levels > 0) f.max_levels = (size_t)l.rec_levels - 1;
         else return f;
     }
 }
 
-template <int MAXD, bool ORDERED, bool LIGHTS, bool MTL_LDS, typename StackT, bool ENVIS = false, bool PAIR = false,
-          bool DRAIN = false, bool QUAD = false, bool NOEMIT = false>
-static void launch_one(const TraceArgs& a_in, LaunchCtx& c) {
-    constexpr int WGW = trace_wgw<ORDERED, ENVIS, PAIR, DRAIN, QUAD>();
-    // the variant's waves per SIMD (k_trace's __launch_bounds__)
-    constexpr int kWaves = ENVIS ? TPT_TRACE_WAVES_IS
-                                 : (PAIR ? TPT_TRACE_WAVES_PAIR
-                                         : (QUAD ? TPT_TRACE_WAVES_QUAD
-                                                 : (DRAIN ? TPT_TRACE_WAVES_DRAIN : TPT_TRACE_WAVES)));
-    const auto kern = k_trace<MAXD, ORDERED, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, QUAD, NOEMIT>;
+template <class V>
+static hipError_t launch_one(const TraceArgs& a_in, const LaunchCtx& c) {
+    constexpr int WGW = V::WGW;
+    const auto kern = k_trace<V>;
     // once per variant and layout input, not per launch
     static std::mutex mu;
     static std::map<std::array<int, 3>, LdsFit> fits;
@@ -1202,158 +1125,73 @@ static void launch_one(const TraceArgs& a_in, LaunchCtx& c) {
     {
         std::lock_guard<std::mutex> lock(mu);
         auto it = fits.find(key);
-        if (it == fits.end()) it = fits.emplace(key, fit_lds(kern, a_in, c.lds, WGW, kWaves)).first;
+        if (it == fits.end()) it = fits.emplace(key, fit_lds(kern, a_in, V::key, WGW, V::WAVES)).first;
         f = it->second;
     }
     TraceArgs a = a_in;
-    const size_t lds = trace_lds_bytes(a, c.lds, WGW, f.max_slots, f.max_levels);
+    // the grid in tiles of four waves: 16x16 pixels (pair mode 16x8, four lanes per pixel 8x8)
+    const unsigned nfr = (unsigned)(a.n_frames > 0 ? a.n_frames : 1);
+    const dim3 tiles((a.width + V::fam.tile_w - 1) / V::fam.tile_w,
+                     ((a.band_height + V::fam.tile_rows - 1) / V::fam.tile_rows) * nfr);
+    // the XCD-run remap is a permutation of a row's tiles only if runs tile the row's tiles / 8
+    // (16-pixel columns; four lanes per pixel keep the round-robin deal)
+    if (a.xcd_run > 0 && (V::QUAD || tiles.x % 8 != 0 || (tiles.x / 8) % (unsigned)a.xcd_run != 0)) a.xcd_run = 0;
+    const TraceLds l = trace_lds_layout(V::key, WGW, a.stack_depth, a.max_depth, a.n_materials, f.max_slots, f.max_levels);
+    a.mtl_in_lds = V::MTL_LDS ? 1 : 0;
+    a.lds_mtl_offset = l.mtl_offset;
+    a.lds_nodes = 0;
+    a.lds_nodes_offset = l.stack_offset;
+    a.lds_stack_offset = l.stack_offset;
+    a.stack_lds_slots = l.stack_slots;
+    a.lds_rec_offset = l.rec_offset;
+    a.rec_lds_levels = l.rec_levels;
     if (c.shape) {
         c.shape[0] = WGW;
         c.shape[1] = f.resident;
         c.shape[2] = f.need;
-        c.shape[3] = (int32_t)lds;
-        c.shape[4] = a.stack_lds_slots;
-        c.shape[5] = a.rec_lds_levels;
+        c.shape[3] = (int32_t)l.bytes;
+        c.shape[4] = l.stack_slots;
+        c.shape[5] = l.rec_levels;
     }
     // four lanes per pixel: the quads' stacks must lie in LDS whole
-    if (QUAD && a.stack_lds_slots < a.stack_depth + 3) {
-        c.err = hipErrorInvalidValue;
-        return;
-    }
-    if (c.dry) return;
-    hipLaunchKernelGGL(kern, dim3(c.tiles.x * (4 / WGW), c.tiles.y), dim3(64 * WGW), lds, c.s, a);
-    c.err = hipGetLastError();
-}
-// four lanes per pixel (a.quad): one-lane logic without delta lights
-template <bool MTL_LDS, typename StackT>
-static void launch_quad(const TraceArgs& a, LaunchCtx& c) {
-    if (a.max_depth <= 8) launch_one<8, true, false, MTL_LDS, StackT, false, false, false, true>(a, c);
-    else launch_one<64, true, false, MTL_LDS, StackT, false, false, false, true>(a, c);
+    if (V::QUAD && l.stack_slots < a.stack_depth + 3) return hipErrorInvalidValue;
+    if (c.dry) return hipSuccess;
+    hipLaunchKernelGGL(kern, dim3(tiles.x * (4 / WGW), tiles.y), dim3(64 * WGW), l.bytes, c.s, a);
+    return hipGetLastError();
 }
 
-// PAIR: pair mode (delta-light scenes only).  NOEMIT (pair variants): no triangle
-// emits, so every direct probe ends in the shading pass and the probe's
-// traversal phases are compiled out -- the pair kernel's registers for C3's and
-// C3 + IS's ball.
-template <bool LIGHTS, bool MTL_LDS, typename StackT, bool PAIR = false, bool ENVIS = false, bool DRAIN = false>
-static void launch_ordered_d(const TraceArgs& a, LaunchCtx& c) {
-    if constexpr (PAIR) {
-        if (!a.any_emitter) {
-            if (a.max_depth <= 8)
-                launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, false, true>(a, c);
-            else
-                launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN, false, true>(a, c);
-            return;
-        }
+// The runtime key's instantiation: a descent over the packed key's bits that ends in
+// launch_one of that variant.  Exactly the legal keys exist as kernels.
+template <unsigned K = 0, int BIT = 0>
+static hipError_t launch_key(unsigned packed, const TraceArgs& a, const LaunchCtx& c) {
+    if constexpr (BIT < kTraceKeyBits) {
+        return (packed >> BIT & 1) ? launch_key<(K | 1u << BIT), BIT + 1>(packed, a, c) : launch_key<K, BIT + 1>(packed, a, c);
+    } else if constexpr (trace_key_legal(trace_key_unpack(K))) {
+        constexpr TraceKey k = trace_key_unpack(K);
+        return launch_one<TraceVariant<k.family, k.deep ? 64 : 8, k.lights, k.mtl_lds,
+                                std::conditional_t<k.wide_ids, int, uint16_t>, k.noemit>>(a, c);
+    } else {
+        return hipErrorInvalidValue;
     }
-    if (a.max_depth <= 8) launch_one<8, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN>(a, c);
-    else launch_one<64, true, LIGHTS, MTL_LDS, StackT, ENVIS, PAIR, DRAIN>(a, c);
-}
-// DRAIN variants (parked triangles prefetched) for launches that cannot fill the
-// chip (a.drained), one-lane-per-pixel ordered kernels only
-template <bool LIGHTS, bool MTL_LDS, typename StackT, bool PAIR = false, bool ENVIS = false>
-static void launch_ordered(const TraceArgs& a, LaunchCtx& c) {
-    if constexpr (!PAIR && !ENVIS) {
-        if (a.drained) {   // (the one-lane variants' LDS budget: the layout does not depend on the launch size)
-            launch_ordered_d<LIGHTS, MTL_LDS, StackT, PAIR, ENVIS, true>(a, c);
-            return;
-        }
-    }
-    launch_ordered_d<LIGHTS, MTL_LDS, StackT, PAIR, ENVIS, false>(a, c);
 }
 
 // waves per SIMD the one-lane trace variants are built for (__launch_bounds__):
 // with the device's CU count, the resident lanes the host's launch rules use
-int trace_waves_per_simd() { return TPT_TRACE_WAVES; }
+int trace_waves_per_simd() { return kTraceFamily[TF_LANE].waves; }
 
 // the build's workgroup shape per family, in tpt_debug_trace_wg_waves' order
-int trace_family_wgw(int family) {
-    static const int kWgw[6] = {trace_wgw<true, false, false, false, false>(), trace_wgw<true, false, false, true, false>(),
-                                trace_wgw<true, false, true, false, false>(),  trace_wgw<true, true, false, false, false>(),
-                                trace_wgw<true, false, false, false, true>(),  trace_wgw<false, false, false, false, false>()};
-    return family >= 0 && family < 6 ? kWgw[family] : 0;
-}
-
-// f(MTL_LDS as std::bool_constant, StackT as a value) for the launch's material-table
-// placement and node-id width
-template <typename F>
-static void for_mtl_stack(bool mtl_lds, bool small, F f) {
-    if (mtl_lds) {
-        if (small) f(std::true_type{}, uint16_t{});
-        else f(std::true_type{}, int{});
-    } else {
-        if (small) f(std::false_type{}, uint16_t{});
-        else f(std::false_type{}, int{});
-    }
-}
+int trace_family_wgw(int family) { return family >= 0 && family < kTracePublicFamilies ? kTraceFamily[family].wgw : 0; }
 
 static hipError_t launch_trace_impl(const TraceArgs& a_in, hipStream_t s, bool dry, int32_t* shape) {
-    TraceArgs a = a_in;
-    const unsigned nfr = (unsigned)(a.n_frames > 0 ? a.n_frames : 1);
-    // the grid in tiles of four waves: 16x16 pixels (pair mode 16x8, four lanes per pixel 8x8)
-    LaunchCtx c{dim3((a.width + 15) / 16, ((a.band_height + 15) / 16) * nfr), LdsSpec{}, s, dry, shape, hipSuccess};
-    // the XCD-run remap is a permutation of a row's tiles only if runs tile the row's tiles / 8
-    if (a.xcd_run > 0 && (c.tiles.x % 8 != 0 || (c.tiles.x / 8) % (unsigned)a.xcd_run != 0)) a.xcd_run = 0;
-    if (a.flags & TPT_FLAG_REF_ORDER) {
-        // the reference's visit order (tests, diagnostics): one general variant
-        c.lds = LdsSpec{5, sizeof(int), false, false, false, TPT_TRACE_WAVES};
-        if (a.env_is) launch_one<64, false, true, false, int, true>(a, c);
-        else launch_one<64, false, true, false, int>(a, c);
-        return c.err;
-    }
-    const bool small = (2 * (size_t)a.n_faces - 1) <= 65535;
-    const bool mtl_lds = (size_t)(a.n_materials + 1) * 2 * sizeof(float4) <= kLdsMtlMax;
-    const size_t elem = small ? 2 : 4;
-    if (a.env_is) {
-        // opt-in env next-event estimation (A15): variants of their own (the
-        // delta-light machinery: 5-word records), so the others stay lean; pair
-        // mode hands each diffuse bounce's env shadow ray (and its delta lights'
-        // rays) to the side lane
-        const bool pair_is = a.pair && (a.n_materials + 1) < (int)kNoProbe;
-        if (pair_is) c.tiles.y = ((a.band_height + 7) / 8) * nfr;
-        c.lds = LdsSpec{5, elem, mtl_lds, pair_is, false, TPT_TRACE_WAVES_IS};
-        for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
-            if (pair_is) launch_ordered<true, decltype(m)::value, decltype(st), true, true>(a, c);
-            else launch_ordered<true, decltype(m)::value, decltype(st), false, true>(a, c);
-        });
-        return c.err;
-    }
-    const bool lights = rec_words(a.n_lights, a.n_materials) == 5;
-    if (a.quad) {
-        // four lanes per pixel: 8x8-pixel tiles (the host checked lights == 0)
-        if (lights) return hipErrorInvalidValue;
-        c.tiles = dim3((a.width + 7) / 8, ((a.band_height + 7) / 8) * nfr);
-        a.xcd_run = 0;
-        c.lds = LdsSpec{2, elem, mtl_lds, false, true, TPT_TRACE_WAVES_QUAD};
-        for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
-            launch_quad<decltype(m)::value, decltype(st)>(a, c);
-        });
-        return c.err;
-    }
-    // pair mode: delta lights (shadow rays to hand off), packed probe ids
-    const bool pair = a.pair && lights && a.n_lights > 0 && (a.n_materials + 1) < (int)kNoProbe;
-    if (pair) {
-        c.tiles.y = ((a.band_height + 7) / 8) * nfr;   // 16x8 pixels per tile
-        c.lds = LdsSpec{5, elem, mtl_lds, true, false, TPT_TRACE_WAVES_PAIR};
-        for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
-            launch_ordered<true, decltype(m)::value, decltype(st), true>(a, c);
-        });
-        return c.err;
-    }
-    c.lds = LdsSpec{lights ? 5 : 2, elem, mtl_lds, false, false, TPT_TRACE_WAVES};
-    for_mtl_stack(mtl_lds, small, [&](auto m, auto st) {
-        if (lights) launch_ordered<true, decltype(m)::value, decltype(st)>(a, c);
-        else launch_ordered<false, decltype(m)::value, decltype(st)>(a, c);
-    });
-    return c.err;
+    const TraceSelection sel = select_trace_variant(
+        {(a_in.flags & TPT_FLAG_REF_ORDER) != 0, a_in.env_is != 0, a_in.pair != 0, a_in.quad != 0, a_in.drained != 0,
+         a_in.n_lights, a_in.n_materials, a_in.n_faces, a_in.max_depth, a_in.any_emitter != 0});
+    return sel.error ? hipErrorInvalidValue : launch_key(trace_key_pack(sel.key), a_in, LaunchCtx{s, dry, shape});
 }
 
-hipError_t launch_trace(const TraceArgs& a, hipStream_t s, int32_t* shape) {
-    return launch_trace_impl(a, s, false, shape);
-}
+hipError_t launch_trace(const TraceArgs& a, hipStream_t s, int32_t* shape) { return launch_trace_impl(a, s, false, shape); }
 
 bool trace_quad_fits(const TraceArgs& a_in) {
-    if (rec_words(a_in.n_lights, a_in.n_materials) != 2) return false;
     TraceArgs a = a_in;
     a.quad = 1;
     a.env_is = 0;

@@ -14,6 +14,7 @@
 #include "../common/rng.hpp"
 #include "../common/tri_rec.hpp"
 #include "../common/tpt_math.hpp"
+#include "../common/trace_variant.hpp"
 #include "tpt.h"
 
 #ifndef TPT_FAST
@@ -33,65 +34,8 @@
 #ifndef TPT_LEAF_KP
 #define TPT_LEAF_KP 24    // run the triangle branch once this many lanes hold a parked leaf (or a.leaf_kb are blocked)
 #endif
-#ifndef TPT_TRACE_WAVES
-#define TPT_TRACE_WAVES 5   // min waves per SIMD requested from the register allocator
-#endif
-
-#ifndef TPT_TRACE_WAVES_IS
-// The env importance-sampling variants (A15) carry the env sample's state across
-// the shading pass: at 96 VGPRs (5 waves) they spilled 121 VGPRs to scratch;
-// 4 waves give them 128.
-#define TPT_TRACE_WAVES_IS 4
-#endif
-#ifndef TPT_TRACE_WAVES_PAIR
-// pair-mode (delta-light) variants: at 5 waves (96 VGPRs) they spilled 38 VGPRs;
-// C3 4096 spp, 4 waves: +6.4 % (7,220 -> 7,685 Mrays/s, 2 interleaved reps)
-#define TPT_TRACE_WAVES_PAIR 4
-#endif
-#ifndef TPT_TRACE_WAVES_DRAIN
-// DRAIN variants (launches that cannot fill the chip: a few waves per SIMD anyway)
-#define TPT_TRACE_WAVES_DRAIN 4
-#endif
-#ifndef TPT_TRACE_WAVES_QUAD
-#define TPT_TRACE_WAVES_QUAD 4   // four lanes per pixel (k_trace QUAD)
-#endif
-
-// WGW: the waves of a k_trace workgroup (1, 2 or 4; block size 64 * WGW), one
-// shape per variant family ("Workgroup shape").  A wave's
-// tile does not depend on it.  A workgroup's LDS and its waves' slots are handed
-// on only when its last wave ends, so a smaller workgroup returns the slots of
-// waves that end before their tile's siblings sooner.
-// -DTPT_WG_WAVES=N (EXTRA) builds every family at N waves: 4 is the shape before
-// WGW existed, for an A/B library from the same tree.
-#ifdef TPT_WG_WAVES
-#define TPT_WGW_LANE TPT_WG_WAVES
-#define TPT_WGW_DRAIN TPT_WG_WAVES
-#define TPT_WGW_PAIR TPT_WG_WAVES
-#define TPT_WGW_IS TPT_WG_WAVES
-#define TPT_WGW_QUAD TPT_WG_WAVES
-#define TPT_WGW_REF TPT_WG_WAVES
-#else
-// Measured: one lane per pixel at one wave, C2 +2.6 %; the other families
-// keep four waves until their own configurations are measured.
-#define TPT_WGW_LANE 1    // one lane per pixel, ordered traversal
-#define TPT_WGW_DRAIN 1   // the same, drained launches
-#define TPT_WGW_PAIR 4    // pair mode
-#define TPT_WGW_IS 4      // env importance sampling (pair mode or one lane)
-#define TPT_WGW_QUAD 4    // four lanes per pixel
-#define TPT_WGW_REF 4     // the reference's visit order
-#endif
 
 namespace tpt {
-
-// the workgroup shape of a k_trace variant's family
-template <bool ORDERED, bool ENVIS, bool PAIR, bool DRAIN, bool QUAD>
-constexpr int trace_wgw() {
-    constexpr int w = !ORDERED ? TPT_WGW_REF
-                               : (ENVIS ? TPT_WGW_IS
-                                        : (PAIR ? TPT_WGW_PAIR : (QUAD ? TPT_WGW_QUAD : (DRAIN ? TPT_WGW_DRAIN : TPT_WGW_LANE))));
-    static_assert(w == 1 || w == 2 || w == 4, "waves per k_trace workgroup: 1, 2 or 4");
-    return w;
-}
 
 // LDS-typed pointers: the compiler then always emits ds_* accesses; a plain
 // (generic) pointer that may meet a private or global one in a select is
@@ -941,8 +885,7 @@ enum : int { PH_WAIT = 5 };   // pair mode: path lane waiting to unwind
 //     15-29 (0x7fff: none);
 //   delta lights (rec_words == 5): material id in bits 0-29, w2..w4 direct.
 // Levels < a.rec_lds_levels live in LDS ([level][word][lane]); deeper ones in
-// private memory.
-constexpr uint32_t kNoProbe = 0x7fffu;
+// private memory.  (kNoProbe: trace_variant.hpp)
 
 __device__ __forceinline__ uint32_t p_kind(float prob) {
     const uint32_t pb = __float_as_uint(prob);

@@ -657,7 +657,7 @@ static void wf_logic(const WfArgs& w, int init, hipStream_t s) {
     else launch_logic<true, false, false>(w, init, s);
 }
 static void wf_trace(const WfArgs& w, hipStream_t s) {
-    const bool small = (2 * (size_t)w.t.n_faces - 1) <= 65535;
+    const bool small = trace_small_ids(w.t.n_faces);
     const dim3 g(w.trace_blocks), b(256);
     if (!w.ordered) hipLaunchKernelGGL((k_wf_trace<false, int>), g, b, w.lds_bytes, s, w);
     else if (small) hipLaunchKernelGGL((k_wf_trace<true, uint16_t>), g, b, w.lds_bytes, s, w);
@@ -667,7 +667,7 @@ static void wf_trace(const WfArgs& w, hipStream_t s) {
 // LDS of k_wf_trace: the traversal stack only ([slot][lane]), within the share of
 // a CU's 160 KiB one of TPT_WF_TRACE_WAVES workgroups gets; deeper slots private.
 size_t wf_trace_lds(WfArgs& w) {
-    const size_t elem = (w.ordered && (2 * (size_t)w.t.n_faces - 1) <= 65535) ? 2 : 4;
+    const size_t elem = (w.ordered && trace_small_ids(w.t.n_faces)) ? 2 : 4;
     const size_t budget = (163840 / TPT_WF_TRACE_WAVES) & ~(size_t)255;
     size_t slots = (size_t)w.t.stack_depth + 3;
     slots = std::min(slots, budget / (256 * elem));
@@ -683,7 +683,7 @@ static hipError_t wf_trace_grid(WfArgs& w) {
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
-    const bool small = (2 * (size_t)w.t.n_faces - 1) <= 65535;
+    const bool small = trace_small_ids(w.t.n_faces);
     if (!w.ordered)
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_wf_trace<false, int>, 256, w.lds_bytes);
     else if (small)

@@ -2,11 +2,16 @@
 """Compare two device code objects function by function (CPU only).
 
     hipcc <flags> -x hip --cuda-device-only -c trace.hip -o new.co     (and old.co at another commit)
-    tools/kernel_diff.py old.co new.co [--drop-arg N]
+    tools/kernel_diff.py old.co new.co [--rename-new PATTERN REPL]... [--rename-old PATTERN REPL]... [--drop-arg N]
 
 Each input is a clang offload bundle (or a bare ELF).  Functions are matched by
-demangled name; --drop-arg N removes the N-th (0-based) template argument of
-k_trace<...> from the OLD names, for a commit that deleted that parameter.  The
+demangled name.  For a commit that renames kernels, --rename-new / --rename-old
+rewrite the demangled names of that side before matching: re.sub(PATTERN, REPL),
+each rule applied to every name, in the order given.  Rules can be kept in a file,
+one argument per line, and given as @FILE (kernel_diff_variants.args maps
+k_trace<TraceVariant<...>> names back to the ten positional arguments k_trace had
+before the descriptor).  --drop-arg N removes the N-th (0-based) template argument
+of k_trace<a, b, ...> from the OLD names, for a commit that deleted that parameter.  The
 disassembly is compared as text with addresses and encodings stripped.  Lines
 that differ only in the literal of the s_add_u32 / s_addc_u32 pair that follows an
 s_getpc_b64 are reported apart: those are pc-relative addresses of out-of-line
@@ -52,7 +57,7 @@ def functions(elf):
             continue
         ins = line.split("//")[0].strip()
         ins = re.sub(r"\s+", " ", ins)
-        if ins:
+        if ins and ins != "...":   # (objdump's mark for a run of zero bytes: padding behind a function)
             cur.append(ins)
     names = list(funcs)
     dem = subprocess.run(["c++filt"], input="\n".join(names), check=True, capture_output=True, text=True).stdout
@@ -82,26 +87,40 @@ def drop_arg(name, k):
     return name[:m.start(1)] + ", ".join(args) + name[m.end(1):]
 
 
+def renamed(funcs, rules):
+    out = {}
+    for n, body in funcs.items():
+        for pat, repl in rules:
+            n = re.sub(pat, repl, n)
+        if n in out:
+            sys.exit(f"rename rules map two functions to {n}")
+        out[n] = body
+    return out
+
+
 def main():
-    ap = argparse.ArgumentParser()
+    ap = argparse.ArgumentParser(fromfile_prefix_chars="@")
     ap.add_argument("old")
     ap.add_argument("new")
+    ap.add_argument("--rename-old", nargs=2, action="append", default=[], metavar=("PATTERN", "REPL"))
+    ap.add_argument("--rename-new", nargs=2, action="append", default=[], metavar=("PATTERN", "REPL"))
     ap.add_argument("--drop-arg", type=int, default=None)
     ap.add_argument("--drop-value", default="false", help="old k_trace variants whose dropped argument differs are "
                     "expected to have no counterpart")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         old, new = functions(elf_of(a.old, tmp)), functions(elf_of(a.new, tmp))
+    old, new = renamed(old, a.rename_old), renamed(new, a.rename_new)
     gone = []
     if a.drop_arg is not None:
-        renamed = {}
+        kept = {}
         for n, body in old.items():
             m = re.search(r"k_trace<(.*)>\(", n)
             if m and m.group(1).split(", ")[a.drop_arg] != a.drop_value:
                 gone.append(n)
                 continue
-            renamed[drop_arg(n, a.drop_arg)] = body
-        old = renamed
+            kept[drop_arg(n, a.drop_arg)] = body
+        old = kept
     only_old, only_new = sorted(set(old) - set(new)), sorted(set(new) - set(old))
     same = reloc_only = 0
     bad = []

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """VGPRs / VGPR spills / scratch per k_trace variant from a
-`-Rpass-analysis=kernel-resource-usage` remark stream on stdin.  With an argument,
-the kernels whose mangled name contains it instead (e.g. `svgf` for post.hip's)."""
+`-Rpass-analysis=kernel-resource-usage` remark stream on stdin: the depth-8 variants,
+named by the TraceVariant arguments of their mangled names (trace_variant.hpp: the
+family's number, Li8, then Lb0 / Lb1 for 5-word records and the material table in
+LDS, t / i for 16- / 32-bit ids, Lb1 for NOEMIT).  With an argument, the kernels
+whose mangled name contains it instead (e.g. `svgf` for post.hip's)."""
 import re
 import sys
 
@@ -21,6 +24,6 @@ for k, v in rows.items():
         if only in k:
             print(f"{k[:60]:60s} VGPRs {v.get('VGPRs', 0):4d} spill {v.get('VGPRs Spill', 0):3d} "
                   f"scratch {v.get('ScratchSize', 0):5d} waves {v.get('Occupancy', 0)}")
-    elif "k_trace" in k and "ILi8E" in k:
-        print(f"{k[18:60]:44s} VGPRs {v.get('VGPRs', 0):4d} spill {v.get('VGPRs Spill', 0):3d} "
+    elif "k_trace" in k and "ELi8E" in k:
+        print(f"{k.split('TraceFamilyE')[1][:24]:24s} VGPRs {v.get('VGPRs', 0):4d} spill {v.get('VGPRs Spill', 0):3d} "
               f"scratch {v.get('ScratchSize', 0):5d} waves {v.get('Occupancy', 0)}")
