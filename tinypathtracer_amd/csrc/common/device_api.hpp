@@ -99,6 +99,10 @@ struct TraceArgs {
     int32_t boxes_finite;                // all node boxes finite: min/max slab test is exact
     int32_t any_emitter;                 // some triangle emits (else a direct probe adds nothing)
     int32_t emit_root;                   // inner4 id of the emissive-triangle tree (-1: none)
+    // 1: every material's baseColor component is finite, has a clear sign bit and is at most
+    // kPruneColorCap (trace_variant.hpp), so the unwind may skip levels that provably give +0
+    // (trace.hip "Pruned unwind").  (Fills the padding before emit_box: no other field moves.)
+    int32_t unwind_prune;
     // Boxes enclosing every emissive triangle's leaf box (the emissive tree
     // root's child boxes, overlapping ones merged): (lo.xyz, 0), (hi.xyz, 0) per
     // box.  A direct probe whose line misses all of them by a margin can hit no

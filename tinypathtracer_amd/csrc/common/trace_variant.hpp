@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <type_traits>
 
 #ifndef TPT_TRACE_WAVES
@@ -121,8 +122,36 @@ struct TraceVariant {
     static constexpr int MAXD = MAXD_, WGW = fam.wgw, WAVES = fam.waves;
     static constexpr bool ORDERED = fam.ordered, LIGHTS = LIGHTS_, MTL_LDS = MTL_LDS_, ENVIS = fam.env_is,
                           PAIR = fam.lanes == 2, DRAIN = F == TF_DRAIN, QUAD = fam.lanes == 4, NOEMIT = NOEMIT_;
+    // the pruned unwind (below): the 2-word-record variants of the one-lane, DRAIN and four-lane families
+    static constexpr bool PRUNE = !LIGHTS_ && ORDERED && !PAIR && !ENVIS;
     using StackT = StackT_;
 };
+
+// Pruned unwind (k_trace, 2-word records).  The unwind's step is
+// L = (1/p) * ((dst + L) * (af * color)).  A level is *clean* when its probe reached no
+// emitter (dst is exactly +0), its p is af itself (p-kind 0) and af lies in
+// [kPruneAfMin, kPruneAfMax]; the scene is prunable when every baseColor component passes
+// prune_color_ok.  Then a clean level maps L = +0 to +0, in IEEE arithmetic without
+// contraction:
+//   +0 + +0 = +0;
+//   +0 * x = +0 for finite x with a clear sign bit, and x = af * color is that: af is
+//     positive and at most 2^100, color has a clear sign bit and is at most 2^27, so the
+//     product is at most 2^127 and has a clear sign bit (+0 where color is +0 or it underflows);
+//   y * +0 = +0 for finite positive y, and y = 1 / af is that for af in [2^-100, 2^100].
+// A path that ends with L = +0 (a miss without env map, max_depth) therefore keeps +0 down
+// to the deepest level that is not clean, and the unwind may start there.  Every level it
+// does run is the same arithmetic on the same inputs.  The p-kinds 1 and 2 (p = -0 / +0, a
+// hemisphere sample whose cosine rounds to zero) divide by zero: such a level is never
+// clean.  No test input reaches them -- the sample's cosine is at least about 1.5e-5 --
+// so the rule for them is conservative and rests on this argument alone.
+constexpr float kPruneAfMin = 0x1p-100f, kPruneAfMax = 0x1p100f, kPruneColorCap = 0x1p27f;
+// finite, sign bit clear (no -0, no negative NaN) and at most the cap: as bits, one unsigned
+// compare (a set sign bit, inf and NaN all lie above the cap's pattern, 2^27 = 0x4d000000)
+inline bool prune_color_ok(float c) {
+    uint32_t b;
+    std::memcpy(&b, &c, sizeof b);
+    return b <= 0x4d000000u;
+}
 
 constexpr uint32_t kNoProbe = 0x7fffu;   // the packed records' 15-bit probe material id for "the probe hit nothing"
 // Path-record words per bounce (k_trace): 2 when the scene has no delta lights

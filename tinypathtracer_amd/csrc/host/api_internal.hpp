@@ -297,6 +297,7 @@ struct tpt_scene {
     int32_t stack_depth = 0;
     int32_t boxes_finite = 0;
     int32_t any_emitter = 1;                // some triangle's material has emissionFactor != 0
+    int32_t unwind_prune = 0;               // every baseColor component passes tpt::prune_color_ok (TraceArgs unwind_prune)
     int32_t n4 = 0;
     int32_t wide_tree = 0;                  // 1: inner4 holds the SAH 4-wide tree (wide_bvh.cpp)
     int32_t emit_root = -1;                 // inner4 id of the emissive-triangle tree's root (-1: none)

@@ -46,6 +46,10 @@ void tpt::host::fill_trace_args(tpt_scene* s, const tpt_env* env, const tpt_came
     a.boxes_finite = s->boxes_finite;
     a.any_emitter = s->any_emitter;
     a.emit_root = s->emit_root;
+    a.unwind_prune = s->unwind_prune;
+#ifdef TPT_PROFILE_PHASES
+    if (std::getenv("TPT_DEBUG_NO_PRUNE")) a.unwind_prune = 0;   // the unpruned unwind's counts from the same build
+#endif
     a.n_emit_box = s->any_emitter ? s->n_emit_box : 0;
     for (int k = 0; k < a.n_emit_box; ++k) {
         const float* b = s->emit_box + 6 * k;
@@ -467,7 +471,7 @@ tpt_status tpt_render_frames(tpt_scene* s, const tpt_env* env, const tpt_camera*
         }
     }
 #if defined(TPT_PROFILE_PHASES) || defined(TPT_VERIFY_CULL)
-    if (std::getenv("TPT_DEBUG_COUNTERS")) {   // raw kernel counters (TPT_PROFILE_PHASES builds: 6..15 phases, 16..22 shading-pass sections)
+    if (std::getenv("TPT_DEBUG_COUNTERS")) {   // raw kernel counters (TPT_PROFILE_PHASES builds: 6..15 phases, 16..22 shading-pass sections, 29..31 the unwind)
         std::fprintf(stderr, "tpt counters:");
         for (int i = 0; i < 32; ++i) std::fprintf(stderr, " %llu", cnt[i]);
         std::fprintf(stderr, "\n");

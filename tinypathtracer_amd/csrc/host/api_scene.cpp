@@ -558,8 +558,11 @@ tpt_status tpt_scene_create(const tpt_scene_desc* d_in, int device, tpt_scene** 
     for (uint32_t i = 0; i < d->n_objects; ++i) lut[i] = make_int2(d->lut[i].begin, d->lut[i].mtl);
     // materials + one Material() slot for meshes without a material (App. A.9)
     std::vector<float4> mtl(2 * ((size_t)d->n_materials + 1));
+    s->unwind_prune = 1;   // k_trace's pruned unwind needs every colour of the table, the Material() slot included
     for (uint32_t i = 0; i <= d->n_materials; ++i) {
         tpt_material m = (i < d->n_materials && d->materials) ? d->materials[i] : tpt::default_material();
+        for (int c = 0; c < 3; ++c)
+            if (!tpt::prune_color_ok(m.base_color[c])) s->unwind_prune = 0;
         mtl[2 * i] = make_float4(m.base_color[0], m.base_color[1], m.base_color[2], m.emission_factor);
         mtl[2 * i + 1] = make_float4(m.eta, m.metallic, 0.0f, 0.0f);
     }

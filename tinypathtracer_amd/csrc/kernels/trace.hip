@@ -110,7 +110,12 @@ template <class V>
 __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
     constexpr int MAXD = V::MAXD;
     constexpr bool ORDERED = V::ORDERED, LIGHTS = V::LIGHTS, MTL_LDS = V::MTL_LDS, ENVIS = V::ENVIS, PAIR = V::PAIR,
-                   DRAIN = V::DRAIN, QUAD = V::QUAD, NOEMIT = V::NOEMIT;
+                   DRAIN = V::DRAIN, QUAD = V::QUAD, NOEMIT = V::NOEMIT, PRUNE = V::PRUNE;
+    // Pruned unwind (trace_variant.hpp has the rule and its proof): ztop, the levels the
+    // unwind needs when the path ends with L = +0 (0 at the camera ray, level + 1 at every
+    // level that is not clean), rides in bits 15-21 of mk, which the 2-word variants'
+    // 15-bit material ids leave free: no register of its own across the traversal loop.
+    constexpr uint32_t kZTop = PRUNE ? 0x7fu << 15 : 0u, kMkId = PRUNE ? 0x7fffu : 0x3fffffffu;
     using StackT = typename V::StackT;
     // A tile is four waves (2 x 2 sub-tiles), rendered by 4 / WGW workgroups of WGW
     // waves each, adjacent in grid x: block x = tile * (4 / WGW) + part.  The tiles
@@ -231,7 +236,7 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
     int remaining = a.samples;
     int phase = PH_CAMERA;
     int depth = 0, li = 0;
-    uint32_t mk = 0;   // material id | p-kind << 30 of the current bounce
+    uint32_t mk = 0;   // material id | p-kind << 30 of the current bounce (PRUNE: | the path's ztop << 15)
     bool env_pending = false;   // A15: this bounce's env next-event sample is still to be drawn
     V3 env_k = v3(0.0f, 0.0f, 0.0f);
     // pair mode + A15: the env sample's uniforms and incident-side normal, drawn by
@@ -279,7 +284,10 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
                 rec.put(depth, 4, direct.z);
             }
         } else {
-            rec.put_dst(depth, mk, pm, dl);
+            if constexpr (PRUNE) {
+                if (pm != kNoProbe) mk = (mk & ~kZTop) | (uint32_t)(depth + 1) << 15;   // a direct term: not clean
+            }
+            rec.put_dst(depth, mk & ~kZTop, pm, dl);
         }
     };
 
@@ -290,6 +298,8 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
     // finished ray waiting for the wave's next shading pass, no work (pixel done
     // or none, pair-mode idle); and the lanes each shading pass serves
     unsigned long long p_lt = 0, p_lw = 0, p_lx = 0, p_lp = 0;
+    // the unwind: the wave's loop iterations, its lanes' steps, shading passes with at least one iteration
+    uint32_t p_uw_iter = 0, p_uw_lane = 0, p_uw_pass = 0;
     // shading-pass sections (profiling builds only): every boundary drains
     // the wave's outstanding memory operations, so a section is charged the
     // latency of its own loads; the pass's first active lane adds the time
@@ -401,7 +411,14 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
                         const float prob = new_direction(rd, nrm, m1.x, m1.y, st, nd, af);
                         graze_next = grazing(gpass, nd);
                         rec.put(depth, 0, af);
-                        mk = (uint32_t)mtl | (p_kind(prob) << 30);
+                        if constexpr (PRUNE) {
+                            // not clean: p is a signed zero, or af (NaN included) outside the range
+                            const uint32_t kind = p_kind(prob);
+                            const bool clean = kind == 0u && af >= kPruneAfMin && af <= kPruneAfMax;
+                            mk = (uint32_t)mtl | (kind << 30) | (clean ? (mk & kZTop) : (uint32_t)(depth + 1) << 15);
+                        } else {
+                            mk = (uint32_t)mtl | (p_kind(prob) << 30);
+                        }
                         direct = v3(0.0f, 0.0f, 0.0f);
                         li = 0;
                         delegated = false;
@@ -464,7 +481,7 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
                 lights_next = false;
             }
             if (lights_next) {
-                const float4 m1 = MT(2 * (mk & 0x3fffffffu) + 1);
+                const float4 m1 = MT(2 * (mk & kMkId) + 1);
                 if (LIGHTS && li < a.n_lights) {
                     V3 lrad;
                     light_sample(a.lights, li, r.o, td, lrad);
@@ -518,7 +535,7 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
             }
             TPT_SEC(2)
             if (after) {
-                const float e = MT(2 * (mk & 0x3fffffffu)).w;
+                const float e = MT(2 * (mk & kMkId)).w;
                 if (e > 0.0f) {   // an emitter ends the path (:408-412); the unwind starts from e
                     L = e * v3(1.0f, 1.0f, 1.0f);
                     finish = true;
@@ -568,12 +585,40 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
                 finish = false;
             }
             bool unwound = false;
+            if constexpr (PRUNE) {
+                // Pruned unwind: a path that ends with L = +0 in all three words, in a scene whose
+                // colours allow it, unwinds from its deepest level that is not clean.  A finishing
+                // path's depth is dead but for the unwind (the camera ray resets it), so it takes
+                // the unwind's level count: no register beside it.
+                const uint32_t lbits = __float_as_uint(L.x) | __float_as_uint(L.y) | __float_as_uint(L.z);
+                if (finish && a.unwind_prune && lbits == 0u) depth = min(depth, (int)((mk & kZTop) >> 15));
+            }
+#ifdef TPT_PROFILE_PHASES
+            {   // the wave's unwind iterations (its deepest finishing lane's levels), charged to the
+                // pass's first lane; each lane's own steps; passes with any iteration
+                uint32_t mt = 0;
+                while (__ballot(finish && depth > (int)mt) != 0ull) ++mt;
+                if (__builtin_amdgcn_readfirstlane(lane) == lane) {
+                    p_uw_iter += mt;
+                    p_uw_pass += mt > 0u ? 1u : 0u;
+                }
+                p_uw_lane += finish ? (uint32_t)depth : 0u;
+            }
+#endif
             if constexpr (DRAIN && !LIGHTS && MAXD == 8) {
                 // DRAIN variants: every level's record and materials read before the
                 // arithmetic, so the unwind pays one LDS latency chain instead of one
                 // per level (the same operations in the same order as below)
                 static_assert(!PAIR && !LIGHTS, "DRAIN unwind: one-lane 2-word records");
-                if (finish && rec.nlds >= 8) {
+                // No finishing lane has a level to run (pruned unwind): they finish here and the
+                // block below, loads included, runs with no lane.  (A block of its own: nested in
+                // the one below, the same test cost the depth-8 DRAIN variants 2-4 spilled VGPRs.)
+                if (finish && rec.nlds >= 8 && __ballot(finish && depth > 0) == 0ull) {
+                    unwound = true;
+                    total = total + L;
+                    phase = PH_CAMERA;
+                }
+                if (finish && !unwound && rec.nlds >= 8) {
                     unwound = true;
                     float af[8];
                     uint32_t w1[8];
@@ -661,6 +706,7 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
                     to = v3(a.origin[0], a.origin[1], a.origin[2]);
                     tg = false;   // the camera: no surface
                     depth = 0;
+                    if constexpr (PRUNE) mk = 0;   // ztop = 0
                     phase = PH_EXT;
                 }
             }
@@ -866,6 +912,7 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
     unsigned long long s_sec[7];
 #pragma unroll
     for (int k = 0; k < 7; ++k) s_sec[k] = wave_sum(p_sec[k]);
+    const unsigned long long s_uw[3] = {wave_sum(p_uw_iter), wave_sum(QUAD && !lead ? 0u : p_uw_lane), wave_sum(p_uw_pass)};
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 7; ++k) atomicAdd(&a.counters[16 + k], s_sec[k]);
@@ -891,6 +938,9 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
         atomicAdd(&a.counters[26], p_lw);
         atomicAdd(&a.counters[27], p_lx);
         atomicAdd(&a.counters[28], p_lp);
+        atomicAdd(&a.counters[29], s_uw[0]);
+        atomicAdd(&a.counters[30], s_uw[1]);
+        atomicAdd(&a.counters[31], s_uw[2]);
         const unsigned long long life = wall_clock64() - t_wave0;
         atomicMax(&a.counters[13], life);
         atomicAdd(&a.counters[14], life);

@@ -3,7 +3,10 @@
 # phase-profiling build (variants/prof, -DTPT_PROFILE_PHASES) counts, per
 # traversal step, the lanes traversing / holding a finished ray that waits for
 # the wave's next shading pass / without work, and the lanes each shading pass
-# serves.  One 256-spp full-frame launch per config.
+# serves; and the unwind's loop iterations per wave, its steps per lane and the
+# passes that run at least one (TPT_DEBUG_NO_PRUNE=1: with the unwind unpruned, what
+# the same build counts for the rule switched off).  One 256-spp full-frame launch
+# per config.
 # Usage: [PROF_LIB=variants/NAME] bash tools/gpu_lanes.sh "C2 C5" [extra bench args]
 #   (PROF_LIB: another phase-profiling build)
 set -o pipefail
@@ -23,6 +26,8 @@ tot = lt + lw + lx
 print(f"{sys.argv[3]} {sys.argv[1]}: steps {steps} passes {passes} steps/pass {steps / max(passes, 1):.2f} | lane-steps: traversing "
       f"{lt / tot:.3f} waiting-for-pass {lw / tot:.3f} no-work {lx / tot:.3f} | lanes per pass {lp / max(passes, 1):.1f} | "
       f"shading ticks {c[6]} traversal ticks {c[7]} | pass sections (consume, lights/probe set-up, after, unwind, "
-      f"camera, ray set-up): {' '.join(str(v) for v in c[17:23])}")
+      f"camera, ray set-up): {' '.join(str(v) for v in c[17:23])} | unwind: wave iterations {c[29]} "
+      f"({c[29] / max(passes, 1):.3f} per pass) lane steps {c[30]} passes with an iteration {c[31]} "
+      f"({c[31] / max(passes, 1):.3f} of passes)")
 PY
 done
