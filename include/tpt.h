@@ -328,6 +328,41 @@ typedef struct {
 tpt_status tpt_render_aov(tpt_scene* scene, const tpt_camera* camera, int32_t width, int32_t height,
                           const tpt_aov* out, double* trace_ms);
 
+/* Mirror-path feature buffers: tpt_render_aov continued through perfect mirrors
+ * (DESIGN.md section 5 "Post-pass" holds the definition).  A hit is a mirror when its
+ * material has !(eta > 0), metallic > 0 and !(emission_factor > 0): getNewDirection's
+ * branch order, and an emitter ends a path.  The reference's metal reflects without a random
+ * number, so the path is followed exactly: from the hit point along reflect(d, n) about the
+ * shading normal, traced as the render traces an extension ray from that face, up to
+ * max_bounces mirrors.  The buffers describe the first surface that is no mirror (glass is
+ * one such: its two lobes are a coin flip), or the mirror met at the cap:
+ *   face, material, normal: that surface's; -1, -1, 0 when the path leaves the scene;
+ *   albedo: the product of the base colours of every surface met, mirrors included, so that
+ *     demodulation divides a reflection by the tint it carries; on a miss the mirrors' alone;
+ *   depth: the distance travelled along the whole path, on a miss up to the last mirror;
+ *   bounces_out: nullable, W*H (host or device memory as out's pointers): mirrors followed.
+ * With max_bounces 0, and in a scene without a mirror, every buffer equals tpt_render_aov's
+ * bit for bit.  Deterministic; no RNG is consumed.  tpt_denoise and tpt_denoise_svgf take
+ * the result as `guides` unchanged.  tpt_temporal and tpt_temporal_motion do not: they
+ * reproject the first hit and compare its material, so they stay on tpt_render_aov's buffers.
+ * stats: nullable.
+ * TPT_ERR_INVALID_ARG: tpt_render_aov's refusals (out itself may be null when bounces_out is
+ * not: at least one output is needed), null params, max_bounces outside 0..64, flags != 0. */
+typedef struct {
+    int32_t max_bounces;     /* 0..64, as tpt_params.max_depth's range */
+    int32_t flags;           /* 0; unknown bits are refused */
+} tpt_aov_path_params;
+
+typedef struct {
+    double   trace_ms;       /* the kernel's duration (HIP events) */
+    uint64_t followed;       /* pixels that followed at least one mirror */
+    int32_t  deepest;        /* the largest bounce count of the frame */
+} tpt_aov_path_stats;
+
+tpt_status tpt_render_aov_path(tpt_scene* scene, const tpt_camera* camera, int32_t width, int32_t height,
+                               const tpt_aov_path_params* params, const tpt_aov* out, int32_t* bounces_out,
+                               tpt_aov_path_stats* stats);
+
 #define TPT_DENOISE_DEMODULATE 0x1   /* filter radiance / max(albedo, 1e-3), multiply back afterwards */
 #define TPT_DENOISE_DIRECT     0x2   /* A/B: steps 1 and 2 through the direct kernel too instead of the
                                         LDS-staged one (bit-identical output) */

@@ -41,6 +41,7 @@ struct BVHNode {
     float bmin[3], bmax[3];
 };
 static_assert(sizeof(BVHNode) == 36, "BVHNode layout");
+static_assert(sizeof(tpt_aov_path_params) == 8 && sizeof(tpt_aov_path_stats) == 24, "tpt_aov_path_* layout");
 
 class DeviceScene;
 
@@ -298,6 +299,32 @@ public:
     void renderAOV(DeviceScene& scene, const Camera& camera, const tpt_aov& out, double* trace_ms = nullptr) {
         if (!scene.built()) scene.build();
         check(tpt_render_aov(scene.handle(), &camera.c, m_width, m_height, &out, trace_ms));
+    }
+
+    // Mirror-path feature buffers (tpt_render_aov_path): renderAOV continued through up to
+    // max_bounces perfect mirrors, for denoise / denoiseSVGF (temporal stays on renderAOV's).
+    // bounces (nullable) receives the W*H bounce counts.
+    AOV renderAOVPath(DeviceScene& scene, const Camera& camera, int max_bounces = 8,
+                      std::vector<int32_t>* bounces = nullptr, tpt_aov_path_stats* stats = nullptr) {
+        AOV a;
+        a.width = m_width;
+        a.height = m_height;
+        const size_t n = (size_t)m_width * m_height;
+        a.albedo.resize(3 * n);
+        a.normal.resize(3 * n);
+        a.depth.resize(n);
+        a.face.resize(n);
+        a.material.resize(n);
+        if (bounces) bounces->resize(n);
+        renderAOVPath(scene, camera, a.view(), bounces ? bounces->data() : nullptr, max_bounces, stats);
+        return a;
+    }
+    // The same into caller buffers (host or device pointers, each nullable).
+    void renderAOVPath(DeviceScene& scene, const Camera& camera, const tpt_aov& out, int32_t* bounces,
+                       int max_bounces = 8, tpt_aov_path_stats* stats = nullptr) {
+        if (!scene.built()) scene.build();
+        const tpt_aov_path_params p{max_bounces, 0};
+        check(tpt_render_aov_path(scene.handle(), &camera.c, m_width, m_height, &p, &out, bounces, stats));
     }
 
     // Edge-avoiding a-trous filter (tpt_denoise) of a radiance frame guided by its

@@ -479,6 +479,11 @@ AOV_LAYOUT = {"albedo": (3, "float32"), "normal": (3, "float32"), "depth": (1, "
               "face": (1, "int32"), "material": (1, "int32")}
 _PLANES = dict(AOV_LAYOUT, radiance=(3, "float32"), framebuffer=(4, "uint8"))
 
+# Mirror-path feature buffers (tpt_render_aov_path): the hosts' and the CLI's default cap, the
+# render's default max_depth
+AOV_PATH_DEFAULTS = {"max_bounces": 8}
+_PLANES.update(bounces=(1, "int32"))
+
 
 def _check_plane(name, buf, width, height):
     """The library reads / writes width * height * channels elements behind the
@@ -666,6 +671,47 @@ class PathTracer:
         check(lib().tpt_render_aov(d_scene.handle, C.byref(cam), W, H, C.byref(a), C.byref(ms)))
         if stats is not None:
             stats["trace_ms"] = ms.value
+        return out
+
+    def renderAOVPath(self, d_scene: DeviceScene, camera: Camera, max_bounces: int = AOV_PATH_DEFAULTS["max_bounces"],
+                      out=None, stats=None):
+        """Mirror-path feature buffers (tpt_render_aov_path, DESIGN.md section 5
+        "Post-pass"): renderAOV continued through up to `max_bounces` perfect mirrors.
+        The buffers describe the first surface that is no mirror (or the mirror met at
+        the cap): its face, material and normal, the product of every base colour met
+        as `albedo`, the distance along the whole path as `depth`; a path that leaves
+        the scene holds face / material -1, normal 0, the mirrors' tint and the distance
+        to the last mirror.  Returns renderAOV's dict plus `bounces` [H, W] (int32), the
+        mirrors followed.  out: as renderAOV's, `bounces` included.  stats: a dict that
+        receives trace_ms, followed (pixels with bounces > 0) and deepest.  The result
+        guides denoise / denoiseSVGF; temporal stays on renderAOV's first-hit buffers."""
+        if not d_scene.built:
+            d_scene.build()
+        W, H = self.m_width, self.m_height
+        if out is None:
+            out = {"albedo": np.zeros((H, W, 3), np.float32), "normal": np.zeros((H, W, 3), np.float32),
+                   "depth": np.zeros((H, W), np.float32), "face": np.zeros((H, W), np.int32),
+                   "material": np.zeros((H, W), np.int32), "bounces": np.zeros((H, W), np.int32)}
+        unknown = set(out) - set(AOV_LAYOUT) - {"bounces"}
+        if unknown:
+            raise ValueError(f"unknown feature buffers {sorted(unknown)}")
+        a = _lib.Aov()
+        bounces = None
+        for k, buf in out.items():
+            if buf is None:
+                continue
+            _check_plane(k, buf, W, H)
+            if k == "bounces":
+                bounces = _addr(buf)
+            else:
+                setattr(a, k, _addr(buf))
+        p = _lib.AovPathParams(int(max_bounces), 0)
+        st = _lib.AovPathStats()
+        cam = camera.to_c()
+        check(lib().tpt_render_aov_path(d_scene.handle, C.byref(cam), W, H, C.byref(p), C.byref(a), bounces,
+                                        C.byref(st)))
+        if stats is not None:
+            stats.update(st.as_dict())
         return out
 
     def denoise(self, d_scene: DeviceScene, radiance, aov, iterations: int = DENOISE_DEFAULTS["iterations"],

@@ -103,6 +103,17 @@ class Aov(C.Structure):
                 ("material", C.c_void_p)]
 
 
+class AovPathParams(C.Structure):
+    _fields_ = [("max_bounces", C.c_int32), ("flags", C.c_int32)]
+
+
+class AovPathStats(C.Structure):
+    _fields_ = [("trace_ms", C.c_double), ("followed", C.c_uint64), ("deepest", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
                 ("sigma_depth", C.c_float), ("flags", C.c_int32)]
@@ -151,6 +162,9 @@ SIGNATURES = [
                                     C.POINTER(Stats)]),
     ("tpt_render_aov", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(Aov),
                                  C.POINTER(C.c_double)]),
+    ("tpt_render_aov_path", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32,
+                                      C.POINTER(AovPathParams), C.POINTER(Aov), C.c_void_p,
+                                      C.POINTER(AovPathStats)]),
     ("tpt_denoise", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Aov),
                               C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.POINTER(DenoiseStats)]),
     ("tpt_history_create", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),

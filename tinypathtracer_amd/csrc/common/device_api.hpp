@@ -269,6 +269,16 @@ struct AovArgs {                         // device pointers, each nullable; W*H 
 // a: the scene, the camera constants, width, height, inv_w, inv_h (whole frame; bands do not apply)
 hipError_t launch_aov(const TraceArgs& a, const AovArgs& o, hipStream_t s);
 
+// post.hip k_aov_path: the same continued through perfect mirrors (tpt_render_aov_path)
+struct AovPathArgs {
+    int32_t* bounces;                    // nullable, W*H: mirrors followed
+    int32_t max_bounces;
+    unsigned long long* followed;        // kTemporalSlots counters, kTemporalSlotStride words apart (zeroed by the
+                                         //   caller): their sum = pixels with bounces > 0
+    unsigned long long* deepest;         // as many, as far apart (zeroed): their maximum = the largest bounces
+};
+hipError_t launch_aov_path(const TraceArgs& a, const AovArgs& o, const AovPathArgs& p, hipStream_t s);
+
 struct DenoiseArgs {                     // pack (inputs -> planes) and resolve (plane -> outputs)
     const float* radiance_in;            // pack: W*H*3
     const float* albedo;                 // W*H*3 (read when demodulate)

@@ -383,6 +383,11 @@ struct tpt_scene {
     DevBuf<unsigned long long> sv_count;
     HostPinned<unsigned long long> sv_h_count;
     hipEvent_t sv_ev = nullptr;
+    // tpt_render_aov_path: tpt_render_aov's staging above, and of its own the staging of the bounce
+    // counts and the counters of AovPathArgs::followed and ::deepest (one allocation, followed first)
+    DevBuf<int32_t> ap_bounces;
+    DevBuf<unsigned long long> ap_count;
+    HostPinned<unsigned long long> ap_h_count;
 
     ~tpt_scene() {
         DeviceGuard g(device);

@@ -1,4 +1,4 @@
-// api_post.cpp -- the post-pass entry points of the C-ABI (post.hip): tpt_render_aov,
+// api_post.cpp -- the post-pass entry points of the C-ABI (post.hip): tpt_render_aov, tpt_render_aov_path,
 // tpt_denoise, tpt_history_*, tpt_temporal, tpt_temporal_motion and tpt_denoise_svgf.  Each takes its buffers from either
 // side: host buffers go through the device staging the scene / history keeps
 // (api_internal.hpp Staging).
@@ -82,6 +82,73 @@ tpt_status tpt_render_aov(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_
         float ms = 0.0f;
         HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
         *trace_ms = ms;
+    }
+    return TPT_OK;
+}
+
+// Mirror-path feature buffers (post.hip k_aov_path; DESIGN.md section 5 "Post-pass"):
+// tpt_render_aov's call with the bounce counts as a sixth output and two statistics,
+// counted by the kernel in the spread counters and reduced here.
+tpt_status tpt_render_aov_path(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_t H,
+                               const tpt_aov_path_params* p, const tpt_aov* out, int32_t* bounces_out,
+                               tpt_aov_path_stats* stats) {
+    if (!s || !s->built) return fail(TPT_ERR_INVALID_ARG, "scene not built");
+    if (!cam) return fail(TPT_ERR_INVALID_ARG, "null camera");
+    if (!p) return fail(TPT_ERR_INVALID_ARG, "null params");
+    if (W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size");
+    if (p->max_bounces < 0 || p->max_bounces > 64) return fail(TPT_ERR_INVALID_ARG, "max_bounces must be 0..64");
+    if (p->flags != 0) return fail(TPT_ERR_INVALID_ARG, "unknown aov path flags");
+    if (!bounces_out && !(out && (out->albedo || out->normal || out->depth || out->face || out->material)))
+        return fail(TPT_ERR_INVALID_ARG,
+                    "no feature buffer requested: every pointer of out and bounces_out are null");
+    {
+        const tpt_status bs = finish_pending(s);
+        if (bs != TPT_OK) return bs;
+    }
+    DeviceGuard g(s->device);
+    hipStream_t st = s->stream;
+    const size_t npix = (size_t)W * (size_t)H;
+    tpt::TraceArgs a{};
+    fill_trace_args(s, nullptr, cam, a);
+    a.width = W;
+    a.height = H;
+    a.inv_w = 1.0f / (float)W;
+    a.inv_h = 1.0f / (float)H;
+    const tpt_aov none{};
+    const tpt_aov* q = out ? out : &none;
+    tpt::AovArgs o{};
+    tpt::AovPathArgs pa{};
+    pa.max_bounces = p->max_bounces;
+    HIP_OR_FAIL(s->ap_count.alloc(2 * kCountWords));
+    HIP_OR_FAIL(s->ap_h_count.alloc(2 * kCountWords));
+    pa.followed = s->ap_count.p;
+    pa.deepest = s->ap_count.p + kCountWords;
+    Staging sg(st);
+    HIP_OR_FAIL(sg.out(s->aov_f3[0], q->albedo, 3 * npix, &o.albedo));
+    HIP_OR_FAIL(sg.out(s->aov_i[0], q->face, npix, &o.face));
+    HIP_OR_FAIL(sg.out(s->aov_f3[1], q->normal, 3 * npix, &o.normal));
+    HIP_OR_FAIL(sg.out(s->aov_i[1], q->material, npix, &o.material));
+    HIP_OR_FAIL(sg.out(s->aov_depth, q->depth, npix, &o.depth));
+    HIP_OR_FAIL(sg.out(s->ap_bounces, bounces_out, npix, &pa.bounces));
+    HIP_OR_FAIL(hipMemsetAsync(s->ap_count.p, 0, 2 * kCountWords * sizeof(unsigned long long), st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
+    HIP_OR_FAIL(tpt::launch_aov_path(a, o, pa, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
+    HIP_OR_FAIL(sg.finish());
+    HIP_OR_FAIL(hipMemcpyAsync(s->ap_h_count.p, s->ap_count.p, 2 * kCountWords * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    if (stats) {
+        unsigned long long followed = 0, deepest = 0;
+        for (int k = 0; k < tpt::kTemporalSlots; ++k) {
+            followed += s->ap_h_count.p[(size_t)k * tpt::kTemporalSlotStride];
+            deepest = std::max(deepest, s->ap_h_count.p[kCountWords + (size_t)k * tpt::kTemporalSlotStride]);
+        }
+        float ms = 0.0f;
+        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        stats->trace_ms = ms;
+        stats->followed = followed;
+        stats->deepest = (int32_t)deepest;
     }
     return TPT_OK;
 }

@@ -8,6 +8,8 @@
 //    walks the render's own closest-hit traversal exactly as k_trace_rays mode 1
 //    (trav_lane<true>, the sliver pass, the grazing re-trace), then the hit prelude
 //    of path_tracer.cu:364-374.  The LDS stack is k_trace_rays'.
+//  * k_aov_path: the same ray followed through perfect mirrors to the first surface
+//    that is none (tpt_render_aov_path), a wave looping until none of its lanes continues.
 //  * k_dn_pack / k_atrous / k_atrous_lds / k_dn_resolve: the filter.  Two float4
 //    planes per pixel (colour; normal + depth), one launch per iteration ping-ponging
 //    between two colour planes, no atomics.  Each tap is two 16-B loads per lane;
@@ -90,6 +92,117 @@ hipError_t launch_aov(const TraceArgs& a, const AovArgs& o, hipStream_t s) {
     const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
     const size_t lds = (size_t)kAovLdsSlots * 256 * sizeof(int);
     hipLaunchKernelGGL(k_aov, grid, dim3(256), lds, s, a, o);
+    return hipGetLastError();
+}
+
+// k_aov continued through perfect mirrors (tpt_render_aov_path; DESIGN.md section 5
+// "Post-pass" holds the definition the tests pin).  k_aov's lanes, tiles and LDS stack.  A
+// lane traces, runs the hit prelude, and where the hit is a mirror below the cap reflects and
+// goes round again from the hit point, as k_trace starts an extension ray: the origin advanced
+// to o + t d, reflect_dir about the shading normal, the grazing rule with the face it leaves;
+// rayHitTriangle's t > kDelta keeps the ray off that face, there is no offset.  A finished
+// lane waits for its wave; the wave leaves when no lane continues, so a wave that meets no
+// mirror does k_aov's one traversal.  Lanes outside the frame stay to the end (they never
+// trace): the statistics are taken by the whole wave.
+__global__ __launch_bounds__(256) void k_aov_path(TraceArgs a, AovArgs o, AovPathArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+    const int y = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    const bool inside = x < a.width && y < a.height;   // (no barrier below)
+    // sampleRays (path_tracer.cu:42-59), k_aov's camera section
+    float lx = 0.5f * 1.0f, lyf = 0.5f * 1.0f;
+    lx = lx + (float)x;
+    lyf = lyf + (float)y;
+    lx = lx * a.inv_w;
+    lyf = lyf * a.inv_h;
+    lx = lx * a.sensor_w;
+    lyf = lyf * a.sensor_h;
+    float r4[4];
+    mat4_vec4(a.c2w, lx - a.half_sw, lyf - a.half_sh, 0.0f - 1.0f, 0.0f, r4);
+    V3 rd = normalize(v3(r4[0], r4[1], r4[2]));
+    V3 ro = v3(a.origin[0], a.origin[1], a.origin[2]);
+    Trav r;
+    LaneStack<int> stk;
+    stk.lds = (TPT_LDS int*)lds + tid;
+    stk.nlds = kAovLdsSlots;
+    uint32_t c_ovf = 0, c_leaf = 0;
+    V3 alb = v3(1.0f, 1.0f, 1.0f), nrm = v3(0.0f, 0.0f, 0.0f);   // the product of the base colours so far
+    float depth = 0.0f;                                          // the distance travelled so far
+    int fid = -1, mtl = -1, k = 0;
+    bool tg = false;   // the camera: no surface
+    bool live = inside;
+    while (__ballot(live) != 0ull) {
+        if (live) {
+            trav_begin(r, ro, rd, TM_CLOSEST, a.boxes_finite != 0, a.emit_root, a.cull_eps, tg);
+            trav_lane<true>(r, a, stk, c_ovf);
+            if (a.n_sliver_groups > 0) sliver_pass(r, a, c_leaf);
+            // the render's grazing-hit rule (trace.hip "Culling"): traced again on the uncull'd binary path
+            if (r.fin && r.fid >= 0 && r.mode == TM_CLOSEST && a.graze &&
+                grazing(Surf{a.shade[3 * r.fid + 1].w, a.shade[3 * r.fid + 2].w}, r.d)) {
+                trav_begin(r, ro, rd, r.mode, a.boxes_finite != 0, a.emit_root, a.cull_eps, true);
+                trav_lane<true>(r, a, stk, c_ovf);
+            }
+            live = false;
+            fid = r.fid;
+            if (fid < 0) {   // the path ends in a miss: the product and the distance stand
+                nrm = v3(0.0f, 0.0f, 0.0f);
+                mtl = -1;
+            } else {   // hit prelude (path_tracer.cu:364-374)
+                const float4* sh = a.shade + 3 * fid;
+                const float4 s0 = sh[0], s1 = sh[1], s2 = sh[2];
+                const float w = 1.0f - r.u - r.v;
+                nrm = normalize(((w * v3(s0.x, s0.y, s0.z)) + (r.u * v3(s1.x, s1.y, s1.z))) + (r.v * v3(s2.x, s2.y, s2.z)));
+                mtl = __float_as_int(s0.w);
+                const float4 m0 = a.mtl[2 * mtl], m1 = a.mtl[2 * mtl + 1];
+                alb = alb * v3(m0.x, m0.y, m0.z);
+                depth = depth + r.t;
+                // new_direction's branch order (eta, then metallic); an emitter ends a path (:408-412)
+                const bool mirror = !(m1.x > 0.0f) && m1.y > 0.0f && !(m0.w > 0.0f);
+                if (mirror && k < p.max_bounces) {
+                    ro = ro + (r.t * rd);   // k_trace's advance (:372)
+                    rd = reflect_dir(rd, nrm);
+                    tg = grazing(a.graze ? Surf{s1.w, s2.w} : no_surface(), rd);
+                    ++k;
+                    live = true;
+                }
+            }
+        }
+    }
+    // the statistics, as k_temporal's: one integer atomic each per wave over the spread counters
+    const unsigned long long found = __ballot(k > 0);
+    if (found) {   // (wave-uniform)
+        int deep = k;
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) deep = max(deep, __shfl_xor(deep, s, 64));
+        if (lane == 0) {
+            const unsigned slot = ((unsigned)blockIdx.y * gridDim.x + (unsigned)blockIdx.x) % (unsigned)kTemporalSlots;
+            atomicAdd(p.followed + (size_t)slot * kTemporalSlotStride, (unsigned long long)__popcll(found));
+            atomicMax(p.deepest + (size_t)slot * kTemporalSlotStride, (unsigned long long)deep);
+        }
+    }
+    if (!inside) return;
+    const size_t off = (size_t)x + (size_t)y * (size_t)a.width;
+    if (o.albedo) {
+        o.albedo[3 * off] = alb.x;
+        o.albedo[3 * off + 1] = alb.y;
+        o.albedo[3 * off + 2] = alb.z;
+    }
+    if (o.normal) {
+        o.normal[3 * off] = nrm.x;
+        o.normal[3 * off + 1] = nrm.y;
+        o.normal[3 * off + 2] = nrm.z;
+    }
+    if (o.depth) o.depth[off] = depth;
+    if (o.face) o.face[off] = fid;
+    if (o.material) o.material[off] = mtl;
+    if (p.bounces) p.bounces[off] = k;
+}
+
+hipError_t launch_aov_path(const TraceArgs& a, const AovArgs& o, const AovPathArgs& p, hipStream_t s) {
+    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+    const size_t lds = (size_t)kAovLdsSlots * 256 * sizeof(int);
+    hipLaunchKernelGGL(k_aov_path, grid, dim3(256), lds, s, a, o, p);
     return hipGetLastError();
 }
 

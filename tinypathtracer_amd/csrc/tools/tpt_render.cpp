@@ -6,7 +6,7 @@
 //   tpt_render scene.gltf [--width W] [--height H] [--spp N] [--depth D]
 //              [--seed S] [--env equirect.jpg|.ppm|--sky] [--out prefix] [--device i]
 //              [--frames F [--progressive]] [--aov] [--denoise [iterations]]
-//              [--temporal] [--yaw DEG] [--svgf [iterations]]
+//              [--temporal] [--yaw DEG] [--svgf [iterations]] [--aov-path [bounces]]
 //              [--move OBJ DX DY DZ] [--spin OBJ DEG]
 // --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
 // <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
@@ -18,6 +18,10 @@
 // hosts' defaults): with --temporal of the accumulated frame, by that pass's variance
 // and history length; without it of the written frame, on the spatial variance
 // estimate alone.  --denoise and --svgf may be combined: both files are written.
+// --aov-path follows perfect mirrors (tpt_render_aov_path, up to `bounces` of them, default 8):
+// <out>_albedo.pfm, <out>_normal.pfm and <out>_depth.pfm are written from the path buffers,
+// with <out>_bounces.pfm, and --denoise / --svgf take them as guides; --temporal keeps the
+// first-hit buffers, whose surface it reprojects.
 // --yaw DEG turns the camera about its own origin and up axis by DEG per frame.
 // --move OBJ DX DY DZ translates object OBJ (its index in the scene's object order: the
 // mesh nodes of the glTF file in node order) by (DX, DY, DZ) world units per frame; --spin
@@ -84,7 +88,7 @@ const char* kUsage =
     "usage: %s scene.gltf [--width W] [--height H] [--spp N] [--depth D] [--seed S] "
     "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]] "
     "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]] "
-    "[--move OBJ DX DY DZ] [--spin OBJ DEG]\n";
+    "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG]\n";
 
 // The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
 tpt::Camera yawed(const tpt::Camera& base, double deg) {
@@ -153,7 +157,8 @@ int main(int argc, char** argv) {
     }
     std::string scene_file = argv[1], env_file, out = "out";
     int W = 1920, H = 1080, spp = 64, depth = 8, device = 0, frames = 1;
-    bool progressive = false, aov = false, denoise = false, temporal = false, svgf = false;
+    bool progressive = false, aov = false, denoise = false, temporal = false, svgf = false, aov_path = false;
+    int path_bounces = 8;
     double yaw = 0.0;
     std::vector<ObjectMotion> motions;   // --move / --spin, one entry per object named
     auto motion_of = [&](uint32_t object) -> ObjectMotion& {
@@ -186,6 +191,10 @@ int main(int argc, char** argv) {
         else if (a == "--progressive") progressive = true;
         else if (a == "--aov") aov = true;
         else if (a == "--temporal") temporal = true;
+        else if (a == "--aov-path") {
+            aov_path = true;   // an optional bounce cap follows
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') path_bounces = std::stoi(argv[++i]);
+        }
         else if (a == "--yaw") yaw = std::stod(next());
         else if (a == "--move") {
             ObjectMotion& om = motion_of((uint32_t)std::stoul(next()));
@@ -277,9 +286,15 @@ int main(int argc, char** argv) {
         }
         write_ppm(out + ".ppm", f.bgra, W, H);
         write_pfm(out + ".pfm", f.radiance, W, H, 3);
-        if (aov || denoise || svgf) {
-            if (!temporal) g = pt.renderAOV(d, cam);
-            if (aov) {
+        if (aov || aov_path || denoise || svgf) {
+            if (aov_path) {   // the filters' guides follow the mirrors (the temporal pass above did not)
+                std::vector<int32_t> bounces;
+                g = pt.renderAOVPath(d, cam, path_bounces, &bounces);
+                write_pfm(out + "_bounces.pfm", std::vector<float>(bounces.begin(), bounces.end()), W, H, 1);
+            } else if (!temporal) {
+                g = pt.renderAOV(d, cam);
+            }
+            if (aov || aov_path) {
                 write_pfm(out + "_albedo.pfm", g.albedo, W, H, 3);
                 write_pfm(out + "_normal.pfm", g.normal, W, H, 3);
                 write_pfm(out + "_depth.pfm", g.depth, W, H, 1);
