@@ -161,6 +161,41 @@ def test_aov_nullable_outputs(frames):
     assert np.array_equal(_bits(depth), _bits(gpu["depth"]))
 
 
+@pytest.mark.parametrize("w,h", [(17, 16), (37, 29)])
+def test_same_camera_reprojects_every_pixel_onto_itself(frames, w, h):
+    """The feature buffers' ray and the temporal pass's are one text (post.hip centre_ray):
+    a second frame of a static scene from the same camera -- box, the scene's camera yawed 7
+    degrees -- finds its history at its own pixel everywhere, hit or miss, and where the
+    motion vector is asked for it is zero.  tests/temporal_ref.py, fed the same buffers, says
+    the same of this camera (with the oracle's buffers too: 272 of 272 and 1,073 of 1,073)."""
+    from tests import temporal_ref as TR
+    s, d, _, _, _ = frames["box"]
+    cam = s.m_camera.yawed(7.0)
+    cd = {"c2w": np.asarray(cam.c2w, np.float32), "vfov": cam.vfov, "aspect": cam.aspect}
+    params = dict(alpha=0.1, depth_tol=0.1, normal_min=0.9, max_history=32, demodulate=True)
+    pt = T.PathTracer("", w, h, 0)
+    aov = pt.renderAOV(d, cam)
+    assert 0.25 < (aov["face"] >= 0).mean() < 0.75         # hits and misses both
+    rng = np.random.default_rng(5)
+    rads = [rng.uniform(0.0, 2.0, (h, w, 3)).astype(np.float32) for _ in range(2)]
+    state = None
+    for rad in rads:
+        ref = TR.temporal_ref(state, cd, rad, aov, **params)
+        state = ref["state"]
+    assert ref["decidable"].all() and ref["reprojected"].all()
+    for motion in (False, True):
+        hist = T.History(d, w, h)
+        for rad in rads:
+            st = {}
+            n = np.zeros((h, w), np.float32)
+            mv = np.full((h, w, 2), -7.0, np.float32) if motion else None
+            pt.temporal(hist, cam, rad, aov, history_len=n, stats=st, motion=motion, motion_out=mv, **params)
+        hist.close()
+        assert st["reprojected"] == w * h and (n == 2.0).all(), motion
+        if motion:
+            assert (mv == 0.0).all()
+
+
 def test_aov_refusals(frames):
     s, d, pt, _, _ = frames["box"]
     L = T.lib()

@@ -485,6 +485,28 @@ AOV_PATH_DEFAULTS = {"max_bounces": 8}
 _PLANES.update(bounces=(1, "int32"))
 
 
+def _aov_out(out, width, height, extra=()):
+    """renderAOV's / renderAOVPath's `out`: the default buffers for None, the unknown-key check."""
+    keys = tuple(AOV_LAYOUT) + tuple(extra)
+    if out is None:
+        return {k: np.zeros((height, width) + ((3,) if _PLANES[k][0] == 3 else ()), _PLANES[k][1]) for k in keys}
+    unknown = set(out) - set(keys)
+    if unknown:
+        raise ValueError(f"unknown feature buffers {sorted(unknown)}")
+    return out
+
+
+def _take_guides(aov, keys, width, height):
+    """The feature planes `keys` of aov that are there, checked, as the library's tpt_aov."""
+    g = _lib.Aov()
+    for k in keys:
+        buf = aov.get(k)
+        if buf is not None:
+            _check_plane(k, buf, width, height)
+            setattr(g, k, _addr(buf))
+    return g
+
+
 def _check_plane(name, buf, width, height):
     """The library reads / writes width * height * channels elements behind the
     pointer: refuse a buffer of another size or element type."""
@@ -654,18 +676,8 @@ class PathTracer:
         if not d_scene.built:
             d_scene.build()
         W, H = self.m_width, self.m_height
-        if out is None:
-            out = {"albedo": np.zeros((H, W, 3), np.float32), "normal": np.zeros((H, W, 3), np.float32),
-                   "depth": np.zeros((H, W), np.float32), "face": np.zeros((H, W), np.int32),
-                   "material": np.zeros((H, W), np.int32)}
-        unknown = set(out) - set(AOV_LAYOUT)
-        if unknown:
-            raise ValueError(f"unknown feature buffers {sorted(unknown)}")
-        a = _lib.Aov()
-        for k, buf in out.items():
-            if buf is not None:
-                _check_plane(k, buf, W, H)
-                setattr(a, k, _addr(buf))
+        out = _aov_out(out, W, H)
+        a = _take_guides(out, out, W, H)
         ms = C.c_double()
         cam = camera.to_c()
         check(lib().tpt_render_aov(d_scene.handle, C.byref(cam), W, H, C.byref(a), C.byref(ms)))
@@ -688,27 +700,15 @@ class PathTracer:
         if not d_scene.built:
             d_scene.build()
         W, H = self.m_width, self.m_height
-        if out is None:
-            out = {"albedo": np.zeros((H, W, 3), np.float32), "normal": np.zeros((H, W, 3), np.float32),
-                   "depth": np.zeros((H, W), np.float32), "face": np.zeros((H, W), np.int32),
-                   "material": np.zeros((H, W), np.int32), "bounces": np.zeros((H, W), np.int32)}
-        unknown = set(out) - set(AOV_LAYOUT) - {"bounces"}
-        if unknown:
-            raise ValueError(f"unknown feature buffers {sorted(unknown)}")
-        a = _lib.Aov()
-        bounces = None
-        for k, buf in out.items():
-            if buf is None:
-                continue
-            _check_plane(k, buf, W, H)
-            if k == "bounces":
-                bounces = _addr(buf)
-            else:
-                setattr(a, k, _addr(buf))
+        out = _aov_out(out, W, H, extra=("bounces",))
+        a = _take_guides(out, [k for k in out if k != "bounces"], W, H)
+        bounces = out.get("bounces")
+        if bounces is not None:
+            _check_plane("bounces", bounces, W, H)
         p = _lib.AovPathParams(int(max_bounces), 0)
         st = _lib.AovPathStats()
         cam = camera.to_c()
-        check(lib().tpt_render_aov_path(d_scene.handle, C.byref(cam), W, H, C.byref(p), C.byref(a), bounces,
+        check(lib().tpt_render_aov_path(d_scene.handle, C.byref(cam), W, H, C.byref(p), C.byref(a), _addr(bounces),
                                         C.byref(st)))
         if stats is not None:
             stats.update(st.as_dict())
@@ -730,12 +730,7 @@ class PathTracer:
         pack_ms, filter_ms, resolve_ms."""
         W, H = self.m_width, self.m_height
         _check_plane("radiance", radiance, W, H)
-        g = _lib.Aov()
-        for k in ("albedo", "normal", "depth"):
-            buf = aov.get(k)
-            if buf is not None:
-                _check_plane(k, buf, W, H)
-                setattr(g, k, _addr(buf))
+        g = _take_guides(aov, ("albedo", "normal", "depth"), W, H)
         if out is None:
             out = np.zeros((H, W, 3), np.float32)
         _check_plane("radiance", out, W, H)
@@ -777,12 +772,8 @@ class PathTracer:
         if (history.width, history.height) != (W, H):
             raise ValueError(f"the history is {history.width} x {history.height}, the frame {W} x {H}")
         _check_plane("radiance", radiance, W, H)
-        g = _lib.Aov()
-        for k in (("albedo",) if demodulate else ()) + ("normal", "depth", "material") + (("face",) if motion else ()):
-            buf = aov.get(k)
-            if buf is not None:
-                _check_plane(k, buf, W, H)
-                setattr(g, k, _addr(buf))
+        g = _take_guides(aov, (("albedo",) if demodulate else ()) + ("normal", "depth", "material") +
+                         (("face",) if motion else ()), W, H)
         if out is None:
             out = np.zeros((H, W, 3), np.float32)
         _check_plane("radiance", out, W, H)
@@ -828,12 +819,7 @@ class PathTracer:
         if history_len is not None and variance is None:
             raise ValueError("history_len needs a variance")
         _check_plane("radiance", radiance, W, H)
-        g = _lib.Aov()
-        for k in ("albedo", "normal", "depth") if demodulate else ("normal", "depth"):
-            buf = aov.get(k)
-            if buf is not None:
-                _check_plane(k, buf, W, H)
-                setattr(g, k, _addr(buf))
+        g = _take_guides(aov, ("albedo", "normal", "depth") if demodulate else ("normal", "depth"), W, H)
         if out is None:
             out = np.zeros((H, W, 3), np.float32)
         _check_plane("radiance", out, W, H)

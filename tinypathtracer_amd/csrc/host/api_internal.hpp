@@ -168,7 +168,7 @@ private:
         const void* dev;
         size_t bytes;
     };
-    static constexpr int kMaxBack = 8;   // (tpt_render_aov has five outputs)
+    static constexpr int kMaxBack = 8;   // (tpt_render_aov_path has six outputs)
     Back back[kMaxBack];
     int n_back = 0;
     template <class T>
@@ -182,6 +182,35 @@ private:
         if (down) back[n_back++] = {p, buf.p, count * sizeof(T)};
         *dev = buf.p;
         return hipSuccess;
+    }
+};
+
+// The counters of the post-pass's statistics (post.hip spread_slot): `sets` sets of
+// kTemporalSlots words, kTemporalSlotStride apart, on the device, and their pinned copy on the
+// host.  zero() before the kernel, fetch() after it, sum() / max() once the stream has run.
+struct SpreadCounters {
+    static constexpr size_t kWords = (size_t)tpt::kTemporalSlots * tpt::kTemporalSlotStride;
+    DevBuf<unsigned long long> dev;
+    HostPinned<unsigned long long> host;
+    hipError_t alloc(int sets) {
+        const hipError_t e = dev.alloc((size_t)sets * kWords);
+        return e != hipSuccess ? e : host.alloc((size_t)sets * kWords);
+    }
+    unsigned long long* set(int k) const { return dev.p + (size_t)k * kWords; }
+    hipError_t zero(hipStream_t st) { return hipMemsetAsync(dev.p, 0, dev.n * sizeof(unsigned long long), st); }
+    hipError_t fetch(hipStream_t st) {
+        return hipMemcpyAsync(host.p, dev.p, dev.n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+    }
+    unsigned long long word(int set, int k) const { return host.p[(size_t)set * kWords + (size_t)k * tpt::kTemporalSlotStride]; }
+    unsigned long long sum(int set) const {
+        unsigned long long r = 0;
+        for (int k = 0; k < tpt::kTemporalSlots; ++k) r += word(set, k);
+        return r;
+    }
+    unsigned long long max(int set) const {
+        unsigned long long r = 0;
+        for (int k = 0; k < tpt::kTemporalSlots; ++k) r = std::max(r, word(set, k));
+        return r;
     }
 };
 
@@ -291,7 +320,7 @@ struct tpt_env {
 struct tpt_scene {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[5] = {};                  // tpt_render uses four, tpt_denoise_svgf's four kernels all five
     int32_t n_faces = 0, n_vertices = 0, n_objects = 0, n_materials = 0, n_lights = 0;
     bool built = false;
     int32_t stack_depth = 0;
@@ -378,20 +407,16 @@ struct tpt_scene {
     DevBuf<float> dn_rad, dn_f3[2], dn_depth;   // radiance in / out; albedo, normal; depth
     DevBuf<uint8_t> dn_bgra;
     // tpt_denoise_svgf: the planes and staging above, and of its own the staging of the variance
-    // (in and out share it), of the history length, the counters of SvgfArgs::estimated and a fifth event
+    // (in and out share it), of the history length and the counters of SvgfArgs::estimated
     DevBuf<float> sv_var, sv_len;
-    DevBuf<unsigned long long> sv_count;
-    HostPinned<unsigned long long> sv_h_count;
-    hipEvent_t sv_ev = nullptr;
+    SpreadCounters sv_count;
     // tpt_render_aov_path: tpt_render_aov's staging above, and of its own the staging of the bounce
-    // counts and the counters of AovPathArgs::followed and ::deepest (one allocation, followed first)
+    // counts and the counters of AovPathArgs::followed (set 0) and ::deepest (set 1)
     DevBuf<int32_t> ap_bounces;
-    DevBuf<unsigned long long> ap_count;
-    HostPinned<unsigned long long> ap_h_count;
+    SpreadCounters ap_count;
 
     ~tpt_scene() {
         DeviceGuard g(device);
-        if (sv_ev) (void)hipEventDestroy(sv_ev);
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
         for (auto& e : lev)
@@ -451,8 +476,7 @@ struct tpt_history {
     DevBuf<float> st_rad, st_f3[2], st_depth, st_var, st_len;
     DevBuf<int32_t> st_mtl;
     DevBuf<uint8_t> st_bgra;
-    DevBuf<unsigned long long> count;       // the reprojected-pixel counters (TemporalArgs::reprojected)
-    HostPinned<unsigned long long> h_count;
+    SpreadCounters count;                   // the reprojected pixels (TemporalArgs::reprojected)
     // tpt_temporal_motion: the scene's vert_trans as they were at the previous call (empty: no
     // state), the face -> object table (built once from the lut), the objects' records
     // (tpt_motion_matrices) on both sides, device staging of the face guide and of motion_out

@@ -8,8 +8,6 @@
 
 namespace {
 
-constexpr size_t kCountWords = (size_t)tpt::kTemporalSlots * tpt::kTemporalSlotStride;
-
 // Inverse of a column-major 4x4 matrix by Gauss-Jordan elimination with partial
 // pivoting in double, rounded to float.  false: singular.
 bool invert4(const float* m, float* out) {
@@ -40,6 +38,46 @@ bool invert4(const float* m, float* out) {
     return true;
 }
 
+// The time between two events of a stream that has run, as the stats structs hold it.
+hipError_t elapsed_ms(hipEvent_t e0, hipEvent_t e1, double* out) {
+    float ms = 0.0f;
+    const hipError_t e = hipEventElapsedTime(&ms, e0, e1);
+    if (e == hipSuccess) *out = ms;
+    return e;
+}
+
+// The scene, the camera and the whole frame as the feature-buffer kernels take them.
+tpt::TraceArgs frame_trace_args(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_t H) {
+    tpt::TraceArgs a{};
+    fill_trace_args(s, nullptr, cam, a);
+    a.width = W;
+    a.height = H;
+    a.inv_w = 1.0f / (float)W;
+    a.inv_h = 1.0f / (float)H;
+    return a;
+}
+
+// The five feature planes of `out` as the kernels' outputs: host ones through the scene's staging.
+hipError_t stage_aov(Staging& sg, tpt_scene* s, const tpt_aov* out, size_t npix, tpt::AovArgs& o) {
+    hipError_t e = sg.out(s->aov_f3[0], out->albedo, 3 * npix, &o.albedo);
+    if (e == hipSuccess) e = sg.out(s->aov_i[0], out->face, npix, &o.face);
+    if (e == hipSuccess) e = sg.out(s->aov_f3[1], out->normal, 3 * npix, &o.normal);
+    if (e == hipSuccess) e = sg.out(s->aov_i[1], out->material, npix, &o.material);
+    if (e == hipSuccess) e = sg.out(s->aov_depth, out->depth, npix, &o.depth);
+    return e;
+}
+
+// What both a-trous filters make of their parameters: 1 / sigma^2 kept finite, sigma_z^2, and
+// whether steps 1 and 2 go through the LDS kernels.
+float inv_sq(double sigma) { return (float)std::min(1.0 / (sigma * sigma), 3.402823466e+38); }
+struct FilterConsts {
+    float inv_sn2, sz2;
+    bool use_lds;
+};
+FilterConsts filter_consts(float sigma_normal, float sigma_depth, bool direct) {
+    return {inv_sq(sigma_normal), (float)((double)sigma_depth * sigma_depth), !direct};
+}
+
 }  // namespace
 
 extern "C" {
@@ -60,29 +98,16 @@ tpt_status tpt_render_aov(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_
     DeviceGuard g(s->device);
     hipStream_t st = s->stream;
     const size_t npix = (size_t)W * (size_t)H;
-    tpt::TraceArgs a{};
-    fill_trace_args(s, nullptr, cam, a);
-    a.width = W;
-    a.height = H;
-    a.inv_w = 1.0f / (float)W;
-    a.inv_h = 1.0f / (float)H;
+    const tpt::TraceArgs a = frame_trace_args(s, cam, W, H);
     tpt::AovArgs o{};
     Staging sg(st);
-    HIP_OR_FAIL(sg.out(s->aov_f3[0], out->albedo, 3 * npix, &o.albedo));
-    HIP_OR_FAIL(sg.out(s->aov_i[0], out->face, npix, &o.face));
-    HIP_OR_FAIL(sg.out(s->aov_f3[1], out->normal, 3 * npix, &o.normal));
-    HIP_OR_FAIL(sg.out(s->aov_i[1], out->material, npix, &o.material));
-    HIP_OR_FAIL(sg.out(s->aov_depth, out->depth, npix, &o.depth));
+    HIP_OR_FAIL(stage_aov(sg, s, out, npix, o));
     HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
     HIP_OR_FAIL(tpt::launch_aov(a, o, st));
     HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
     HIP_OR_FAIL(sg.finish());
     HIP_OR_FAIL(hipStreamSynchronize(st));
-    if (trace_ms) {
-        float ms = 0.0f;
-        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-        *trace_ms = ms;
-    }
+    if (trace_ms) HIP_OR_FAIL(elapsed_ms(s->ev[0], s->ev[1], trace_ms));
     return TPT_OK;
 }
 
@@ -108,47 +133,28 @@ tpt_status tpt_render_aov_path(tpt_scene* s, const tpt_camera* cam, int32_t W, i
     DeviceGuard g(s->device);
     hipStream_t st = s->stream;
     const size_t npix = (size_t)W * (size_t)H;
-    tpt::TraceArgs a{};
-    fill_trace_args(s, nullptr, cam, a);
-    a.width = W;
-    a.height = H;
-    a.inv_w = 1.0f / (float)W;
-    a.inv_h = 1.0f / (float)H;
+    const tpt::TraceArgs a = frame_trace_args(s, cam, W, H);
     const tpt_aov none{};
-    const tpt_aov* q = out ? out : &none;
     tpt::AovArgs o{};
     tpt::AovPathArgs pa{};
     pa.max_bounces = p->max_bounces;
-    HIP_OR_FAIL(s->ap_count.alloc(2 * kCountWords));
-    HIP_OR_FAIL(s->ap_h_count.alloc(2 * kCountWords));
-    pa.followed = s->ap_count.p;
-    pa.deepest = s->ap_count.p + kCountWords;
+    HIP_OR_FAIL(s->ap_count.alloc(2));
+    pa.followed = s->ap_count.set(0);
+    pa.deepest = s->ap_count.set(1);
     Staging sg(st);
-    HIP_OR_FAIL(sg.out(s->aov_f3[0], q->albedo, 3 * npix, &o.albedo));
-    HIP_OR_FAIL(sg.out(s->aov_i[0], q->face, npix, &o.face));
-    HIP_OR_FAIL(sg.out(s->aov_f3[1], q->normal, 3 * npix, &o.normal));
-    HIP_OR_FAIL(sg.out(s->aov_i[1], q->material, npix, &o.material));
-    HIP_OR_FAIL(sg.out(s->aov_depth, q->depth, npix, &o.depth));
+    HIP_OR_FAIL(stage_aov(sg, s, out ? out : &none, npix, o));
     HIP_OR_FAIL(sg.out(s->ap_bounces, bounces_out, npix, &pa.bounces));
-    HIP_OR_FAIL(hipMemsetAsync(s->ap_count.p, 0, 2 * kCountWords * sizeof(unsigned long long), st));
+    HIP_OR_FAIL(s->ap_count.zero(st));
     HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
     HIP_OR_FAIL(tpt::launch_aov_path(a, o, pa, st));
     HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
     HIP_OR_FAIL(sg.finish());
-    HIP_OR_FAIL(hipMemcpyAsync(s->ap_h_count.p, s->ap_count.p, 2 * kCountWords * sizeof(unsigned long long),
-                               hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(s->ap_count.fetch(st));
     HIP_OR_FAIL(hipStreamSynchronize(st));
     if (stats) {
-        unsigned long long followed = 0, deepest = 0;
-        for (int k = 0; k < tpt::kTemporalSlots; ++k) {
-            followed += s->ap_h_count.p[(size_t)k * tpt::kTemporalSlotStride];
-            deepest = std::max(deepest, s->ap_h_count.p[kCountWords + (size_t)k * tpt::kTemporalSlotStride]);
-        }
-        float ms = 0.0f;
-        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-        stats->trace_ms = ms;
-        stats->followed = followed;
-        stats->deepest = (int32_t)deepest;
+        HIP_OR_FAIL(elapsed_ms(s->ev[0], s->ev[1], &stats->trace_ms));
+        stats->followed = s->ap_count.sum(0);
+        stats->deepest = (int32_t)s->ap_count.max(1);
     }
     return TPT_OK;
 }
@@ -200,17 +206,15 @@ tpt_status tpt_denoise(tpt_scene* s, int32_t W, int32_t H, const float* radiance
     f.guide = s->dn_guide.p;
     f.width = W;
     f.height = H;
-    constexpr double kFltMax = 3.402823466e+38;
-    f.inv_sn2 = (float)std::min(1.0 / ((double)p->sigma_normal * p->sigma_normal), kFltMax);
-    f.sz2 = (float)((double)p->sigma_depth * p->sigma_depth);
-    const bool use_lds = !(p->flags & TPT_DENOISE_DIRECT);
+    const FilterConsts fc = filter_consts(p->sigma_normal, p->sigma_depth, p->flags & TPT_DENOISE_DIRECT);
+    f.inv_sn2 = fc.inv_sn2;
+    f.sz2 = fc.sz2;
     for (int i = 0; i < p->iterations; ++i) {
         f.src = s->dn_color[i & 1].p;
         f.dst = s->dn_color[(i + 1) & 1].p;
         f.step = 1 << i;
-        const double sc = (double)p->sigma_color / (double)(1 << i);   // sigma_c,i = sigma_color 2^-i
-        f.inv_sc2 = (float)std::min(1.0 / (sc * sc), kFltMax);
-        HIP_OR_FAIL(tpt::launch_atrous(f, use_lds, st));
+        f.inv_sc2 = inv_sq((double)p->sigma_color / (double)(1 << i));   // sigma_c,i = sigma_color 2^-i
+        HIP_OR_FAIL(tpt::launch_atrous(f, fc.use_lds, st));
     }
     HIP_OR_FAIL(hipEventRecord(s->ev[2], st));
     d.color0 = s->dn_color[p->iterations & 1].p;
@@ -219,13 +223,9 @@ tpt_status tpt_denoise(tpt_scene* s, int32_t W, int32_t H, const float* radiance
     HIP_OR_FAIL(sg.finish());
     HIP_OR_FAIL(hipStreamSynchronize(st));
     if (stats) {
-        float ms = 0.0f;
-        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-        stats->pack_ms = ms;
-        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
-        stats->filter_ms = ms;
-        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
-        stats->resolve_ms = ms;
+        HIP_OR_FAIL(elapsed_ms(s->ev[0], s->ev[1], &stats->pack_ms));
+        HIP_OR_FAIL(elapsed_ms(s->ev[1], s->ev[2], &stats->filter_ms));
+        HIP_OR_FAIL(elapsed_ms(s->ev[2], s->ev[3], &stats->resolve_ms));
     }
     return TPT_OK;
 }
@@ -246,8 +246,7 @@ tpt_status tpt_history_create(tpt_scene* s, int32_t W, int32_t H, tpt_history** 
     const size_t npix = (size_t)W * (size_t)H;
     for (auto& set : h->state)
         for (auto& plane : set) HIP_OR_FAIL(plane.alloc(npix));
-    HIP_OR_FAIL(h->count.alloc(kCountWords));
-    HIP_OR_FAIL(h->h_count.alloc(kCountWords));
+    HIP_OR_FAIL(h->count.alloc(1));
     {   // tpt_temporal_motion: which object each face belongs to, and room for the objects' records
         std::vector<int32_t> fo((size_t)s->n_faces);
         for (int32_t o = 0; o < s->n_objects; ++o) {
@@ -355,17 +354,14 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
         a.prev[k] = h->state[from][k].p;
         a.next[k] = h->state[to][k].p;
     }
-    a.reprojected = h->count.p;
-    HIP_OR_FAIL(hipMemsetAsync(h->count.p, 0, kCountWords * sizeof(unsigned long long), st));
+    a.reprojected = h->count.set(0);
+    HIP_OR_FAIL(h->count.zero(st));
     HIP_OR_FAIL(hipEventRecord(h->ev[0], st));
     HIP_OR_FAIL(motion ? tpt::launch_temporal_motion(a, mo, st) : tpt::launch_temporal(a, st));
     HIP_OR_FAIL(hipEventRecord(h->ev[1], st));
     HIP_OR_FAIL(sg.finish());
-    HIP_OR_FAIL(hipMemcpyAsync(h->h_count.p, h->count.p, kCountWords * sizeof(unsigned long long),
-                               hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(h->count.fetch(st));
     HIP_OR_FAIL(hipStreamSynchronize(st));
-    unsigned long long found = 0;
-    for (int k = 0; k < tpt::kTemporalSlots; ++k) found += h->h_count.p[(size_t)k * tpt::kTemporalSlotStride];
     // the new state, this camera and the scene's object transforms replace the old
     h->prev_vert_trans = s->h_vert_trans;
     h->cur = to;
@@ -373,10 +369,8 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
     if (!invert4(cam->c2w, h->prev_inv)) h->valid = false;   // a singular c2w: nothing can be reprojected into it
     h->prev = cc;
     if (stats) {
-        float ms = 0.0f;
-        HIP_OR_FAIL(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        stats->kernel_ms = ms;
-        stats->reprojected = found;
+        HIP_OR_FAIL(elapsed_ms(h->ev[0], h->ev[1], &stats->kernel_ms));
+        stats->reprojected = h->count.sum(0);
     }
     return TPT_OK;
 }
@@ -426,10 +420,8 @@ tpt_status tpt_denoise_svgf(tpt_scene* s, int32_t W, int32_t H, const float* rad
     HIP_OR_FAIL(s->dn_color[0].alloc(npix));
     HIP_OR_FAIL(s->dn_color[1].alloc(npix));
     HIP_OR_FAIL(s->dn_guide.alloc(npix));
-    HIP_OR_FAIL(s->sv_count.alloc(kCountWords));
-    HIP_OR_FAIL(s->sv_h_count.alloc(kCountWords));
-    if (!s->sv_ev) HIP_OR_FAIL(hipEventCreate(&s->sv_ev));
-    constexpr double kFltMax = 3.402823466e+38;
+    HIP_OR_FAIL(s->sv_count.alloc(1));
+    const FilterConsts fc = filter_consts(p->sigma_normal, p->sigma_depth, p->flags & TPT_SVGF_DIRECT);
     tpt::SvgfArgs d{};
     d.npix = npix;
     d.width = W;
@@ -437,10 +429,10 @@ tpt_status tpt_denoise_svgf(tpt_scene* s, int32_t W, int32_t H, const float* rad
     d.demodulate = demod ? 1 : 0;
     d.passthrough = p->iterations == 0 ? 1 : 0;   // the input bit for bit, so no demodulation round trip
     d.min_history = (float)p->min_history;
-    d.inv_sn2 = (float)std::min(1.0 / ((double)p->sigma_normal * p->sigma_normal), kFltMax);
-    d.sz2 = (float)((double)p->sigma_depth * p->sigma_depth);
+    d.inv_sn2 = fc.inv_sn2;
+    d.sz2 = fc.sz2;
     d.guide = s->dn_guide.p;
-    d.estimated = s->sv_count.p;
+    d.estimated = s->sv_count.set(0);
     Staging sg(st);
     HIP_OR_FAIL(sg.in(s->dn_rad, radiance_in, 3 * npix, &d.radiance_in));
     HIP_OR_FAIL(sg.in(s->dn_f3[0], demod ? guides->albedo : nullptr, 3 * npix, &d.albedo));
@@ -454,7 +446,7 @@ tpt_status tpt_denoise_svgf(tpt_scene* s, int32_t W, int32_t H, const float* rad
     HIP_OR_FAIL(sg.out(s->sv_var, variance_out, npix, &d.variance_out));
     // alpha is untouched: the caller's bytes go up first
     HIP_OR_FAIL(sg.inout(s->dn_bgra, bgra_out, 4 * npix, &d.bgra));
-    HIP_OR_FAIL(hipMemsetAsync(s->sv_count.p, 0, kCountWords * sizeof(unsigned long long), st));
+    HIP_OR_FAIL(s->sv_count.zero(st));
     HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
     d.dst = s->dn_color[0].p;
     HIP_OR_FAIL(tpt::launch_svgf_pack(d, st));
@@ -472,37 +464,28 @@ tpt_status tpt_denoise_svgf(tpt_scene* s, int32_t W, int32_t H, const float* rad
     f.width = W;
     f.height = H;
     f.sigma_lum = p->sigma_lum;
-    f.inv_sn2 = d.inv_sn2;
-    f.sz2 = d.sz2;
-    const bool use_lds = !(p->flags & TPT_SVGF_DIRECT);
+    f.inv_sn2 = fc.inv_sn2;
+    f.sz2 = fc.sz2;
     for (int i = 0; i < p->iterations; ++i) {
         f.src = s->dn_color[cur].p;
         f.dst = s->dn_color[cur ^ 1].p;
         f.step = 1 << i;
-        HIP_OR_FAIL(tpt::launch_svgf_filter(f, use_lds, st));
+        HIP_OR_FAIL(tpt::launch_svgf_filter(f, fc.use_lds, st));
         cur ^= 1;
     }
     HIP_OR_FAIL(hipEventRecord(s->ev[3], st));
     d.src = s->dn_color[cur].p;
     HIP_OR_FAIL(tpt::launch_svgf_resolve(d, st));
-    HIP_OR_FAIL(hipEventRecord(s->sv_ev, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[4], st));
     HIP_OR_FAIL(sg.finish());
-    HIP_OR_FAIL(hipMemcpyAsync(s->sv_h_count.p, s->sv_count.p, kCountWords * sizeof(unsigned long long),
-                               hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(s->sv_count.fetch(st));
     HIP_OR_FAIL(hipStreamSynchronize(st));
     if (stats) {
-        unsigned long long found = 0;
-        for (int k = 0; k < tpt::kTemporalSlots; ++k) found += s->sv_h_count.p[(size_t)k * tpt::kTemporalSlotStride];
-        float ms = 0.0f;
-        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-        stats->pack_ms = ms;
-        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
-        stats->estimate_ms = ms;
-        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
-        stats->filter_ms = ms;
-        HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[3], s->sv_ev));
-        stats->resolve_ms = ms;
-        stats->estimated = found;
+        HIP_OR_FAIL(elapsed_ms(s->ev[0], s->ev[1], &stats->pack_ms));
+        HIP_OR_FAIL(elapsed_ms(s->ev[1], s->ev[2], &stats->estimate_ms));
+        HIP_OR_FAIL(elapsed_ms(s->ev[2], s->ev[3], &stats->filter_ms));
+        HIP_OR_FAIL(elapsed_ms(s->ev[3], s->ev[4], &stats->resolve_ms));
+        stats->estimated = s->sv_count.sum(0);
     }
     return TPT_OK;
 }

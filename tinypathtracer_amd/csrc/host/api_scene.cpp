@@ -536,7 +536,7 @@ tpt_status tpt_scene_create(const tpt_scene_desc* d_in, int device, tpt_scene** 
         return st;
     };
     hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    for (int i = 0; e == hipSuccess && i < 4; ++i) e = hipEventCreate(&s->ev[i]);
+    for (int i = 0; e == hipSuccess && i < 5; ++i) e = hipEventCreate(&s->ev[i]);
     if (e != hipSuccess) return cleanup(fail(TPT_ERR_HIP, std::string("stream/event: ") + hipGetErrorString(e)));
     {
         // the launch rules that key on the chip's resident lanes (launch_plan.cpp:

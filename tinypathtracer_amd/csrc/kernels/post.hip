@@ -1,15 +1,19 @@
-// post.hip -- what follows a render: the first-hit feature buffers (tpt_render_aov)
-// and the edge-avoiding a-trous wavelet denoiser (tpt_denoise; Dammertz et al. 2010,
-// DESIGN.md section 5 "Post-pass").
+// post.hip -- what follows a render (DESIGN.md section 5 "Post-pass"): the feature buffers
+// (tpt_render_aov, tpt_render_aov_path), the edge-avoiding a-trous wavelet denoiser
+// (tpt_denoise; Dammertz et al. 2010), temporal accumulation (tpt_temporal,
+// tpt_temporal_motion) and the variance-guided filter (tpt_denoise_svgf; Schied et al. 2017).
 //
-//  * k_aov: one lane per pixel in 16x16 tiles, each wave an 8x8 sub-tile as in
-//    k_trace (primary rays are coherent); the ray through the pixel centre --
-//    sampleRays (path_tracer.cu:42-59) with the jitter fixed at (0.5, 0.5), no RNG --
-//    walks the render's own closest-hit traversal exactly as k_trace_rays mode 1
-//    (trav_lane<true>, the sliver pass, the grazing re-trace), then the hit prelude
-//    of path_tracer.cu:364-374.  The LDS stack is k_trace_rays'.
-//  * k_aov_path: the same ray followed through perfect mirrors to the first surface
-//    that is none (tpt_render_aov_path), a wave looping until none of its lanes continues.
+//  * The steps that several kernels take are written once, ahead of them: the pixel of a
+//    lane, the pixel-centre ray, the closest-hit walk, the hit prelude, the feature-buffer
+//    write, the albedo floor of (de)modulation, the framebuffer write, the spread counters,
+//    the LDS staging of a tile and its halo, the guide terms, the launch shapes.  Their
+//    forms (results and the args struct by value, a scalar albedo floor) are the ones under
+//    which the kernels' instructions stayed what they were (tools/kernel_diff.py; DESIGN.md
+//    section 5 "One text per shared step" has the outcome per kernel).
+//  * k_aov / k_aov_path: one lane per pixel in 16x16 tiles; the ray through the pixel
+//    centre walks the render's own closest-hit traversal; k_aov_path follows it through
+//    perfect mirrors, a wave looping until none of its lanes continues.  The LDS stack
+//    is k_trace_rays'.
 //  * k_dn_pack / k_atrous / k_atrous_lds / k_dn_resolve: the filter.  Two float4
 //    planes per pixel (colour; normal + depth), one launch per iteration ping-ponging
 //    between two colour planes, no atomics.  Each tap is two 16-B loads per lane;
@@ -25,15 +29,20 @@
 
 namespace tpt {
 
-constexpr int kAovLdsSlots = 48;   // LDS stack slots per lane, as k_trace_rays; deeper ones private
+// ---- the shared steps ----
 
-__global__ __launch_bounds__(256) void k_aov(TraceArgs a, AovArgs o) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int x = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-    const int y = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (x >= a.width || y >= a.height) return;   // (no barrier below)
-    // sampleRays (path_tracer.cu:42-59), k_trace's camera section with ju = jv = 0.5
+// The lane's pixel in 16x16 tiles, each wave an 8x8 sub-tile as in k_trace (primary rays are coherent).
+__device__ __forceinline__ int2 tile_wave_xy(int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    return make_int2((int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3));
+}
+
+// The ray through the centre of pixel (x, y): sampleRays (path_tracer.cu:42-59), k_trace's
+// camera section with the jitter fixed at ju = jv = 0.5, no RNG.  Args: TraceArgs or
+// TemporalArgs, which hold the camera under the same names.  Reprojection is exact only
+// while the feature buffers' rays and the temporal pass's are the same bits: this is both.
+template <class Args>
+__device__ __forceinline__ void centre_ray(const Args& a, int x, int y, V3& ro, V3& rd) {
     float lx = 0.5f * 1.0f, lyf = 0.5f * 1.0f;
     lx = lx + (float)x;
     lyf = lyf + (float)y;
@@ -43,56 +52,167 @@ __global__ __launch_bounds__(256) void k_aov(TraceArgs a, AovArgs o) {
     lyf = lyf * a.sensor_h;
     float r4[4];
     mat4_vec4(a.c2w, lx - a.half_sw, lyf - a.half_sh, 0.0f - 1.0f, 0.0f, r4);
-    const V3 rd = normalize(v3(r4[0], r4[1], r4[2]));
-    const V3 ro = v3(a.origin[0], a.origin[1], a.origin[2]);
-    Trav r;
-    LaneStack<int> stk;
-    stk.lds = (TPT_LDS int*)lds + tid;
-    stk.nlds = kAovLdsSlots;
+    rd = normalize(v3(r4[0], r4[1], r4[2]));
+    ro = v3(a.origin[0], a.origin[1], a.origin[2]);
+}
+
+// The render's closest hit along (ro, rd), exactly as k_trace_rays mode 1: trav_lane<true>, the
+// sliver pass, and the render's grazing-hit rule (trace.hip "Culling"): a grazing hit is traced
+// again on the uncull'd binary path.  tg: the ray leaves a surface that it grazes.
+__device__ __forceinline__ void closest_hit(Trav& r, const TraceArgs& a, LaneStack<int>& stk, V3 ro, V3 rd, bool tg) {
     uint32_t c_ovf = 0, c_leaf = 0;
-    trav_begin(r, ro, rd, TM_CLOSEST, a.boxes_finite != 0, a.emit_root, a.cull_eps, false);   // the camera: no surface
+    trav_begin(r, ro, rd, TM_CLOSEST, a.boxes_finite != 0, a.emit_root, a.cull_eps, tg);
     trav_lane<true>(r, a, stk, c_ovf);
     if (a.n_sliver_groups > 0) sliver_pass(r, a, c_leaf);
-    // the render's grazing-hit rule (trace.hip "Culling"): traced again on the uncull'd binary path
     if (r.fin && r.fid >= 0 && r.mode == TM_CLOSEST && a.graze &&
         grazing(Surf{a.shade[3 * r.fid + 1].w, a.shade[3 * r.fid + 2].w}, r.d)) {
         trav_begin(r, ro, rd, r.mode, a.boxes_finite != 0, a.emit_root, a.cull_eps, true);
         trav_lane<true>(r, a, stk, c_ovf);
     }
-    const size_t off = (size_t)x + (size_t)y * (size_t)a.width;
-    V3 alb = v3(1.0f, 1.0f, 1.0f), nrm = v3(0.0f, 0.0f, 0.0f);   // miss: demodulation leaves the environment alone
-    float depth = 0.0f;
-    int mtl = -1;
-    if (r.fid >= 0) {   // hit prelude (path_tracer.cu:364-374)
-        const float4* sh = a.shade + 3 * r.fid;
-        const float4 s0 = sh[0], s1 = sh[1], s2 = sh[2];
-        const float w = 1.0f - r.u - r.v;
-        nrm = normalize(((w * v3(s0.x, s0.y, s0.z)) + (r.u * v3(s1.x, s1.y, s1.z))) + (r.v * v3(s2.x, s2.y, s2.z)));
-        mtl = __float_as_int(s0.w);
-        const float4 m0 = a.mtl[2 * mtl];
-        alb = v3(m0.x, m0.y, m0.z);
-        depth = r.t;
-    }
-    if (o.albedo) {
-        o.albedo[3 * off] = alb.x;
-        o.albedo[3 * off + 1] = alb.y;
-        o.albedo[3 * off + 2] = alb.z;
-    }
-    if (o.normal) {
-        o.normal[3 * off] = nrm.x;
-        o.normal[3 * off + 1] = nrm.y;
-        o.normal[3 * off + 2] = nrm.z;
-    }
+}
+
+// The hit prelude (path_tracer.cu:364-374) of the hit r holds: the shading normal, the
+// material id (returned), the material's first record (base colour; .w the emission) and the
+// face's grazing data.
+__device__ __forceinline__ int hit_prelude(const TraceArgs& a, const Trav& r, V3& nrm, float4& m0, Surf& face) {
+    const float4* sh = a.shade + 3 * r.fid;
+    const float4 s0 = sh[0], s1 = sh[1], s2 = sh[2];
+    const float w = 1.0f - r.u - r.v;
+    nrm = normalize(((w * v3(s0.x, s0.y, s0.z)) + (r.u * v3(s1.x, s1.y, s1.z))) + (r.v * v3(s2.x, s2.y, s2.z)));
+    const int mtl = __float_as_int(s0.w);
+    m0 = a.mtl[2 * mtl];
+    face = Surf{s1.w, s2.w};
+    return mtl;
+}
+
+// Pixel p of a plane of three floats per pixel.
+__device__ __forceinline__ void store3(float* f, size_t p, V3 v) {
+    f[3 * p] = v.x;
+    f[3 * p + 1] = v.y;
+    f[3 * p + 2] = v.z;
+}
+
+// One pixel of the feature buffers, each plane nullable.
+__device__ __forceinline__ void write_aov(const AovArgs& o, size_t off, V3 alb, V3 nrm, float depth, int fid, int mtl) {
+    if (o.albedo) store3(o.albedo, off, alb);
+    if (o.normal) store3(o.normal, off, nrm);
     if (o.depth) o.depth[off] = depth;
-    if (o.face) o.face[off] = r.fid;
+    if (o.face) o.face[off] = fid;
     if (o.material) o.material[off] = mtl;
 }
 
-hipError_t launch_aov(const TraceArgs& a, const AovArgs& o, hipStream_t s) {
-    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-    const size_t lds = (size_t)kAovLdsSlots * 256 * sizeof(int);
-    hipLaunchKernelGGL(k_aov, grid, dim3(256), lds, s, a, o);
+// Demodulation divides by max(albedo, kAlbedoFloor), re-modulation multiplies by the same.
+constexpr float kAlbedoFloor = 1e-3f;
+__device__ __forceinline__ float albedo_floor(float alb) { return fmaxf(alb, kAlbedoFloor); }
+
+// copyToFB's conventions as k_resolve: row 0 = top, B, G, R written, alpha untouched,
+// truncating to_uchar.  (x, y): the pixel, row 0 = bottom.
+__device__ __forceinline__ void write_bgr(uint8_t* bgra, int width, int height, size_t x, size_t y, V3 c) {
+    uint8_t* px = bgra + 4 * (((size_t)height - y - 1) * (size_t)width + x);
+    px[0] = to_uchar(c.z);
+    px[1] = to_uchar(c.y);
+    px[2] = to_uchar(c.x);
+}
+
+// The statistics' counters: kTemporalSlots words a cache line apart, a workgroup's chosen by
+// its index, added up (or their maximum taken) by the host: every wave of a 1080p frame adding
+// to one address would queue 32,400 atomics on it.  spread_count: one integer atomic per wave.
+__device__ __forceinline__ unsigned long long* spread_slot(unsigned long long* base) {
+    const unsigned slot = ((unsigned)blockIdx.y * gridDim.x + (unsigned)blockIdx.x) % (unsigned)kTemporalSlots;
+    return base + (size_t)slot * kTemporalSlotStride;
+}
+__device__ __forceinline__ void spread_count(unsigned long long* base, int tid, bool counted) {
+    const unsigned long long found = __ballot(counted);
+    if ((tid & 63) == 0 && found) atomicAdd(spread_slot(base), (unsigned long long)__popcll(found));
+}
+
+// tpt_denoise's two guide factors as one exponent: |dn|^2 / sigma_n^2 + dz^2 kz
+__device__ __forceinline__ float guide_kz(float z, float sz2) {   // 1 / (sigma_z^2 max(z^2, 1e-12)); finite: a centre tap's 0 * kz is 0
+    return fminf(1.0f / (sz2 * fmaxf(z * z, 1e-12f)), kRealMax);
+}
+__device__ __forceinline__ float guide_arg(float4 gp, float4 gq, float inv_sn2, float kz) {
+    const float nx = gq.x - gp.x, ny = gq.y - gp.y, nz = gq.z - gp.z, dz = gq.w - gp.w;
+    return (nx * nx + ny * ny + nz * nz) * inv_sn2 + (dz * dz) * kz;
+}
+
+// A 16x16 tile and its halo staged in LDS as the colour and the guide plane, T pixels a side
+// from (x0, y0), zeros outside the frame (never read as a tap, or read at weight 0).  The
+// barrier is the caller's.
+__device__ __forceinline__ void lds_put(TPT_LDS LdsF4* q, float4 v) {
+    q->x = v.x;
+    q->y = v.y;
+    q->z = v.z;
+    q->w = v.w;
+}
+template <int T, class Args>
+__device__ __forceinline__ void stage_tile(TPT_LDS LdsF4* sc, TPT_LDS LdsF4* sg, const Args a, int x0, int y0, int tid) {
+    for (int i = tid; i < T * T; i += 256) {
+        const int gx = x0 + i % T, gy = y0 + i / T;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g = c;
+        if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) {
+            const size_t q = (size_t)gy * (size_t)a.width + (size_t)gx;
+            c = a.src[q];
+            g = a.guide[q];
+        }
+        lds_put(sc + i, c);
+        lds_put(sg + i, g);
+    }
+}
+
+// The launch shapes: one lane per pixel in 16x16 tiles (block 256) or in 64-pixel row
+// segments (block (64, 4)), or one lane per pixel of the frame as a row of npix.
+static dim3 tile_grid(int w, int h) { return dim3((w + 15) / 16, (h + 15) / 16); }
+template <class... A>
+static hipError_t launch_tiles_or_rows(bool tiles, void (*kt)(A...), size_t lds, void (*kr)(A...), int w, int h,
+                                       hipStream_t s, const A&... a) {
+    if (tiles) hipLaunchKernelGGL(kt, tile_grid(w, h), dim3(256), lds, s, a...);
+    else hipLaunchKernelGGL(kr, dim3((w + 63) / 64, (h + 3) / 4), dim3(64, 4), 0, s, a...);
     return hipGetLastError();
+}
+template <class Args>
+static hipError_t launch_pixels(void (*k)(Args), const Args& a, hipStream_t s) {
+    hipLaunchKernelGGL(k, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+// An a-trous iteration: steps 1 and 2 through the LDS-staged kernel ((16 + 4 S)^2 pixels x 32 B) where use_lds.
+template <class Args>
+static hipError_t launch_filter_step(void (*lds1)(Args), void (*lds2)(Args), void (*direct)(Args), const Args& a,
+                                     bool use_lds, hipStream_t s) {
+    const int T = 16 + 4 * a.step;
+    return launch_tiles_or_rows(use_lds && (a.step == 1 || a.step == 2), a.step == 1 ? lds1 : lds2, (size_t)T * T * 32,
+                                direct, a.width, a.height, s, a);
+}
+
+// ---- the feature buffers ----
+
+constexpr int kAovLdsSlots = 48;   // LDS stack slots per lane, as k_trace_rays; deeper ones private
+constexpr size_t kAovLdsBytes = (size_t)kAovLdsSlots * 256 * sizeof(int);
+
+// tpt_render_aov: the pixel-centre ray's closest hit and its prelude.
+__global__ __launch_bounds__(256) void k_aov(TraceArgs a, AovArgs o) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int tid = threadIdx.x;
+    const int2 xy = tile_wave_xy(tid);
+    const int x = xy.x, y = xy.y;
+    if (x >= a.width || y >= a.height) return;   // (no barrier below)
+    V3 ro, rd;
+    centre_ray(a, x, y, ro, rd);
+    Trav r;
+    LaneStack<int> stk;
+    stk.lds = (TPT_LDS int*)lds + tid;
+    stk.nlds = kAovLdsSlots;
+    closest_hit(r, a, stk, ro, rd, false);   // the camera: no surface
+    V3 alb = v3(1.0f, 1.0f, 1.0f), nrm = v3(0.0f, 0.0f, 0.0f);   // miss: demodulation leaves the environment alone
+    float depth = 0.0f;
+    int mtl = -1;
+    if (r.fid >= 0) {
+        float4 m0;
+        Surf face;
+        mtl = hit_prelude(a, r, nrm, m0, face);
+        alb = v3(m0.x, m0.y, m0.z);
+        depth = r.t;
+    }
+    write_aov(o, (size_t)x + (size_t)y * (size_t)a.width, alb, nrm, depth, r.fid, mtl);
 }
 
 // k_aov continued through perfect mirrors (tpt_render_aov_path; DESIGN.md section 5
@@ -106,27 +226,16 @@ hipError_t launch_aov(const TraceArgs& a, const AovArgs& o, hipStream_t s) {
 // trace): the statistics are taken by the whole wave.
 __global__ __launch_bounds__(256) void k_aov_path(TraceArgs a, AovArgs o, AovPathArgs p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int x = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-    const int y = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    const int tid = threadIdx.x;
+    const int2 xy = tile_wave_xy(tid);
+    const int x = xy.x, y = xy.y;
     const bool inside = x < a.width && y < a.height;   // (no barrier below)
-    // sampleRays (path_tracer.cu:42-59), k_aov's camera section
-    float lx = 0.5f * 1.0f, lyf = 0.5f * 1.0f;
-    lx = lx + (float)x;
-    lyf = lyf + (float)y;
-    lx = lx * a.inv_w;
-    lyf = lyf * a.inv_h;
-    lx = lx * a.sensor_w;
-    lyf = lyf * a.sensor_h;
-    float r4[4];
-    mat4_vec4(a.c2w, lx - a.half_sw, lyf - a.half_sh, 0.0f - 1.0f, 0.0f, r4);
-    V3 rd = normalize(v3(r4[0], r4[1], r4[2]));
-    V3 ro = v3(a.origin[0], a.origin[1], a.origin[2]);
+    V3 ro, rd;
+    centre_ray(a, x, y, ro, rd);
     Trav r;
     LaneStack<int> stk;
     stk.lds = (TPT_LDS int*)lds + tid;
     stk.nlds = kAovLdsSlots;
-    uint32_t c_ovf = 0, c_leaf = 0;
     V3 alb = v3(1.0f, 1.0f, 1.0f), nrm = v3(0.0f, 0.0f, 0.0f);   // the product of the base colours so far
     float depth = 0.0f;                                          // the distance travelled so far
     int fid = -1, mtl = -1, k = 0;
@@ -134,27 +243,17 @@ __global__ __launch_bounds__(256) void k_aov_path(TraceArgs a, AovArgs o, AovPat
     bool live = inside;
     while (__ballot(live) != 0ull) {
         if (live) {
-            trav_begin(r, ro, rd, TM_CLOSEST, a.boxes_finite != 0, a.emit_root, a.cull_eps, tg);
-            trav_lane<true>(r, a, stk, c_ovf);
-            if (a.n_sliver_groups > 0) sliver_pass(r, a, c_leaf);
-            // the render's grazing-hit rule (trace.hip "Culling"): traced again on the uncull'd binary path
-            if (r.fin && r.fid >= 0 && r.mode == TM_CLOSEST && a.graze &&
-                grazing(Surf{a.shade[3 * r.fid + 1].w, a.shade[3 * r.fid + 2].w}, r.d)) {
-                trav_begin(r, ro, rd, r.mode, a.boxes_finite != 0, a.emit_root, a.cull_eps, true);
-                trav_lane<true>(r, a, stk, c_ovf);
-            }
+            closest_hit(r, a, stk, ro, rd, tg);
             live = false;
             fid = r.fid;
             if (fid < 0) {   // the path ends in a miss: the product and the distance stand
                 nrm = v3(0.0f, 0.0f, 0.0f);
                 mtl = -1;
-            } else {   // hit prelude (path_tracer.cu:364-374)
-                const float4* sh = a.shade + 3 * fid;
-                const float4 s0 = sh[0], s1 = sh[1], s2 = sh[2];
-                const float w = 1.0f - r.u - r.v;
-                nrm = normalize(((w * v3(s0.x, s0.y, s0.z)) + (r.u * v3(s1.x, s1.y, s1.z))) + (r.v * v3(s2.x, s2.y, s2.z)));
-                mtl = __float_as_int(s0.w);
-                const float4 m0 = a.mtl[2 * mtl], m1 = a.mtl[2 * mtl + 1];
+            } else {
+                float4 m0;
+                Surf face;
+                mtl = hit_prelude(a, r, nrm, m0, face);
+                const float4 m1 = a.mtl[2 * mtl + 1];
                 alb = alb * v3(m0.x, m0.y, m0.z);
                 depth = depth + r.t;
                 // new_direction's branch order (eta, then metallic); an emitter ends a path (:408-412)
@@ -162,64 +261,49 @@ __global__ __launch_bounds__(256) void k_aov_path(TraceArgs a, AovArgs o, AovPat
                 if (mirror && k < p.max_bounces) {
                     ro = ro + (r.t * rd);   // k_trace's advance (:372)
                     rd = reflect_dir(rd, nrm);
-                    tg = grazing(a.graze ? Surf{s1.w, s2.w} : no_surface(), rd);
+                    tg = grazing(a.graze ? face : no_surface(), rd);
                     ++k;
                     live = true;
                 }
             }
         }
     }
-    // the statistics, as k_temporal's: one integer atomic each per wave over the spread counters
+    // the statistics: one integer atomic each per wave over the spread counters
     const unsigned long long found = __ballot(k > 0);
     if (found) {   // (wave-uniform)
         int deep = k;
 #pragma unroll
         for (int s = 32; s > 0; s >>= 1) deep = max(deep, __shfl_xor(deep, s, 64));
-        if (lane == 0) {
-            const unsigned slot = ((unsigned)blockIdx.y * gridDim.x + (unsigned)blockIdx.x) % (unsigned)kTemporalSlots;
-            atomicAdd(p.followed + (size_t)slot * kTemporalSlotStride, (unsigned long long)__popcll(found));
-            atomicMax(p.deepest + (size_t)slot * kTemporalSlotStride, (unsigned long long)deep);
+        if ((tid & 63) == 0) {
+            atomicAdd(spread_slot(p.followed), (unsigned long long)__popcll(found));
+            atomicMax(spread_slot(p.deepest), (unsigned long long)deep);
         }
     }
     if (!inside) return;
     const size_t off = (size_t)x + (size_t)y * (size_t)a.width;
-    if (o.albedo) {
-        o.albedo[3 * off] = alb.x;
-        o.albedo[3 * off + 1] = alb.y;
-        o.albedo[3 * off + 2] = alb.z;
-    }
-    if (o.normal) {
-        o.normal[3 * off] = nrm.x;
-        o.normal[3 * off + 1] = nrm.y;
-        o.normal[3 * off + 2] = nrm.z;
-    }
-    if (o.depth) o.depth[off] = depth;
-    if (o.face) o.face[off] = fid;
-    if (o.material) o.material[off] = mtl;
+    write_aov(o, off, alb, nrm, depth, fid, mtl);
     if (p.bounces) p.bounces[off] = k;
 }
 
+hipError_t launch_aov(const TraceArgs& a, const AovArgs& o, hipStream_t s) {
+    hipLaunchKernelGGL(k_aov, tile_grid(a.width, a.height), dim3(256), kAovLdsBytes, s, a, o);
+    return hipGetLastError();
+}
+
 hipError_t launch_aov_path(const TraceArgs& a, const AovArgs& o, const AovPathArgs& p, hipStream_t s) {
-    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-    const size_t lds = (size_t)kAovLdsSlots * 256 * sizeof(int);
-    hipLaunchKernelGGL(k_aov_path, grid, dim3(256), lds, s, a, o, p);
+    hipLaunchKernelGGL(k_aov_path, tile_grid(a.width, a.height), dim3(256), kAovLdsBytes, s, a, o, p);
     return hipGetLastError();
 }
 
 // ---- the a-trous filter (DESIGN.md section 5 "Post-pass" holds the definition the tests pin) ----
 
-constexpr float kAlbedoFloor = 1e-3f;   // demodulation divides by max(albedo, this)
-
 __global__ __launch_bounds__(256) void k_dn_pack(DenoiseArgs a) {
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= a.npix) return;
-    float r = a.radiance_in[3 * p], g = a.radiance_in[3 * p + 1], b = a.radiance_in[3 * p + 2];
-    if (a.demodulate) {
-        r = r / fmaxf(a.albedo[3 * p], kAlbedoFloor);
-        g = g / fmaxf(a.albedo[3 * p + 1], kAlbedoFloor);
-        b = b / fmaxf(a.albedo[3 * p + 2], kAlbedoFloor);
-    }
-    a.color0[p] = make_float4(r, g, b, 0.0f);
+    V3 c = v3(a.radiance_in[3 * p], a.radiance_in[3 * p + 1], a.radiance_in[3 * p + 2]);
+    if (a.demodulate)
+        c = v3(c.x / albedo_floor(a.albedo[3 * p]), c.y / albedo_floor(a.albedo[3 * p + 1]), c.z / albedo_floor(a.albedo[3 * p + 2]));
+    a.color0[p] = make_float4(c.x, c.y, c.z, 0.0f);
     a.guide[p] = make_float4(a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2], a.depth[p]);
 }
 
@@ -234,10 +318,11 @@ struct Taps {
     __device__ __forceinline__ void begin(float4 c, float4 g, float sz2) {
         cp = c;
         gp = g;
-        kz = fminf(1.0f / (sz2 * fmaxf(g.w * g.w, 1e-12f)), kRealMax);   // (finite: the centre tap's 0 * kz is 0)
+        kz = guide_kz(g.w, sz2);
         sw = 0.0f;
         ar = ag = ab = 0.0f;
     }
+    // (guide_arg's two terms, added one by one to the colour term: guide_arg's own sum would round otherwise)
     __device__ __forceinline__ void tap(float hh, float4 cq, float4 gq, float inv_sc2, float inv_sn2) {
         const float dr = cq.x - cp.x, dg = cq.y - cp.y, db = cq.z - cp.z;
         const float nx = gq.x - gp.x, ny = gq.y - gp.y, nz = gq.z - gp.z, dz = gq.w - gp.w;
@@ -292,23 +377,7 @@ __global__ __launch_bounds__(256) void k_atrous_lds(AtrousArgs a) {
     TPT_LDS LdsF4* sg = sc + T * T;
     const int tid = threadIdx.x;
     const int x0 = (int)blockIdx.x * 16 - 2 * S, y0 = (int)blockIdx.y * 16 - 2 * S;
-    for (int i = tid; i < T * T; i += 256) {
-        const int gx = x0 + i % T, gy = y0 + i / T;
-        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g = c;
-        if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) {   // (outside the frame: never read as a tap)
-            const size_t q = (size_t)gy * (size_t)a.width + (size_t)gx;
-            c = a.src[q];
-            g = a.guide[q];
-        }
-        sc[i].x = c.x;
-        sc[i].y = c.y;
-        sc[i].z = c.z;
-        sc[i].w = c.w;
-        sg[i].x = g.x;
-        sg[i].y = g.y;
-        sg[i].z = g.z;
-        sg[i].w = g.w;
-    }
+    stage_tile<T>(sc, sg, a, x0, y0, tid);
     __syncthreads();
     const int tx = tid & 15, ty = tid >> 4;
     const int x = (int)blockIdx.x * 16 + tx, y = (int)blockIdx.y * 16 + ty;
@@ -331,55 +400,26 @@ __global__ __launch_bounds__(256) void k_atrous_lds(AtrousArgs a) {
     a.dst[(size_t)y * (size_t)a.width + (size_t)x] = t.end();
 }
 
-// Re-modulation, the radiance readout and copyToFB's conventions as k_resolve:
-// row 0 = top, B, G, R written, alpha untouched, truncating to_uchar.
+// Re-modulation, the radiance readout and the framebuffer (write_bgr).
 __global__ __launch_bounds__(256) void k_dn_resolve(DenoiseArgs a) {
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= a.npix) return;
-    const float4 c = a.color0[p];
-    float r = c.x, g = c.y, b = c.z;
-    if (a.demodulate) {
-        r = r * fmaxf(a.albedo[3 * p], kAlbedoFloor);
-        g = g * fmaxf(a.albedo[3 * p + 1], kAlbedoFloor);
-        b = b * fmaxf(a.albedo[3 * p + 2], kAlbedoFloor);
-    }
-    if (a.radiance_out) {
-        a.radiance_out[3 * p] = r;
-        a.radiance_out[3 * p + 1] = g;
-        a.radiance_out[3 * p + 2] = b;
-    }
+    const float4 c4 = a.color0[p];
+    V3 c = v3(c4.x, c4.y, c4.z);
+    if (a.demodulate)
+        c = v3(c.x * albedo_floor(a.albedo[3 * p]), c.y * albedo_floor(a.albedo[3 * p + 1]), c.z * albedo_floor(a.albedo[3 * p + 2]));
+    if (a.radiance_out) store3(a.radiance_out, p, c);
     if (a.bgra) {
-        const size_t y = p / (size_t)a.width, x = p - y * (size_t)a.width;
-        uint8_t* px = a.bgra + 4 * (((size_t)a.height - y - 1) * (size_t)a.width + x);
-        px[0] = to_uchar(b);
-        px[1] = to_uchar(g);
-        px[2] = to_uchar(r);
+        const size_t y = p / (size_t)a.width;
+        write_bgr(a.bgra, a.width, a.height, p - y * (size_t)a.width, y, c);
     }
 }
 
-hipError_t launch_denoise_pack(const DenoiseArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_dn_pack, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
+hipError_t launch_denoise_pack(const DenoiseArgs& a, hipStream_t s) { return launch_pixels(k_dn_pack, a, s); }
 hipError_t launch_atrous(const AtrousArgs& a, bool use_lds, hipStream_t s) {
-    if (use_lds && (a.step == 1 || a.step == 2)) {
-        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-        const int T = 16 + 4 * a.step;
-        const size_t lds = (size_t)T * T * 32;
-        if (a.step == 1) hipLaunchKernelGGL(k_atrous_lds<1>, grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL(k_atrous_lds<2>, grid, dim3(256), lds, s, a);
-    } else {
-        const dim3 grid((a.width + 63) / 64, (a.height + 3) / 4);
-        hipLaunchKernelGGL(k_atrous, grid, dim3(64, 4), 0, s, a);
-    }
-    return hipGetLastError();
+    return launch_filter_step(k_atrous_lds<1>, k_atrous_lds<2>, k_atrous, a, use_lds, s);
 }
-
-hipError_t launch_denoise_resolve(const DenoiseArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_dn_resolve, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
+hipError_t launch_denoise_resolve(const DenoiseArgs& a, hipStream_t s) { return launch_pixels(k_dn_resolve, a, s); }
 
 // ---- temporal reprojection and accumulation (DESIGN.md section 5 "Post-pass" holds the definition) ----
 
@@ -391,6 +431,8 @@ constexpr float kMinWsum = 1.0f / 16.0f;     // least sum of valid bilinear weig
 // #if blocks there.  Two compilations of one text and not a template parameter: with the
 // parameter, k_temporal's instructions came out in another order and in other registers
 // (tools/kernel_diff.py), and the post-pass's recorded times belong to the code as it was.
+// Its lane's pixel, ray, albedo floor, framebuffer write and counter are the shared steps above,
+// which leave all four instantiations' instructions as they were.
 #define TPT_TEMPORAL_MOTION 0
 #include "temporal_kernel.hpp"
 #undef TPT_TEMPORAL_MOTION
@@ -399,25 +441,10 @@ constexpr float kMinWsum = 1.0f / 16.0f;     // least sum of valid bilinear weig
 #undef TPT_TEMPORAL_MOTION
 
 hipError_t launch_temporal_motion(const TemporalArgs& a, const MotionArgs& mo, hipStream_t s) {
-    if (a.tiles) {
-        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-        hipLaunchKernelGGL(k_temporal_motion<true>, grid, dim3(256), 0, s, a, mo);
-    } else {
-        const dim3 grid((a.width + 63) / 64, (a.height + 3) / 4);
-        hipLaunchKernelGGL(k_temporal_motion<false>, grid, dim3(64, 4), 0, s, a, mo);
-    }
-    return hipGetLastError();
+    return launch_tiles_or_rows(a.tiles != 0, k_temporal_motion<true>, 0, k_temporal_motion<false>, a.width, a.height, s, a, mo);
 }
-
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t s) {
-    if (a.tiles) {
-        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-        hipLaunchKernelGGL(k_temporal<true>, grid, dim3(256), 0, s, a);
-    } else {
-        const dim3 grid((a.width + 63) / 64, (a.height + 3) / 4);
-        hipLaunchKernelGGL(k_temporal<false>, grid, dim3(64, 4), 0, s, a);
-    }
-    return hipGetLastError();
+    return launch_tiles_or_rows(a.tiles != 0, k_temporal<true>, 0, k_temporal<false>, a.width, a.height, s, a);
 }
 
 // ---- the variance-guided a-trous filter (Schied et al. 2017; DESIGN.md section 5 "Post-pass" holds the definition) ----
@@ -435,26 +462,14 @@ __device__ __forceinline__ float svgf_lum(float r, float g, float b) {   // k_te
     return (0.2126f * r + 0.7152f * g) + 0.0722f * b;
 }
 
-// tpt_denoise's two guide factors as one exponent: |dn|^2 / sigma_n^2 + dz^2 kz
-__device__ __forceinline__ float guide_kz(float z, float sz2) {   // 1 / (sigma_z^2 max(z^2, 1e-12)), finite as Taps::kz
-    return fminf(1.0f / (sz2 * fmaxf(z * z, 1e-12f)), kRealMax);
-}
-__device__ __forceinline__ float guide_arg(float4 gp, float4 gq, float inv_sn2, float kz) {
-    const float nx = gq.x - gp.x, ny = gq.y - gp.y, nz = gq.z - gp.z, dz = gq.w - gp.w;
-    return (nx * nx + ny * ny + nz * nz) * inv_sn2 + (dz * dz) * kz;
-}
-
 __global__ __launch_bounds__(256) void k_svgf_pack(SvgfArgs a) {
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= a.npix) return;
-    float r = a.radiance_in[3 * p], g = a.radiance_in[3 * p + 1], b = a.radiance_in[3 * p + 2];
-    if (a.demodulate) {
-        r = r / fmaxf(a.albedo[3 * p], kAlbedoFloor);
-        g = g / fmaxf(a.albedo[3 * p + 1], kAlbedoFloor);
-        b = b / fmaxf(a.albedo[3 * p + 2], kAlbedoFloor);
-    }
+    V3 c = v3(a.radiance_in[3 * p], a.radiance_in[3 * p + 1], a.radiance_in[3 * p + 2]);
+    if (a.demodulate)
+        c = v3(c.x / albedo_floor(a.albedo[3 * p]), c.y / albedo_floor(a.albedo[3 * p + 1]), c.z / albedo_floor(a.albedo[3 * p + 2]));
     const float v = a.variance_in ? fmaxf(a.variance_in[p], 0.0f) : 0.0f;
-    a.dst[p] = make_float4(r, g, b, v);
+    a.dst[p] = make_float4(c.x, c.y, c.z, v);
     a.guide[p] = make_float4(a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2], a.depth[p]);
 }
 
@@ -484,12 +499,7 @@ __global__ __launch_bounds__(256) void k_svgf_estimate(SvgfArgs a) {
             is_short = N < a.min_history;
         }
     }
-    // the statistic, as k_temporal's: one integer atomic per wave over the spread counters
-    const unsigned long long found = __ballot(is_short);
-    if ((tid & 63) == 0 && found) {
-        const unsigned slot = ((unsigned)blockIdx.y * gridDim.x + (unsigned)blockIdx.x) % (unsigned)kTemporalSlots;
-        atomicAdd(a.estimated + (size_t)slot * kTemporalSlotStride, (unsigned long long)__popcll(found));
-    }
+    spread_count(a.estimated, tid, is_short);   // the statistic
     if (!__syncthreads_or(is_short ? 1 : 0)) {
         if (inside) a.dst[p] = a.src[p];
         return;
@@ -645,23 +655,7 @@ __global__ __launch_bounds__(256) void k_svgf_atrous_lds(SvgfFilterArgs a) {
     TPT_LDS LdsF4* sg = sc + T * T;
     const int tid = threadIdx.x;
     const int x0 = (int)blockIdx.x * 16 - 2 * S, y0 = (int)blockIdx.y * 16 - 2 * S;
-    for (int i = tid; i < T * T; i += 256) {
-        const int gx = x0 + i % T, gy = y0 + i / T;
-        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g = c;
-        if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) {   // (outside the frame: weight 0 below)
-            const size_t q = (size_t)gy * (size_t)a.width + (size_t)gx;
-            c = a.src[q];
-            g = a.guide[q];
-        }
-        sc[i].x = c.x;
-        sc[i].y = c.y;
-        sc[i].z = c.z;
-        sc[i].w = c.w;
-        sg[i].x = g.x;
-        sg[i].y = g.y;
-        sg[i].z = g.z;
-        sg[i].w = g.w;
-    }
+    stage_tile<T>(sc, sg, a, x0, y0, tid);
     __syncthreads();
     const int tx = tid & 15, ty = tid >> 4;
     const int x = (int)blockIdx.x * 16 + tx, y = (int)blockIdx.y * 16 + ty;
@@ -697,65 +691,39 @@ __global__ __launch_bounds__(256) void k_svgf_atrous_lds(SvgfFilterArgs a) {
     a.dst[(size_t)y * (size_t)a.width + (size_t)x] = t.end();
 }
 
-// Re-modulation and the outputs, with k_dn_resolve's conventions; passthrough
+// Re-modulation and the outputs, as k_dn_resolve; passthrough
 // (iterations 0): the radiance is the input bit for bit.
 __global__ __launch_bounds__(256) void k_svgf_resolve(SvgfArgs a) {
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= a.npix) return;
-    const float4 c = a.src[p];
-    float r = c.x, g = c.y, b = c.z;
+    const float4 c4 = a.src[p];
+    float r = c4.x, g = c4.y, b = c4.z;
     if (a.passthrough) {
         r = a.radiance_in[3 * p];
         g = a.radiance_in[3 * p + 1];
         b = a.radiance_in[3 * p + 2];
     } else if (a.demodulate) {
-        r = r * fmaxf(a.albedo[3 * p], kAlbedoFloor);
-        g = g * fmaxf(a.albedo[3 * p + 1], kAlbedoFloor);
-        b = b * fmaxf(a.albedo[3 * p + 2], kAlbedoFloor);
+        r = r * albedo_floor(a.albedo[3 * p]);
+        g = g * albedo_floor(a.albedo[3 * p + 1]);
+        b = b * albedo_floor(a.albedo[3 * p + 2]);
     }
-    if (a.radiance_out) {
-        a.radiance_out[3 * p] = r;
-        a.radiance_out[3 * p + 1] = g;
-        a.radiance_out[3 * p + 2] = b;
-    }
-    if (a.variance_out) a.variance_out[p] = c.w;
+    const V3 c = v3(r, g, b);
+    if (a.radiance_out) store3(a.radiance_out, p, c);
+    if (a.variance_out) a.variance_out[p] = c4.w;
     if (a.bgra) {
-        const size_t y = p / (size_t)a.width, x = p - y * (size_t)a.width;
-        uint8_t* px = a.bgra + 4 * (((size_t)a.height - y - 1) * (size_t)a.width + x);
-        px[0] = to_uchar(b);
-        px[1] = to_uchar(g);
-        px[2] = to_uchar(r);
+        const size_t y = p / (size_t)a.width;
+        write_bgr(a.bgra, a.width, a.height, p - y * (size_t)a.width, y, c);
     }
 }
 
-hipError_t launch_svgf_pack(const SvgfArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_svgf_pack, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
+hipError_t launch_svgf_pack(const SvgfArgs& a, hipStream_t s) { return launch_pixels(k_svgf_pack, a, s); }
 hipError_t launch_svgf_estimate(const SvgfArgs& a, hipStream_t s) {
-    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-    hipLaunchKernelGGL(k_svgf_estimate, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_svgf_estimate, tile_grid(a.width, a.height), dim3(256), 0, s, a);
     return hipGetLastError();
 }
-
 hipError_t launch_svgf_filter(const SvgfFilterArgs& a, bool use_lds, hipStream_t s) {
-    if (use_lds && (a.step == 1 || a.step == 2)) {
-        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-        const int T = 16 + 4 * a.step;
-        const size_t lds = (size_t)T * T * 32;
-        if (a.step == 1) hipLaunchKernelGGL(k_svgf_atrous_lds<1>, grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL(k_svgf_atrous_lds<2>, grid, dim3(256), lds, s, a);
-    } else {
-        const dim3 grid((a.width + 63) / 64, (a.height + 3) / 4);
-        hipLaunchKernelGGL(k_svgf_atrous, grid, dim3(64, 4), 0, s, a);
-    }
-    return hipGetLastError();
+    return launch_filter_step(k_svgf_atrous_lds<1>, k_svgf_atrous_lds<2>, k_svgf_atrous, a, use_lds, s);
 }
-
-hipError_t launch_svgf_resolve(const SvgfArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_svgf_resolve, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
+hipError_t launch_svgf_resolve(const SvgfArgs& a, hipStream_t s) { return launch_pixels(k_svgf_resolve, a, s); }
 
 }  // namespace tpt

@@ -26,9 +26,9 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
     int x, y, tid;
     if (TILES) {
         tid = (int)threadIdx.x;
-        const int lane = tid & 63, wave = tid >> 6;
-        x = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-        y = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+        const int2 xy = tile_wave_xy(tid);
+        x = xy.x;
+        y = xy.y;
     } else {
         tid = (int)threadIdx.y * 64 + (int)threadIdx.x;
         x = (int)blockIdx.x * 64 + (int)threadIdx.x;
@@ -52,18 +52,8 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
         float4 hc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // history: colour, N
         float hm1 = 0.0f, hm2 = 0.0f;
         if (a.has_prev) {
-            // the pixel-centre ray of the current camera: k_aov's text
-            float lx = 0.5f * 1.0f, lyf = 0.5f * 1.0f;
-            lx = lx + (float)x;
-            lyf = lyf + (float)y;
-            lx = lx * a.inv_w;
-            lyf = lyf * a.inv_h;
-            lx = lx * a.sensor_w;
-            lyf = lyf * a.sensor_h;
-            float r4[4];
-            mat4_vec4(a.c2w, lx - a.half_sw, lyf - a.half_sh, 0.0f - 1.0f, 0.0f, r4);
-            const V3 rd = normalize(v3(r4[0], r4[1], r4[2]));
-            const V3 ro = v3(a.origin[0], a.origin[1], a.origin[2]);
+            V3 ro, rd;   // the pixel-centre ray of the current camera: k_aov's
+            centre_ray(a, x, y, ro, rd);
             // a hit reprojects its world position, a miss its direction (a point at infinity)
 #if TPT_TEMPORAL_MOTION
             V3 X = hit ? ro + (z * rd) : rd;
@@ -171,7 +161,7 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
         }
         V3 c = in;
         if (a.demodulate) {
-            alb = v3(fmaxf(alb.x, kAlbedoFloor), fmaxf(alb.y, kAlbedoFloor), fmaxf(alb.z, kAlbedoFloor));
+            alb = v3(albedo_floor(alb.x), albedo_floor(alb.y), albedo_floor(alb.z));
             c = v3(in.x / alb.x, in.y / alb.y, in.z / alb.z);
         }
         const float L = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
@@ -202,20 +192,8 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
             mo.motion_out[2 * p + 1] = mvy;
         }
 #endif
-        if (a.bgra) {   // k_dn_resolve's conventions
-            uint8_t* px = a.bgra + 4 * (((size_t)a.height - (size_t)y - 1) * (size_t)a.width + (size_t)x);
-            px[0] = to_uchar(out.z);
-            px[1] = to_uchar(out.y);
-            px[2] = to_uchar(out.x);
-        }
+        if (a.bgra) write_bgr(a.bgra, a.width, a.height, (size_t)x, (size_t)y, out);
     }
-    // the statistic: one integer atomic per wave, spread over kTemporalSlots counters a cache
-    // line apart (the host adds them up): every wave of a 1080p frame adding to one address
-    // would queue 32,400 atomics on it
-    const unsigned long long found = __ballot(reproj);
-    if ((tid & 63) == 0 && found) {
-        const unsigned slot = ((unsigned)blockIdx.y * gridDim.x + (unsigned)blockIdx.x) % (unsigned)kTemporalSlots;
-        atomicAdd(a.reprojected + (size_t)slot * kTemporalSlotStride, (unsigned long long)__popcll(found));
-    }
+    spread_count(a.reprojected, tid, reproj);   // the statistic
 }
 
