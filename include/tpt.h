@@ -344,7 +344,8 @@ tpt_status tpt_render_aov(tpt_scene* scene, const tpt_camera* camera, int32_t wi
  * With max_bounces 0, and in a scene without a mirror, every buffer equals tpt_render_aov's
  * bit for bit.  Deterministic; no RNG is consumed.  tpt_denoise and tpt_denoise_svgf take
  * the result as `guides` unchanged.  tpt_temporal and tpt_temporal_motion do not: they
- * reproject the first hit and compare its material, so they stay on tpt_render_aov's buffers.
+ * reproject the first hit and compare its material, so they stay on tpt_render_aov's buffers
+ * (tpt_temporal_path is the pass for these).
  * stats: nullable.
  * TPT_ERR_INVALID_ARG: tpt_render_aov's refusals (out itself may be null when bounces_out is
  * not: at least one output is needed), null params, max_bounces outside 0..64, flags != 0. */
@@ -363,7 +364,20 @@ tpt_status tpt_render_aov_path(tpt_scene* scene, const tpt_camera* camera, int32
                                const tpt_aov_path_params* params, const tpt_aov* out, int32_t* bounces_out,
                                tpt_aov_path_stats* stats);
 
-#define TPT_DENOISE_DEMODULATE 0x1   /* filter radiance / max(albedo, 1e-3), multiply back afterwards */
+/* tpt_render_aov_path with where each path ended as a seventh output, for tpt_temporal_path:
+ *   points_out: W*H*3 floats (host or device memory as the others).  Where the path ends on a
+ *     surface (material >= 0): the world point origin_k + t d_k of that hit in float32, formed
+ *     as the walk advances an origin from mirror to mirror.  Where it leaves the scene
+ *     (material -1): the unit direction d_k of its last ray; with no mirror followed that is
+ *     the pixel-centre direction.
+ * Every other output is tpt_render_aov_path's bit for bit, and with points_out null the call is
+ * tpt_render_aov_path.  The refusals are tpt_render_aov_path's (points_out counts as an
+ * output). */
+tpt_status tpt_render_aov_path_points(tpt_scene* scene, const tpt_camera* camera, int32_t width, int32_t height,
+                                      const tpt_aov_path_params* params, const tpt_aov* out, int32_t* bounces_out,
+                                      float* points_out, tpt_aov_path_stats* stats);
+
+#define TPT_DENOISE_DEMODULATE 0x1  /* filter radiance / max(albedo, 1e-3), multiply back afterwards */
 #define TPT_DENOISE_DIRECT     0x2   /* A/B: steps 1 and 2 through the direct kernel too instead of the
                                         LDS-staged one (bit-identical output) */
 
@@ -487,6 +501,50 @@ tpt_status tpt_temporal_motion(tpt_history* h, const tpt_camera* camera, const f
                                const tpt_aov* guides, const tpt_temporal_params* params,
                                float* radiance_out, float* variance_out, float* history_len_out,
                                float* motion_out, uint8_t* bgra_out, tpt_temporal_stats* stats);
+
+/* tpt_temporal on mirror-path guides: accumulation that follows reflections in perfect mirrors
+ * under a moving camera (DESIGN.md section 5 "Temporal accumulation through mirrors" holds the
+ * definition).  tpt_temporal reprojects the first hit, so on a mirror it blends in the history
+ * of whatever the mirror showed from the previous camera.  Here each pixel carries its path:
+ *   path_guides: tpt_render_aov_path's normal, depth D (the whole path's length) and material,
+ *     all required; albedo (the path's product) only with TPT_TEMPORAL_DEMODULATE;
+ *   bounces: W*H, the mirrors followed k; points: W*H*3, tpt_render_aov_path_points' output P.
+ *     Both required, host or device memory as the others.
+ * A pixel with k = 0 takes tpt_temporal's rules, and its taps must have stored k' = 0 too.  A
+ * pixel with k > 0 that ends on a surface reprojects X = o + D d, the virtual image of its
+ * terminal point (a fixed world point for chains of planar mirrors); a tap is valid when
+ * k' = k, the terminal material is equal, n' . n >= normal_min, |D' - |X - o'|| <= depth_tol
+ * |X - o'|, and |P' - P| <= point_tol D sensor_h / height of this camera: the terminal world
+ * points lie within point_tol pixel footprints of each other.  A pixel with k > 0 whose path
+ * left the scene reprojects its direction as a miss does; a tap is valid when k' = k, m' = -1
+ * and |d' - d| <= point_tol sensor_h / height.  Everything else -- the taps, the 1/16 rule, the
+ * accumulation, demodulation, disocclusion, the outputs -- is tpt_temporal's.  On a curved
+ * mirror, or one with tilted shading normals, the point rule rejects what the virtual image
+ * gets wrong: such pixels mostly disocclude (tpt_denoise_svgf's short-history estimate is for
+ * those) instead of ghosting.
+ * The history keeps k in a word of its third plane that was unused and P in a fourth plane per
+ * set, allocated at the first tpt_temporal_path call: 32 B per pixel more, and up to 16 B more
+ * to stage host buffers.  In a scene without a mirror, or with max_bounces 0 buffers, the
+ * outputs and the state are tpt_temporal's bit for bit.  The entry points may alternate on one
+ * history: after a tpt_temporal or tpt_temporal_motion call every stored k' is 0, so the next
+ * tpt_temporal_path call disoccludes its k > 0 pixels.  Moving objects are not followed: after
+ * tpt_scene_set_transforms reset the history, or use tpt_temporal_motion on first-hit guides.
+ * TPT_ERR_INVALID_ARG (nothing is written and the history is left as it was): tpt_temporal's
+ * refusals, null bounces or points, point_tol not > 0. */
+typedef struct {
+    float   alpha;         /* as tpt_temporal_params */
+    float   depth_tol;
+    float   normal_min;
+    int32_t max_history;
+    int32_t flags;         /* TPT_TEMPORAL_* */
+    float   point_tol;     /* > 0, in pixel footprints */
+} tpt_temporal_path_params;
+
+tpt_status tpt_temporal_path(tpt_history* h, const tpt_camera* camera, const float* radiance_in,
+                             const tpt_aov* path_guides, const int32_t* bounces, const float* points,
+                             const tpt_temporal_path_params* params, float* radiance_out,
+                             float* variance_out, float* history_len_out, uint8_t* bgra_out,
+                             tpt_temporal_stats* stats);
 
 #define TPT_SVGF_DEMODULATE 0x1   /* filter radiance / max(albedo, 1e-3), multiply back afterwards */
 #define TPT_SVGF_DIRECT     0x2   /* A/B: steps 1 and 2 through the direct kernel too instead of the

@@ -189,6 +189,20 @@ inline tpt_temporal_params defaultTemporal() {
     return p;
 }
 
+// The hosts' defaults of accumulation through mirrors: defaultTemporal's, and point_tol by the
+// sweep of tools/temporal_path_quality.py (DESIGN.md section 5 "Temporal accumulation through mirrors")
+inline tpt_temporal_path_params defaultTemporalPath() {
+    const tpt_temporal_params t = defaultTemporal();
+    tpt_temporal_path_params p{};
+    p.alpha = t.alpha;
+    p.depth_tol = t.depth_tol;
+    p.normal_min = t.normal_min;
+    p.max_history = t.max_history;
+    p.flags = t.flags;
+    p.point_tol = 8.0f;
+    return p;
+}
+
 // The hosts' defaults of the variance-guided filter (DESIGN.md section 5 "Post-pass":
 // sigma_lum by the sweep there, not the paper's 4)
 inline tpt_svgf_params defaultSVGF(int iterations = 5) {
@@ -302,10 +316,12 @@ public:
     }
 
     // Mirror-path feature buffers (tpt_render_aov_path): renderAOV continued through up to
-    // max_bounces perfect mirrors, for denoise / denoiseSVGF (temporal stays on renderAOV's).
-    // bounces (nullable) receives the W*H bounce counts.
+    // max_bounces perfect mirrors, for denoise / denoiseSVGF and temporalPath (temporal stays on
+    // renderAOV's).  bounces (nullable) receives the W*H bounce counts, points (nullable) the
+    // W*H*3 terminal points (tpt_render_aov_path_points).
     AOV renderAOVPath(DeviceScene& scene, const Camera& camera, int max_bounces = 8,
-                      std::vector<int32_t>* bounces = nullptr, tpt_aov_path_stats* stats = nullptr) {
+                      std::vector<int32_t>* bounces = nullptr, tpt_aov_path_stats* stats = nullptr,
+                      std::vector<float>* points = nullptr) {
         AOV a;
         a.width = m_width;
         a.height = m_height;
@@ -316,15 +332,18 @@ public:
         a.face.resize(n);
         a.material.resize(n);
         if (bounces) bounces->resize(n);
-        renderAOVPath(scene, camera, a.view(), bounces ? bounces->data() : nullptr, max_bounces, stats);
+        if (points) points->resize(3 * n);
+        renderAOVPath(scene, camera, a.view(), bounces ? bounces->data() : nullptr, max_bounces, stats,
+                      points ? points->data() : nullptr);
         return a;
     }
     // The same into caller buffers (host or device pointers, each nullable).
     void renderAOVPath(DeviceScene& scene, const Camera& camera, const tpt_aov& out, int32_t* bounces,
-                       int max_bounces = 8, tpt_aov_path_stats* stats = nullptr) {
+                       int max_bounces = 8, tpt_aov_path_stats* stats = nullptr, float* points = nullptr) {
         if (!scene.built()) scene.build();
         const tpt_aov_path_params p{max_bounces, 0};
-        check(tpt_render_aov_path(scene.handle(), &camera.c, m_width, m_height, &p, &out, bounces, stats));
+        check(tpt_render_aov_path_points(scene.handle(), &camera.c, m_width, m_height, &p, &out, bounces, points,
+                                         stats));
     }
 
     // Edge-avoiding a-trous filter (tpt_denoise) of a radiance frame guided by its
@@ -366,6 +385,20 @@ public:
         tpt_temporal_stats st{};
         check(tpt_temporal_motion(history.handle(), &camera.c, radiance_in, &guides, &params, radiance_out, variance,
                                   history_len, motion, framebuffer, &st));
+        return st;
+    }
+
+    // temporal() on mirror-path guides (tpt_temporal_path): renderAOVPath's buffers, bounce counts
+    // and terminal points, so that reflections in perfect mirrors keep their history while the
+    // camera moves.  Everything else is temporal()'s.
+    tpt_temporal_stats temporalPath(History& history, const Camera& camera, const float* radiance_in,
+                                    const tpt_aov& path_guides, const int32_t* bounces, const float* points,
+                                    float* radiance_out, float* variance = nullptr, float* history_len = nullptr,
+                                    uint8_t* framebuffer = nullptr,
+                                    const tpt_temporal_path_params& params = defaultTemporalPath()) {
+        tpt_temporal_stats st{};
+        check(tpt_temporal_path(history.handle(), &camera.c, radiance_in, &path_guides, bounces, points, &params,
+                                radiance_out, variance, history_len, framebuffer, &st));
         return st;
     }
 

@@ -24,7 +24,7 @@ from ._lib import TPTError, build_identity, check, lib
 
 __all__ = ["Camera", "Scene", "DeviceScene", "BVH", "EnvLight", "PathTracer", "Frame", "TPTError",
            "procedural_sky", "version", "device_count", "build_identity", "NODE_DTYPE", "DENOISE_DEFAULTS",
-           "History", "TEMPORAL_DEFAULTS", "motion_matrices"]
+           "History", "TEMPORAL_DEFAULTS", "TEMPORAL_PATH_DEFAULTS", "motion_matrices"]
 
 # BVHNode (include/bvh.cuh:52-58): parent, info{left,right | fid,placeHolder}, box
 NODE_DTYPE = np.dtype([("parent", "<u4"), ("a", "<i4"), ("b", "<i4"), ("bmin", "<f4", 3), ("bmax", "<f4", 3)])
@@ -68,6 +68,13 @@ class Camera:
         out[0] = np.cos(t) * m[0] - np.sin(t) * m[2]
         out[2] = np.sin(t) * m[0] + np.cos(t) * m[2]
         return Camera(out.astype(np.float32).reshape(16), self.vfov, self.aspect, self.znear)
+
+    def moved(self, dx: float, dy: float, dz: float) -> "Camera":
+        """This camera with its origin shifted by (dx, dy, dz) in world space (as tpt_render
+        --truck does per frame): c2w's translation column plus the shift, in float32."""
+        out = np.array(self.c2w, np.float32).reshape(16).copy()
+        out[12:15] = out[12:15] + np.asarray((dx, dy, dz), np.float32)
+        return Camera(out, self.vfov, self.aspect, self.znear)
 
     def to_c(self) -> _lib.Camera:
         c = _lib.Camera()
@@ -482,7 +489,7 @@ _PLANES = dict(AOV_LAYOUT, radiance=(3, "float32"), framebuffer=(4, "uint8"))
 # Mirror-path feature buffers (tpt_render_aov_path): the hosts' and the CLI's default cap, the
 # render's default max_depth
 AOV_PATH_DEFAULTS = {"max_bounces": 8}
-_PLANES.update(bounces=(1, "int32"))
+_PLANES.update(bounces=(1, "int32"), points=(3, "float32"))
 
 
 def _aov_out(out, width, height, extra=()):
@@ -523,6 +530,11 @@ def _check_plane(name, buf, width, height):
 # Temporal-accumulation defaults of the hosts and the CLI (tpt.hpp defaultTemporal)
 TEMPORAL_DEFAULTS = {"alpha": 0.1, "depth_tol": 0.1, "normal_min": 0.9, "max_history": 32, "demodulate": True}
 _PLANES.update(variance=(1, "float32"), history_len=(1, "float32"), motion_out=(2, "float32"))
+
+
+# Accumulation through mirrors (tpt_temporal_path): TEMPORAL_DEFAULTS, and point_tol by the sweep of
+# tools/temporal_path_quality.py (DESIGN.md section 5 "Temporal accumulation through mirrors")
+TEMPORAL_PATH_DEFAULTS = dict(TEMPORAL_DEFAULTS, point_tol=8.0)
 
 
 def motion_matrices(prev, cur):
@@ -686,7 +698,7 @@ class PathTracer:
         return out
 
     def renderAOVPath(self, d_scene: DeviceScene, camera: Camera, max_bounces: int = AOV_PATH_DEFAULTS["max_bounces"],
-                      out=None, stats=None):
+                      out=None, stats=None, points: bool = False):
         """Mirror-path feature buffers (tpt_render_aov_path, DESIGN.md section 5
         "Post-pass"): renderAOV continued through up to `max_bounces` perfect mirrors.
         The buffers describe the first surface that is no mirror (or the mirror met at
@@ -696,20 +708,33 @@ class PathTracer:
         to the last mirror.  Returns renderAOV's dict plus `bounces` [H, W] (int32), the
         mirrors followed.  out: as renderAOV's, `bounces` included.  stats: a dict that
         receives trace_ms, followed (pixels with bounces > 0) and deepest.  The result
-        guides denoise / denoiseSVGF; temporal stays on renderAOV's first-hit buffers."""
+        guides denoise / denoiseSVGF and temporalPath; temporal stays on renderAOV's
+        first-hit buffers.
+        points=True (tpt_render_aov_path_points), or a `points` key in out: also `points`
+        [H, W, 3] float32, where each path ended -- the terminal world point, or the last
+        ray's direction where the path leaves the scene -- which temporalPath needs."""
         if not d_scene.built:
             d_scene.build()
         W, H = self.m_width, self.m_height
-        out = _aov_out(out, W, H, extra=("bounces",))
-        a = _take_guides(out, [k for k in out if k != "bounces"], W, H)
-        bounces = out.get("bounces")
+        points = bool(points) or (out is not None and "points" in out)
+        out = _aov_out(out, W, H, extra=("bounces", "points") if points else ("bounces",))
+        if points and out.get("points") is None:
+            out["points"] = np.zeros((H, W, 3), np.float32)
+        a = _take_guides(out, [k for k in out if k not in ("bounces", "points")], W, H)
+        bounces, pts = out.get("bounces"), out.get("points")
         if bounces is not None:
             _check_plane("bounces", bounces, W, H)
+        if pts is not None:
+            _check_plane("points", pts, W, H)
         p = _lib.AovPathParams(int(max_bounces), 0)
         st = _lib.AovPathStats()
         cam = camera.to_c()
-        check(lib().tpt_render_aov_path(d_scene.handle, C.byref(cam), W, H, C.byref(p), C.byref(a), _addr(bounces),
-                                        C.byref(st)))
+        if pts is not None:
+            check(lib().tpt_render_aov_path_points(d_scene.handle, C.byref(cam), W, H, C.byref(p), C.byref(a),
+                                                   _addr(bounces), _addr(pts), C.byref(st)))
+        else:
+            check(lib().tpt_render_aov_path(d_scene.handle, C.byref(cam), W, H, C.byref(p), C.byref(a),
+                                            _addr(bounces), C.byref(st)))
         if stats is not None:
             stats.update(st.as_dict())
         return out
@@ -792,6 +817,50 @@ class PathTracer:
         else:
             check(lib().tpt_temporal(history.handle, C.byref(cam), _addr(radiance), C.byref(g), C.byref(p), _addr(out),
                                      _addr(variance), _addr(history_len), _addr(framebuffer), C.byref(st)))
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out
+
+    def temporalPath(self, history: History, camera: Camera, radiance, aov, bounces=None, points=None, *,
+                     alpha: float = TEMPORAL_PATH_DEFAULTS["alpha"],
+                     depth_tol: float = TEMPORAL_PATH_DEFAULTS["depth_tol"],
+                     normal_min: float = TEMPORAL_PATH_DEFAULTS["normal_min"],
+                     max_history: int = TEMPORAL_PATH_DEFAULTS["max_history"],
+                     demodulate: bool = TEMPORAL_PATH_DEFAULTS["demodulate"],
+                     point_tol: float = TEMPORAL_PATH_DEFAULTS["point_tol"], out=None, variance=None,
+                     history_len=None, framebuffer=None, flags: int = 0, stats=None):
+        """temporal on mirror-path guides (tpt_temporal_path, DESIGN.md section 5 "Temporal
+        accumulation through mirrors"): reflections in perfect mirrors keep their history while
+        the camera moves.  aov: renderAOVPath(..., points=True)'s buffers -- normal, depth (the
+        path's length) and material, albedo with demodulate; bounces / points default to
+        aov["bounces"] / aov["points"].  A pixel that followed k mirrors accepts a tap only
+        where the previous frame followed k mirrors to the same material and its terminal
+        world point lies within point_tol pixel footprints; with k = 0 the rules are
+        temporal's.  Everything else -- out, variance, history_len, framebuffer, stats, the
+        buffers' types -- is temporal's.  The history may alternate between temporal and
+        temporalPath: after a temporal call the mirror pixels start over.  Objects that moved
+        are not followed: reset the history, or use temporal(motion=True)."""
+        W, H = self.m_width, self.m_height
+        if (history.width, history.height) != (W, H):
+            raise ValueError(f"the history is {history.width} x {history.height}, the frame {W} x {H}")
+        _check_plane("radiance", radiance, W, H)
+        g = _take_guides(aov, (("albedo",) if demodulate else ()) + ("normal", "depth", "material"), W, H)
+        bounces = aov.get("bounces") if bounces is None else bounces
+        points = aov.get("points") if points is None else points
+        if out is None:
+            out = np.zeros((H, W, 3), np.float32)
+        _check_plane("radiance", out, W, H)
+        for name, buf in (("bounces", bounces), ("points", points), ("variance", variance),
+                          ("history_len", history_len), ("framebuffer", framebuffer)):
+            if buf is not None:
+                _check_plane(name, buf, W, H)
+        p = _lib.TemporalPathParams(float(alpha), float(depth_tol), float(normal_min), int(max_history),
+                                    int(flags) | (_lib.TEMPORAL_DEMODULATE if demodulate else 0), float(point_tol))
+        st = _lib.TemporalStats()
+        cam = camera.to_c()
+        check(lib().tpt_temporal_path(history.handle, C.byref(cam), _addr(radiance), C.byref(g), _addr(bounces),
+                                      _addr(points), C.byref(p), _addr(out), _addr(variance), _addr(history_len),
+                                      _addr(framebuffer), C.byref(st)))
         if stats is not None:
             stats.update(st.as_dict())
         return out

@@ -131,6 +131,10 @@ class TemporalParams(C.Structure):
                 ("max_history", C.c_int32), ("flags", C.c_int32)]
 
 
+class TemporalPathParams(C.Structure):
+    _fields_ = TemporalParams._fields_ + [("point_tol", C.c_float)]
+
+
 class TemporalStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("reprojected", C.c_uint64)]
 
@@ -165,6 +169,9 @@ SIGNATURES = [
     ("tpt_render_aov_path", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32,
                                       C.POINTER(AovPathParams), C.POINTER(Aov), C.c_void_p,
                                       C.POINTER(AovPathStats)]),
+    ("tpt_render_aov_path_points", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32,
+                                             C.POINTER(AovPathParams), C.POINTER(Aov), C.c_void_p, C.c_void_p,
+                                             C.POINTER(AovPathStats)]),
     ("tpt_denoise", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Aov),
                               C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.POINTER(DenoiseStats)]),
     ("tpt_history_create", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
@@ -176,6 +183,9 @@ SIGNATURES = [
     ("tpt_temporal_motion", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(Aov),
                                       C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.POINTER(TemporalStats)]),
+    ("tpt_temporal_path", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(Aov), C.c_void_p, C.c_void_p,
+                                    C.POINTER(TemporalPathParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(TemporalStats)]),
     ("tpt_motion_matrices", C.c_int32, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_denoise_svgf", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Aov), C.c_void_p,
                                    C.c_void_p, C.POINTER(SvgfParams), C.c_void_p, C.c_void_p, C.c_void_p,

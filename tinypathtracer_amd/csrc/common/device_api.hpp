@@ -278,6 +278,9 @@ struct AovPathArgs {
     unsigned long long* deepest;         // as many, as far apart (zeroed): their maximum = the largest bounces
 };
 hipError_t launch_aov_path(const TraceArgs& a, const AovArgs& o, const AovPathArgs& p, hipStream_t s);
+// post.hip k_aov_path_points: the same, and where each path ended (tpt_render_aov_path_points).
+// points: W*H*3, never null: the terminal hit point, or the last ray's direction on a miss
+hipError_t launch_aov_path_points(const TraceArgs& a, const AovArgs& o, const AovPathArgs& p, float* points, hipStream_t s);
 
 struct DenoiseArgs {                     // pack (inputs -> planes) and resolve (plane -> outputs)
     const float* radiance_in;            // pack: W*H*3
@@ -361,6 +364,20 @@ struct MotionArgs {
 constexpr int kMotionRecordFloats = 24;
 constexpr int32_t kMotionTracked = 0, kMotionIdentity = 1, kMotionUntracked = 2;
 hipError_t launch_temporal_motion(const TemporalArgs& a, const MotionArgs& mo, hipStream_t s);
+
+// post.hip: what the pass on mirror-path guides (tpt_temporal_path) reads and writes on top of
+// TemporalArgs, whose guides are then tpt_render_aov_path's.  The bounce count k is kept as its
+// integer bits in the fourth word of state plane 2 (k_temporal and k_temporal_motion write 0.0f
+// there: k = 0); the terminal points are a fourth state plane per set, (P.xyz, 0), written and
+// gathered by k > 0 lanes only.
+struct TemporalPathArgs {
+    const int32_t* bounces;              // W*H: this frame's mirrors followed
+    const float* points;                 // W*H*3: this frame's terminal points / last directions
+    const float4* prev_points;           // the previous state's plane 3 (gathered where k > 0)
+    float4* next_points;                 // the new state's plane 3 (written where k > 0)
+    float point_tol;                     // > 0, in pixel footprints
+};
+hipError_t launch_temporal_path(const TemporalArgs& a, const TemporalPathArgs& pa, hipStream_t s);
 
 // post.hip: the variance-guided a-trous filter (tpt_denoise_svgf; DESIGN.md section 5
 // "Post-pass").  tpt_denoise's planes, the colour plane's fourth component carrying the

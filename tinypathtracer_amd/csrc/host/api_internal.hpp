@@ -168,7 +168,7 @@ private:
         const void* dev;
         size_t bytes;
     };
-    static constexpr int kMaxBack = 8;   // (tpt_render_aov_path has six outputs)
+    static constexpr int kMaxBack = 8;   // (tpt_render_aov_path_points has seven outputs)
     Back back[kMaxBack];
     int n_back = 0;
     template <class T>
@@ -414,6 +414,7 @@ struct tpt_scene {
     // counts and the counters of AovPathArgs::followed (set 0) and ::deepest (set 1)
     DevBuf<int32_t> ap_bounces;
     SpreadCounters ap_count;
+    DevBuf<float> ap_points;                // tpt_render_aov_path_points: the staging of the terminal points
 
     ~tpt_scene() {
         DeviceGuard g(device);
@@ -486,6 +487,11 @@ struct tpt_history {
     HostPinned<float> h_records;
     DevBuf<int32_t> st_face;
     DevBuf<float> st_motion;
+    // tpt_temporal_path: a fourth state plane per set, the paths' terminal points (allocated and
+    // zeroed at the first call: +32 B per pixel), device staging of the bounce counts and the points
+    DevBuf<float4> points[2];
+    DevBuf<int32_t> st_bounces;
+    DevBuf<float> st_points;
     hipEvent_t ev[2] = {nullptr, nullptr};
 
     ~tpt_history() {

@@ -1,5 +1,6 @@
 // api_post.cpp -- the post-pass entry points of the C-ABI (post.hip): tpt_render_aov, tpt_render_aov_path,
-// tpt_denoise, tpt_history_*, tpt_temporal, tpt_temporal_motion and tpt_denoise_svgf.  Each takes its buffers from either
+// tpt_render_aov_path_points, tpt_denoise, tpt_history_*, tpt_temporal, tpt_temporal_motion, tpt_temporal_path
+// and tpt_denoise_svgf.  Each takes its buffers from either
 // side: host buffers go through the device staging the scene / history keeps
 // (api_internal.hpp Staging).
 #include <cmath>
@@ -113,17 +114,18 @@ tpt_status tpt_render_aov(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_
 
 // Mirror-path feature buffers (post.hip k_aov_path; DESIGN.md section 5 "Post-pass"):
 // tpt_render_aov's call with the bounce counts as a sixth output and two statistics,
-// counted by the kernel in the spread counters and reduced here.
-tpt_status tpt_render_aov_path(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_t H,
-                               const tpt_aov_path_params* p, const tpt_aov* out, int32_t* bounces_out,
-                               tpt_aov_path_stats* stats) {
+// counted by the kernel in the spread counters and reduced here.  With points_out
+// (tpt_render_aov_path_points) the sibling kernel k_aov_path_points runs instead.
+static tpt_status aov_path_pass(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_t H,
+                                const tpt_aov_path_params* p, const tpt_aov* out, int32_t* bounces_out,
+                                float* points_out, tpt_aov_path_stats* stats) {
     if (!s || !s->built) return fail(TPT_ERR_INVALID_ARG, "scene not built");
     if (!cam) return fail(TPT_ERR_INVALID_ARG, "null camera");
     if (!p) return fail(TPT_ERR_INVALID_ARG, "null params");
     if (W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size");
     if (p->max_bounces < 0 || p->max_bounces > 64) return fail(TPT_ERR_INVALID_ARG, "max_bounces must be 0..64");
     if (p->flags != 0) return fail(TPT_ERR_INVALID_ARG, "unknown aov path flags");
-    if (!bounces_out && !(out && (out->albedo || out->normal || out->depth || out->face || out->material)))
+    if (!bounces_out && !points_out && !(out && (out->albedo || out->normal || out->depth || out->face || out->material)))
         return fail(TPT_ERR_INVALID_ARG,
                     "no feature buffer requested: every pointer of out and bounces_out are null");
     {
@@ -144,9 +146,11 @@ tpt_status tpt_render_aov_path(tpt_scene* s, const tpt_camera* cam, int32_t W, i
     Staging sg(st);
     HIP_OR_FAIL(stage_aov(sg, s, out ? out : &none, npix, o));
     HIP_OR_FAIL(sg.out(s->ap_bounces, bounces_out, npix, &pa.bounces));
+    float* points = nullptr;
+    HIP_OR_FAIL(sg.out(s->ap_points, points_out, 3 * npix, &points));
     HIP_OR_FAIL(s->ap_count.zero(st));
     HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
-    HIP_OR_FAIL(tpt::launch_aov_path(a, o, pa, st));
+    HIP_OR_FAIL(points ? tpt::launch_aov_path_points(a, o, pa, points, st) : tpt::launch_aov_path(a, o, pa, st));
     HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
     HIP_OR_FAIL(sg.finish());
     HIP_OR_FAIL(s->ap_count.fetch(st));
@@ -157,6 +161,18 @@ tpt_status tpt_render_aov_path(tpt_scene* s, const tpt_camera* cam, int32_t W, i
         stats->deepest = (int32_t)s->ap_count.max(1);
     }
     return TPT_OK;
+}
+
+tpt_status tpt_render_aov_path(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_t H,
+                               const tpt_aov_path_params* p, const tpt_aov* out, int32_t* bounces_out,
+                               tpt_aov_path_stats* stats) {
+    return aov_path_pass(s, cam, W, H, p, out, bounces_out, nullptr, stats);
+}
+
+tpt_status tpt_render_aov_path_points(tpt_scene* s, const tpt_camera* cam, int32_t W, int32_t H,
+                                      const tpt_aov_path_params* p, const tpt_aov* out, int32_t* bounces_out,
+                                      float* points_out, tpt_aov_path_stats* stats) {
+    return aov_path_pass(s, cam, W, H, p, out, bounces_out, points_out, stats);
 }
 
 // The a-trous denoiser (post.hip; DESIGN.md section 5 "Post-pass"): pack, one launch
@@ -272,11 +288,19 @@ tpt_status tpt_history_reset(tpt_history* h) {
 
 void tpt_history_destroy(tpt_history* h) { delete h; }
 
-// tpt_temporal (motion false: face guide and motion_out unused) and tpt_temporal_motion
+// What tpt_temporal_path passes on top of tpt_temporal's arguments.
+struct PathInputs {
+    const int32_t* bounces;
+    const float* points;
+    float point_tol;
+};
+
+// tpt_temporal (motion false: face guide and motion_out unused), tpt_temporal_motion and
+// tpt_temporal_path (path not null; never with motion)
 static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const float* radiance_in,
                                 const tpt_aov* guides, const tpt_temporal_params* p, float* radiance_out,
                                 float* variance_out, float* history_len_out, float* motion_out, uint8_t* bgra_out,
-                                tpt_temporal_stats* stats, bool motion) {
+                                tpt_temporal_stats* stats, bool motion, const PathInputs* path = nullptr) {
     if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
     if (!cam) return fail(TPT_ERR_INVALID_ARG, "null camera");
     if (!radiance_in) return fail(TPT_ERR_INVALID_ARG, "null radiance_in");
@@ -296,6 +320,9 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
         return fail(TPT_ERR_INVALID_ARG, "normal_min must be in [-1, 1]");
     if (p->max_history < 1 || p->max_history > 65536) return fail(TPT_ERR_INVALID_ARG, "max_history must be 1..65536");
     if (!radiance_out && !bgra_out) return fail(TPT_ERR_INVALID_ARG, "no output buffer: radiance_out and bgra_out are null");
+    if (path && (!path->bounces || !path->points))
+        return fail(TPT_ERR_INVALID_ARG, "accumulation through mirrors needs the bounce counts and the terminal points");
+    if (path && !(path->point_tol > 0.0f)) return fail(TPT_ERR_INVALID_ARG, "point_tol must be > 0");
     tpt_scene* s = h->scene;
     DeviceGuard g(s->device);
     hipStream_t st = s->stream;
@@ -343,6 +370,17 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
         HIP_OR_FAIL(sg.in(h->st_face, guides->face, npix, &mo.face));
         HIP_OR_FAIL(sg.out(h->st_motion, motion_out, 2 * npix, &mo.motion_out));
     }
+    tpt::TemporalPathArgs pa{};
+    if (path) {
+        for (auto& plane : h->points)
+            if (!plane.p) {   // the first call on this history: the fourth plane, zeroed once
+                HIP_OR_FAIL(plane.alloc(npix));
+                HIP_OR_FAIL(hipMemsetAsync(plane.p, 0, npix * sizeof(float4), st));
+            }
+        pa.point_tol = path->point_tol;
+        HIP_OR_FAIL(sg.in(h->st_bounces, path->bounces, npix, &pa.bounces));
+        HIP_OR_FAIL(sg.in(h->st_points, path->points, 3 * npix, &pa.points));
+    }
     // radiance in and out share st_rad: a lane reads its pixel before it writes it
     HIP_OR_FAIL(sg.out(h->st_rad, radiance_out, 3 * npix, &a.radiance_out));
     HIP_OR_FAIL(sg.out(h->st_var, variance_out, npix, &a.variance_out));
@@ -354,10 +392,14 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
         a.prev[k] = h->state[from][k].p;
         a.next[k] = h->state[to][k].p;
     }
+    pa.prev_points = h->points[from].p;
+    pa.next_points = h->points[to].p;
     a.reprojected = h->count.set(0);
     HIP_OR_FAIL(h->count.zero(st));
     HIP_OR_FAIL(hipEventRecord(h->ev[0], st));
-    HIP_OR_FAIL(motion ? tpt::launch_temporal_motion(a, mo, st) : tpt::launch_temporal(a, st));
+    HIP_OR_FAIL(path     ? tpt::launch_temporal_path(a, pa, st)
+                : motion ? tpt::launch_temporal_motion(a, mo, st)
+                         : tpt::launch_temporal(a, st));
     HIP_OR_FAIL(hipEventRecord(h->ev[1], st));
     HIP_OR_FAIL(sg.finish());
     HIP_OR_FAIL(h->count.fetch(st));
@@ -388,6 +430,19 @@ tpt_status tpt_temporal_motion(tpt_history* h, const tpt_camera* cam, const floa
                                tpt_temporal_stats* stats) {
     return temporal_pass(h, cam, radiance_in, guides, p, radiance_out, variance_out, history_len_out, motion_out,
                          bgra_out, stats, true);
+}
+
+// tpt_temporal on mirror-path guides (post.hip k_temporal_path; DESIGN.md section 5 "Temporal
+// accumulation through mirrors").
+tpt_status tpt_temporal_path(tpt_history* h, const tpt_camera* cam, const float* radiance_in, const tpt_aov* path_guides,
+                             const int32_t* bounces, const float* points, const tpt_temporal_path_params* p,
+                             float* radiance_out, float* variance_out, float* history_len_out, uint8_t* bgra_out,
+                             tpt_temporal_stats* stats) {
+    if (!p) return fail(TPT_ERR_INVALID_ARG, "null params");
+    const tpt_temporal_params tp{p->alpha, p->depth_tol, p->normal_min, p->max_history, p->flags};
+    const PathInputs path{bounces, points, p->point_tol};
+    return temporal_pass(h, cam, radiance_in, path_guides, &tp, radiance_out, variance_out, history_len_out, nullptr,
+                         bgra_out, stats, false, &path);
 }
 
 // The variance-guided a-trous filter (post.hip k_svgf_*; DESIGN.md section 5

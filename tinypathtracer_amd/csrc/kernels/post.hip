@@ -10,7 +10,7 @@
 //    forms (results and the args struct by value, a scalar albedo floor) are the ones under
 //    which the kernels' instructions stayed what they were (tools/kernel_diff.py; DESIGN.md
 //    section 5 "One text per shared step" has the outcome per kernel).
-//  * k_aov / k_aov_path: one lane per pixel in 16x16 tiles; the ray through the pixel
+//  * k_aov / k_aov_path / k_aov_path_points (aov_path_kernel.hpp): one lane per pixel in 16x16 tiles; the ray through the pixel
 //    centre walks the render's own closest-hit traversal; k_aov_path follows it through
 //    perfect mirrors, a wave looping until none of its lanes continues.  The LDS stack
 //    is k_trace_rays'.
@@ -19,8 +19,9 @@
 //    between two colour planes, no atomics.  Each tap is two 16-B loads per lane;
 //    a wave of the direct kernel is a 64-pixel row segment, so its lanes read
 //    1 KiB of contiguous addresses per plane at every step size.
-//  * k_temporal / k_temporal_motion (temporal_kernel.hpp): reprojection and accumulation across
-//    frames (tpt_temporal; tpt_temporal_motion, which follows objects that moved).
+//  * k_temporal / k_temporal_motion / k_temporal_path (temporal_kernel.hpp): reprojection and
+//    accumulation across frames (tpt_temporal; tpt_temporal_motion, which follows objects that
+//    moved; tpt_temporal_path, which follows reflections in mirrors).
 //  * k_svgf_pack / k_svgf_estimate / k_svgf_atrous / k_svgf_atrous_lds /
 //    k_svgf_resolve: the variance-guided filter (tpt_denoise_svgf) on the same two
 //    planes, the variance in the colour plane's fourth component.
@@ -215,75 +216,16 @@ __global__ __launch_bounds__(256) void k_aov(TraceArgs a, AovArgs o) {
     write_aov(o, (size_t)x + (size_t)y * (size_t)a.width, alb, nrm, depth, r.fid, mtl);
 }
 
-// k_aov continued through perfect mirrors (tpt_render_aov_path; DESIGN.md section 5
-// "Post-pass" holds the definition the tests pin).  k_aov's lanes, tiles and LDS stack.  A
-// lane traces, runs the hit prelude, and where the hit is a mirror below the cap reflects and
-// goes round again from the hit point, as k_trace starts an extension ray: the origin advanced
-// to o + t d, reflect_dir about the shading normal, the grazing rule with the face it leaves;
-// rayHitTriangle's t > kDelta keeps the ray off that face, there is no offset.  A finished
-// lane waits for its wave; the wave leaves when no lane continues, so a wave that meets no
-// mirror does k_aov's one traversal.  Lanes outside the frame stay to the end (they never
-// trace): the statistics are taken by the whole wave.
-__global__ __launch_bounds__(256) void k_aov_path(TraceArgs a, AovArgs o, AovPathArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const int tid = threadIdx.x;
-    const int2 xy = tile_wave_xy(tid);
-    const int x = xy.x, y = xy.y;
-    const bool inside = x < a.width && y < a.height;   // (no barrier below)
-    V3 ro, rd;
-    centre_ray(a, x, y, ro, rd);
-    Trav r;
-    LaneStack<int> stk;
-    stk.lds = (TPT_LDS int*)lds + tid;
-    stk.nlds = kAovLdsSlots;
-    V3 alb = v3(1.0f, 1.0f, 1.0f), nrm = v3(0.0f, 0.0f, 0.0f);   // the product of the base colours so far
-    float depth = 0.0f;                                          // the distance travelled so far
-    int fid = -1, mtl = -1, k = 0;
-    bool tg = false;   // the camera: no surface
-    bool live = inside;
-    while (__ballot(live) != 0ull) {
-        if (live) {
-            closest_hit(r, a, stk, ro, rd, tg);
-            live = false;
-            fid = r.fid;
-            if (fid < 0) {   // the path ends in a miss: the product and the distance stand
-                nrm = v3(0.0f, 0.0f, 0.0f);
-                mtl = -1;
-            } else {
-                float4 m0;
-                Surf face;
-                mtl = hit_prelude(a, r, nrm, m0, face);
-                const float4 m1 = a.mtl[2 * mtl + 1];
-                alb = alb * v3(m0.x, m0.y, m0.z);
-                depth = depth + r.t;
-                // new_direction's branch order (eta, then metallic); an emitter ends a path (:408-412)
-                const bool mirror = !(m1.x > 0.0f) && m1.y > 0.0f && !(m0.w > 0.0f);
-                if (mirror && k < p.max_bounces) {
-                    ro = ro + (r.t * rd);   // k_trace's advance (:372)
-                    rd = reflect_dir(rd, nrm);
-                    tg = grazing(a.graze ? face : no_surface(), rd);
-                    ++k;
-                    live = true;
-                }
-            }
-        }
-    }
-    // the statistics: one integer atomic each per wave over the spread counters
-    const unsigned long long found = __ballot(k > 0);
-    if (found) {   // (wave-uniform)
-        int deep = k;
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) deep = max(deep, __shfl_xor(deep, s, 64));
-        if ((tid & 63) == 0) {
-            atomicAdd(spread_slot(p.followed), (unsigned long long)__popcll(found));
-            atomicMax(spread_slot(p.deepest), (unsigned long long)deep);
-        }
-    }
-    if (!inside) return;
-    const size_t off = (size_t)x + (size_t)y * (size_t)a.width;
-    write_aov(o, off, alb, nrm, depth, fid, mtl);
-    if (p.bounces) p.bounces[off] = k;
-}
+// The mirror-path kernel's text is aov_path_kernel.hpp, compiled twice: as k_aov_path, and with
+// TPT_AOV_PATH_POINTS as k_aov_path_points (tpt_render_aov_path_points), which also writes where
+// each path ended.  Two compilations of one text, as the temporal kernel below and for its reason:
+// k_aov_path's instructions stay what they were (tools/kernel_diff.py).
+#define TPT_AOV_PATH_POINTS 0
+#include "aov_path_kernel.hpp"
+#undef TPT_AOV_PATH_POINTS
+#define TPT_AOV_PATH_POINTS 1
+#include "aov_path_kernel.hpp"
+#undef TPT_AOV_PATH_POINTS
 
 hipError_t launch_aov(const TraceArgs& a, const AovArgs& o, hipStream_t s) {
     hipLaunchKernelGGL(k_aov, tile_grid(a.width, a.height), dim3(256), kAovLdsBytes, s, a, o);
@@ -292,6 +234,11 @@ hipError_t launch_aov(const TraceArgs& a, const AovArgs& o, hipStream_t s) {
 
 hipError_t launch_aov_path(const TraceArgs& a, const AovArgs& o, const AovPathArgs& p, hipStream_t s) {
     hipLaunchKernelGGL(k_aov_path, tile_grid(a.width, a.height), dim3(256), kAovLdsBytes, s, a, o, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_aov_path_points(const TraceArgs& a, const AovArgs& o, const AovPathArgs& p, float* points, hipStream_t s) {
+    hipLaunchKernelGGL(k_aov_path_points, tile_grid(a.width, a.height), dim3(256), kAovLdsBytes, s, a, o, p, points);
     return hipGetLastError();
 }
 
@@ -433,11 +380,20 @@ constexpr float kMinWsum = 1.0f / 16.0f;     // least sum of valid bilinear weig
 // (tools/kernel_diff.py), and the post-pass's recorded times belong to the code as it was.
 // Its lane's pixel, ray, albedo floor, framebuffer write and counter are the shared steps above,
 // which leave all four instantiations' instructions as they were.
+// A third compilation, with TPT_TEMPORAL_PATH, is k_temporal_path (tpt_temporal_path): the
+// pass on mirror-path guides, which compares bounce counts and terminal points as well.
+#define TPT_TEMPORAL_PATH 0
 #define TPT_TEMPORAL_MOTION 0
 #include "temporal_kernel.hpp"
 #undef TPT_TEMPORAL_MOTION
 #define TPT_TEMPORAL_MOTION 1
 #include "temporal_kernel.hpp"
+#undef TPT_TEMPORAL_MOTION
+#undef TPT_TEMPORAL_PATH
+#define TPT_TEMPORAL_MOTION 0
+#define TPT_TEMPORAL_PATH 1
+#include "temporal_kernel.hpp"
+#undef TPT_TEMPORAL_PATH
 #undef TPT_TEMPORAL_MOTION
 
 hipError_t launch_temporal_motion(const TemporalArgs& a, const MotionArgs& mo, hipStream_t s) {
@@ -445,6 +401,9 @@ hipError_t launch_temporal_motion(const TemporalArgs& a, const MotionArgs& mo, h
 }
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t s) {
     return launch_tiles_or_rows(a.tiles != 0, k_temporal<true>, 0, k_temporal<false>, a.width, a.height, s, a);
+}
+hipError_t launch_temporal_path(const TemporalArgs& a, const TemporalPathArgs& pa, hipStream_t s) {
+    return launch_tiles_or_rows(a.tiles != 0, k_temporal_path<true>, 0, k_temporal_path<false>, a.width, a.height, s, a, pa);
 }
 
 // ---- the variance-guided a-trous filter (Schied et al. 2017; DESIGN.md section 5 "Post-pass" holds the definition) ----

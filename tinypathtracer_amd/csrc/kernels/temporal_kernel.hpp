@@ -1,5 +1,6 @@
-// temporal_kernel.hpp -- the text of k_temporal, included by post.hip once as it is and once
-// with TPT_TEMPORAL_MOTION as k_temporal_motion.  No include guard: it is meant to be read twice.
+// temporal_kernel.hpp -- the text of k_temporal, included by post.hip once as it is, once with
+// TPT_TEMPORAL_MOTION as k_temporal_motion and once with TPT_TEMPORAL_PATH as k_temporal_path.
+// No include guard: it is meant to be read three times.
 
 // One lane per pixel, one launch per frame.  The lane reads its pixel of the caller's
 // planes (3-float planes directly: a pack step would write and read them once more),
@@ -17,9 +18,20 @@
 // both products under its flag instead of multiplying by the unit matrix: 1 x + 0 y + 0 z + 0
 // turns -0 into +0 and an infinite coordinate into NaN, while the skipped path leaves X and n
 // as they are for every input, so that case is k_temporal's bit for bit.
+//
+// TPT_TEMPORAL_PATH (k_temporal_path; DESIGN.md section 5 "Temporal accumulation through
+// mirrors"): the guides are the mirror-path ones, so X = ro + z rd is the virtual image of the
+// path's terminal point.  The lane also reads its bounce count k (4 B) and, where k > 0, where
+// its path ended (12 B).  A tap must hold the same k (the free fourth word of plane 2), and for
+// k > 0 a terminal point (plane 3) within point_tol pixel footprints of the lane's own.  The
+// plane-3 gathers are issued with the others, behind a wave-level ballot of k > 0: a wave
+// without a mirror pixel moves k_temporal's bytes and the 4-byte k.  With k = 0 everywhere
+// every added test passes and the arithmetic is k_temporal's: the same bits.
 template <bool TILES>
 #if TPT_TEMPORAL_MOTION
 __global__ __launch_bounds__(256) void k_temporal_motion(TemporalArgs a, MotionArgs mo) {
+#elif TPT_TEMPORAL_PATH
+__global__ __launch_bounds__(256) void k_temporal_path(TemporalArgs a, TemporalPathArgs pa) {
 #else
 __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
 #endif
@@ -40,6 +52,11 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
         // what the reprojection needs first, so that the taps' loads start early
         const float z = a.depth[p];
         const int m = a.material[p];
+#if TPT_TEMPORAL_PATH
+        const int kb = pa.bounces[p];
+        V3 pe = v3(0.0f, 0.0f, 0.0f);                      // where the path ended (k > 0 only)
+        if (kb > 0) pe = v3(pa.points[3 * p], pa.points[3 * p + 1], pa.points[3 * p + 2]);
+#endif
 #if TPT_TEMPORAL_MOTION
         const int face = mo.face[p];
         float mvx = 0.0f, mvy = 0.0f;                      // where the pixel came from, minus where it is
@@ -127,10 +144,27 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
                         s1[t] = a.prev[1][q[t]];
                         s0[t] = a.prev[0][q[t]];
                     }
+#if TPT_TEMPORAL_PATH
+                    float4 s3[4];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) s3[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if (__ballot(kb > 0) != 0ull) {        // (wave-level: no mirror pixel, no plane-3 traffic)
+                        if (kb > 0) {
+#pragma unroll
+                            for (int t = 0; t < 4; ++t) s3[t] = pa.prev_points[q[t]];
+                        }
+                    }
+                    // the point rule's radius: point_tol footprints at the path's length; a direction's at 1
+                    const float ptol = (pa.point_tol * (hit ? z : 1.0f)) * a.sensor_h * a.inv_h;
+#endif
                     float wsum = 0.0f;
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         bool ok = w[t] > 0.0f && __float_as_int(s2[t].z) == m;
+#if TPT_TEMPORAL_PATH
+                        ok = ok && __float_as_int(s2[t].w) == kb;
+                        if (kb > 0) ok = ok && fsqrt(norm2(v3(s3[t].x, s3[t].y, s3[t].z) - pe)) <= ptol;
+#endif
                         if (hit) {
                             const float4 g = s1[t];
                             ok = ok && fabsf(g.w - dist) <= a.depth_tol * dist &&
@@ -178,7 +212,12 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
         }
         a.next[0][p] = make_float4(C.x, C.y, C.z, N);
         a.next[1][p] = make_float4(n.x, n.y, n.z, z);
+#if TPT_TEMPORAL_PATH
+        a.next[2][p] = make_float4(m1, m2, __int_as_float(m), __int_as_float(kb));
+        if (kb > 0) pa.next_points[p] = make_float4(pe.x, pe.y, pe.z, 0.0f);
+#else
         a.next[2][p] = make_float4(m1, m2, __int_as_float(m), 0.0f);
+#endif
         if (a.radiance_out) {
             a.radiance_out[3 * p] = out.x;
             a.radiance_out[3 * p + 1] = out.y;

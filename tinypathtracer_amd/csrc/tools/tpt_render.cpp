@@ -88,7 +88,8 @@ const char* kUsage =
     "usage: %s scene.gltf [--width W] [--height H] [--spp N] [--depth D] [--seed S] "
     "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]] "
     "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]] "
-    "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG]\n";
+    "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG] [--truck DX DY DZ] "
+    "[--temporal-path [bounces]]\n";
 
 // The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
 tpt::Camera yawed(const tpt::Camera& base, double deg) {
@@ -99,6 +100,13 @@ tpt::Camera yawed(const tpt::Camera& base, double deg) {
         cam.c.c2w[i] = (float)(c * right - s * back);
         cam.c.c2w[8 + i] = (float)(s * right + c * back);
     }
+    return cam;
+}
+
+// `base` with its origin shifted by `shift` in world space (--truck, per frame)
+tpt::Camera trucked(const tpt::Camera& base, const double* shift, int frame) {
+    tpt::Camera cam = base;
+    for (int r = 0; r < 3; ++r) cam.c.c2w[12 + r] = base.c.c2w[12 + r] + (float)(shift[r] * frame);
     return cam;
 }
 
@@ -160,6 +168,8 @@ int main(int argc, char** argv) {
     bool progressive = false, aov = false, denoise = false, temporal = false, svgf = false, aov_path = false;
     int path_bounces = 8;
     double yaw = 0.0;
+    double truck[3] = {0.0, 0.0, 0.0};   // --truck: the camera's world-space shift per frame
+    bool temporal_path = false;          // --temporal-path: accumulate on mirror-path guides
     std::vector<ObjectMotion> motions;   // --move / --spin, one entry per object named
     auto motion_of = [&](uint32_t object) -> ObjectMotion& {
         for (auto& om : motions)
@@ -195,7 +205,14 @@ int main(int argc, char** argv) {
             aov_path = true;   // an optional bounce cap follows
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') path_bounces = std::stoi(argv[++i]);
         }
+        else if (a == "--temporal-path") {
+            temporal = temporal_path = true;   // an optional bounce cap follows
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') path_bounces = std::stoi(argv[++i]);
+        }
         else if (a == "--yaw") yaw = std::stod(next());
+        else if (a == "--truck") {
+            for (double& v : truck) v = std::stod(next());
+        }
         else if (a == "--move") {
             ObjectMotion& om = motion_of((uint32_t)std::stoul(next()));
             for (double& v : om.move) v = std::stod(next());
@@ -220,6 +237,10 @@ int main(int argc, char** argv) {
     }
     if (!motions.empty() && (!temporal || frames < 2)) {
         std::fprintf(stderr, "--move and --spin need --frames F (F > 1) and --temporal\n");
+        return 2;
+    }
+    if (!motions.empty() && temporal_path) {   // tpt_temporal_path does not follow moving objects
+        std::fprintf(stderr, "--move and --spin cannot be combined with --temporal-path\n");
         return 2;
     }
     if (temporal && progressive) {   // progressive is already the exact accumulation of an unmoving camera
@@ -260,7 +281,7 @@ int main(int argc, char** argv) {
             std::vector<uint8_t> fb((size_t)W * H * 4, 255);
             const uint64_t base = seed ? seed : (uint64_t)std::time(nullptr);
             for (int i = 0; i < frames; ++i) {
-                cam = yawed(scene.m_camera, yaw * i);
+                cam = trucked(yawed(scene.m_camera, yaw * i), truck, i);
                 for (const auto& om : motions) {   // (frame 0 keeps the loaded matrices)
                     float m[16];
                     moved_matrix(om, scene.desc().vert_trans + 16 * (size_t)om.object, i, m);
@@ -268,6 +289,14 @@ int main(int argc, char** argv) {
                 }
                 if (!d.built()) d.build();
                 f.stats = pt.doTrace(d, cam, f.bgra.data(), spp, base + (uint64_t)i, depth, f.radiance.data());
+                if (temporal_path) {   // the path buffers with their terminal points, every frame
+                    std::vector<int32_t> bounces;
+                    std::vector<float> points;
+                    g = pt.renderAOVPath(d, cam, path_bounces, &bounces, nullptr, &points);
+                    pt.temporalPath(hist, cam, f.radiance.data(), g.view(), bounces.data(), points.data(), acc.data(),
+                                    var.data(), len.data(), fb.data());
+                    continue;
+                }
                 g = pt.renderAOV(d, cam);
                 if (motions.empty())
                     pt.temporal(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(), fb.data());
@@ -279,7 +308,8 @@ int main(int argc, char** argv) {
             write_ppm(out + "_temporal.ppm", fb, W, H);
         } else {
             for (int i = 0; i < frames; ++i) {
-                if (yaw != 0.0) cam = yawed(scene.m_camera, yaw * i);
+                if (yaw != 0.0 || truck[0] != 0.0 || truck[1] != 0.0 || truck[2] != 0.0)
+                    cam = trucked(yawed(scene.m_camera, yaw * i), truck, i);
                 f.stats = pt.doTrace(d, cam, f.bgra.data(), spp, seed, depth, f.radiance.data(), 1, 0,
                                      progressive && i > 0);
             }
@@ -293,7 +323,7 @@ int main(int argc, char** argv) {
                 write_pfm(out + "_bounces.pfm", std::vector<float>(bounces.begin(), bounces.end()), W, H, 1);
             } else if (!temporal) {
                 g = pt.renderAOV(d, cam);
-            }
+            }   // (--temporal-path: g holds the last frame's path guides already)
             if (aov || aov_path) {
                 write_pfm(out + "_albedo.pfm", g.albedo, W, H, 3);
                 write_pfm(out + "_normal.pfm", g.normal, W, H, 3);
