@@ -303,6 +303,61 @@ tpt_status tpt_render_frames(tpt_scene* scene, const tpt_env* env, const tpt_cam
                              const tpt_params* params, int32_t n_frames, const uint64_t* seeds,
                              float* const* radiance_outs, uint8_t* const* bgra_outs, tpt_stats* stats);
 
+/* Adaptive sampling (DESIGN.md section 5 "Adaptive sampling"): every 16x16-pixel tile of the
+ * frame is rendered until its error estimate falls below `target`, at most to max_spp.
+ *
+ * Schedule: every tile gets min_spp samples in two halves; then, with n = min_spp, each tile's
+ * error E is estimated from its pixels' n-spp radiance I and n/2-spp radiance A (Dammertz et
+ * al. 2010, the first half of the samples as the half buffer):
+ *   e = (|I.r - A.r| + |I.g - A.g| + |I.b - A.b|) / sqrt(max(I.r + I.g + I.b, 1e-4)),
+ *   E = the mean of e over the tile's in-frame pixels (float32, a fixed summation order).
+ * A tile with E < target stops with n samples; the others get n more, n doubles and the
+ * estimate repeats, until n == max_spp.  A tile still at or above the target there counts in
+ * unconverged_tiles.  A tile with a non-finite pixel has E = NaN, which is below no target: it
+ * runs to max_spp and counts as unconverged.  target 0 renders every tile to max_spp, +inf
+ * every tile to min_spp.
+ *
+ * So every tile holds min_spp * 2^i samples, and every pixel of radiance_out and bgra_out
+ * equals tpt_render's at its tile's count, bit for bit, with the same seed, max_depth and
+ * flags: the tiles continue the per-pixel streams and sums a progressive render would.
+ *
+ *   params:        width, height, max_depth, seed, flags, lanes_per_pixel, refill, leaf_batch
+ *                  as in tpt_render (each pass picks its lane mode by its own tile count);
+ *                  spp, spp_per_launch and the pipe_* fields are ignored.
+ *   radiance_out, bgra_out: as tpt_render's; at least one is non-null.
+ *   tile_spp_out:   nullable, ceil(height / 16) * ceil(width / 16) entries, row 0 = bottom:
+ *                   the samples each tile holds.  Host or device memory, like the images.
+ *   tile_error_out: nullable, as many floats: each tile's last estimate.
+ *
+ * TPT_ERR_INVALID_ARG, nothing written: min_spp odd or < 2; max_spp not min_spp * 2^j; a NaN
+ * or negative target; unknown adaptive flags (none are defined); TPT_FLAG_WAVEFRONT or
+ * TPT_FLAG_ACCUMULATE; band_count > 1, a band_index, a band_list or a band_cost (the whole
+ * frame only); both image outputs null; a frame wider or higher than 1,048,576 pixels; and
+ * whatever tpt_render refuses.  The scene's progressive state is invalid afterwards: a later
+ * TPT_FLAG_ACCUMULATE render starts over.  The snapshot of the sums (12 bytes per pixel) stays
+ * with the scene. */
+typedef struct {
+    int32_t min_spp, max_spp;     /* even, >= 2; min_spp * 2^j */
+    float target;                 /* >= 0, +inf allowed */
+    int32_t flags;                /* 0 */
+} tpt_adaptive_params;
+
+typedef struct {
+    uint64_t samples;             /* sum over the tiles of in-frame pixels * samples */
+    uint64_t pixels;              /* width * height */
+    uint64_t traversals;          /* as tpt_stats */
+    int32_t passes;               /* trace passes: the two halves of min_spp, then one per doubling */
+    int32_t unconverged_tiles;    /* tiles at or above the target (or NaN) at max_spp */
+    double trace_ms;              /* the passes' trace launches (HIP events), summed */
+    double error_ms;              /* the snapshot and estimate kernels, summed */
+    double total_ms;              /* whole call, host wall */
+} tpt_adaptive_stats;
+
+tpt_status tpt_render_adaptive(tpt_scene* scene, const tpt_env* env, const tpt_camera* camera,
+                               const tpt_params* params, const tpt_adaptive_params* adaptive,
+                               float* radiance_out, uint8_t* bgra_out, int32_t* tile_spp_out,
+                               float* tile_error_out, tpt_adaptive_stats* stats);
+
 /* ---- after the render: first-hit feature buffers and the denoiser (DESIGN.md section 5 "Post-pass") ---- */
 
 /* First-hit feature buffers (AOVs).  Each pointer is nullable and may be host

@@ -291,6 +291,31 @@ public:
         return st;
     }
 
+    // Adaptive sampling (tpt_render_adaptive): every 16x16-pixel tile is rendered until its
+    // error estimate falls below `target`, from min_spp to at most max_spp = min_spp * 2^j
+    // samples; every pixel equals doTrace at its tile's count, bit for bit.  tile_spp /
+    // tile_error: nullable, ceil(H / 16) * ceil(W / 16) entries, row 0 = bottom.
+    tpt_adaptive_stats doTraceAdaptive(DeviceScene& scene, const Camera& camera, uint8_t* framebuffer, int min_spp,
+                                       int max_spp, float target, uint64_t seed = 0, int max_depth = 8,
+                                       float* radiance = nullptr, int32_t* tile_spp = nullptr,
+                                       float* tile_error = nullptr, int flags = 0) {
+        if (!scene.built()) scene.build();
+        tpt_params p{};
+        p.width = m_width;
+        p.height = m_height;
+        p.max_depth = max_depth;
+        p.seed = seed ? seed : (uint64_t)std::time(nullptr);
+        last_seed_ = p.seed;
+        p.band_rows = 16;
+        p.band_count = 1;
+        p.flags = flags;
+        tpt_adaptive_params ap{min_spp, max_spp, target, 0};
+        tpt_adaptive_stats st{};
+        check(tpt_render_adaptive(scene.handle(), envLight.handle(), &camera.c, &p, &ap, radiance, framebuffer,
+                                  tile_spp, tile_error, &st));
+        return st;
+    }
+
     // First-hit feature buffers of the frame (tpt_render_aov): one ray per pixel
     // centre through the render's traversal.  Every plane is sized and filled;
     // row 0 = bottom, like the radiance.

@@ -24,7 +24,7 @@ from ._lib import TPTError, build_identity, check, lib
 
 __all__ = ["Camera", "Scene", "DeviceScene", "BVH", "EnvLight", "PathTracer", "Frame", "TPTError",
            "procedural_sky", "version", "device_count", "build_identity", "NODE_DTYPE", "DENOISE_DEFAULTS",
-           "History", "TEMPORAL_DEFAULTS", "TEMPORAL_PATH_DEFAULTS", "motion_matrices"]
+           "History", "TEMPORAL_DEFAULTS", "TEMPORAL_PATH_DEFAULTS", "motion_matrices", "ADAPTIVE_DEFAULTS"]
 
 # BVHNode (include/bvh.cuh:52-58): parent, info{left,right | fid,placeHolder}, box
 NODE_DTYPE = np.dtype([("parent", "<u4"), ("a", "<i4"), ("b", "<i4"), ("bmin", "<f4", 3), ("bmax", "<f4", 3)])
@@ -489,6 +489,8 @@ _PLANES = dict(AOV_LAYOUT, radiance=(3, "float32"), framebuffer=(4, "uint8"))
 # Mirror-path feature buffers (tpt_render_aov_path): the hosts' and the CLI's default cap, the
 # render's default max_depth
 AOV_PATH_DEFAULTS = {"max_bounces": 8}
+# doTraceAdaptive: tiles stop once their error estimate (tpt.h, tpt_render_adaptive) is below the target
+ADAPTIVE_DEFAULTS = {"min_spp": 16, "max_spp": 1024, "target": 0.1}
 _PLANES.update(bounces=(1, "int32"), points=(3, "float32"))
 
 
@@ -674,6 +676,37 @@ class PathTracer:
         cam = camera.to_c()
         check(lib().tpt_render_frames(d_scene.handle, env, C.byref(cam), C.byref(p), n, cs,
                                       rp[0] if rp else None, fp[0] if fp else None, C.byref(st)))
+        return st.as_dict()
+
+    def doTraceAdaptive(self, d_scene: DeviceScene, camera: Camera, framebuffer=None, *,
+                        min_spp: int = ADAPTIVE_DEFAULTS["min_spp"], max_spp: int = ADAPTIVE_DEFAULTS["max_spp"],
+                        target: float = ADAPTIVE_DEFAULTS["target"], seed=None, max_depth: int = 8, radiance=None,
+                        flags: int = 0, refill: int = 0, lanes_per_pixel: int = 0, leaf_batch: int = 0,
+                        tile_spp=None, tile_error=None, stats=None):
+        """One frame, every 16x16-pixel tile rendered until its error estimate falls
+        below `target` (tpt_render_adaptive): min_spp samples first, then doublings
+        up to max_spp = min_spp * 2^j.  Every pixel equals doTrace at its tile's
+        sample count, bit for bit.  framebuffer / radiance as in doTrace (at least
+        one); tile_spp (int32) / tile_error (float32): optional outputs of
+        ceil(H / 16) x ceil(W / 16) entries, row 0 = bottom.  stats: a dict that
+        receives tpt_adaptive_stats.  Returns the stats."""
+        if not d_scene.built:
+            d_scene.build()
+        W, H = self.m_width, self.m_height
+        if seed is None:
+            seed = int(time.time())
+        self._last_seed = seed
+        # (the wavefront variant takes no tile list: a suite forced through it keeps the megakernel here)
+        p = _lib.Params(W, H, 0, max_depth, seed, 16, 1, 0, 0, flags | (_forced_flags() & ~_lib.FLAG_WAVEFRONT),
+                        refill, 0, 0, lanes_per_pixel, leaf_batch)
+        ap = _lib.AdaptiveParams(min_spp, max_spp, target, 0)
+        st = _lib.AdaptiveStats()
+        env = self.envLight.handle if self.envLight is not None else None
+        cam = camera.to_c()
+        check(lib().tpt_render_adaptive(d_scene.handle, env, C.byref(cam), C.byref(p), C.byref(ap), _addr(radiance),
+                                        _addr(framebuffer), _addr(tile_spp), _addr(tile_error), C.byref(st)))
+        if stats is not None:
+            stats.update(st.as_dict())
         return st.as_dict()
 
     def renderAOV(self, d_scene: DeviceScene, camera: Camera, out=None, stats=None):

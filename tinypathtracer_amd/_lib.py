@@ -98,6 +98,19 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("target", C.c_float), ("flags", C.c_int32)]
+
+
+class AdaptiveStats(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("pixels", C.c_uint64), ("traversals", C.c_uint64),
+                ("passes", C.c_int32), ("unconverged_tiles", C.c_int32), ("trace_ms", C.c_double),
+                ("error_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Aov(C.Structure):
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("face", C.c_void_p),
                 ("material", C.c_void_p)]
@@ -164,6 +177,9 @@ SIGNATURES = [
     ("tpt_render_frames", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_int32,
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                     C.POINTER(Stats)]),
+    ("tpt_render_adaptive", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.POINTER(Params),
+                                      C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(AdaptiveStats)]),
     ("tpt_render_aov", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.POINTER(Aov),
                                  C.POINTER(C.c_double)]),
     ("tpt_render_aov_path", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32,
@@ -252,10 +268,11 @@ def lib():
                               f"`make -C {HERE}` or __graft_entry__.build()")
         L = C.CDLL(LIB_PATH)
         # TPT_LIB (tools/gpu_abn.sh A/B of an older build) may name a library that
-        # predates the newest debug entry points; the product library must export all
+        # predates the newest debug entry points or tpt_render_adaptive (an A/B against the
+        # build before it); the product library must export all
         older = bool(os.environ.get("TPT_LIB"))
         for name, res, args in SIGNATURES:
-            if older and name.startswith("tpt_debug_") and not hasattr(L, name):
+            if older and (name.startswith("tpt_debug_") or name == "tpt_render_adaptive") and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res

@@ -130,6 +130,11 @@ struct TraceArgs {
     float* accum;                        // 3 planes: r, g, b (running totalRad)
     unsigned long long* counters;        // [0] trav [1] inner [2] leaf [3] shade [4] overflow [5] wide
     unsigned long long* debug_waves;     // phase-profiling builds: 8 words per wave (null: off)
+    // Listed launch (tpt_render_adaptive; nullable, device memory): n_tiles 16x16-pixel tiles, each packed
+    // tx | ty << 16, rendered in list order by a one-dimensional grid.  The frame is whole then: no bands,
+    // band list or band_cost, one frame, no XCD runs.  (Last in the struct: no other field moves.)
+    const uint32_t* tile_list;
+    int32_t n_tiles;
 };
 
 struct ResolveArgs {
@@ -253,6 +258,28 @@ hipError_t launch_trace_ptr(const void* a, hipStream_t s, int32_t* shape);   // 
 hipError_t launch_step_latency_ptr(const void* a, uint32_t n, const float* o, const float* d, int nodes_lds,
                                    unsigned long long* out, hipStream_t s);
 hipError_t launch_resolve(const ResolveArgs& a, hipStream_t s);
+
+// adaptive.hip: the tile error estimate and the per-tile resolve of tpt_render_adaptive (DESIGN.md
+// section 5 "Adaptive sampling").  Tiles are 16x16 pixels, packed tx | ty << 16 like TraceArgs::tile_list.
+struct TileErrorArgs {
+    const float* accum;                  // 3 planes of W*H sums (TraceArgs::accum)
+    float* snapshot;                     // 3 planes: the sums when the listed tiles had n / 2 samples
+    const uint32_t* tile_list;           // n_tiles entries
+    float* tile_error;                   // tiles_y * tiles_x, row 0 = bottom; listed tiles' entries are written
+    int32_t n_tiles;
+    int32_t width, height, tiles_x;
+    int32_t n;                           // samples the listed tiles hold now (even)
+    int32_t snapshot_only;               // 1: only copy the listed tiles' sums to the snapshot
+};
+hipError_t launch_tile_error(const TileErrorArgs& a, hipStream_t s);
+struct ResolveTilesArgs {
+    const float* accum;
+    const int32_t* tile_spp;             // tiles_y * tiles_x: the samples each tile holds
+    float* radiance;                     // as ResolveArgs
+    uint8_t* bgra;
+    int32_t width, height, tiles_x;
+};
+hipError_t launch_resolve_tiles(const ResolveTilesArgs& a, hipStream_t s);
 // KAT kernel over the trace kernel's device functions (tpt_debug_hot_kat)
 hipError_t launch_hot_kat(int op, uint32_t n, const float* in, float* out, hipStream_t s);
 hipError_t launch_trace_rays(const TraceArgs& a, uint32_t n, const float* o, const float* d, const int32_t* ofid,

@@ -1,7 +1,7 @@
 // api.cpp -- the C-ABI (include/tpt.h) over the HIP kernels: version, errors,
 // read-backs, the debug entry points and the loaders.  The scene and env
-// handles are in api_scene.cpp, tpt_render* in api_render.cpp, the post-pass in
-// api_post.cpp; api_internal.hpp holds what they share.
+// handles are in api_scene.cpp, tpt_render* in api_render.cpp, tpt_render_adaptive in
+// api_adaptive.cpp, the post-pass in api_post.cpp; api_internal.hpp holds what they share.
 //
 // No exceptions cross the ABI: every entry point returns tpt_status and records
 // a thread-local message for tpt_last_error().

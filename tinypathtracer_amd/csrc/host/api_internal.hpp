@@ -415,6 +415,15 @@ struct tpt_scene {
     DevBuf<int32_t> ap_bounces;
     SpreadCounters ap_count;
     DevBuf<float> ap_points;                // tpt_render_aov_path_points: the staging of the terminal points
+    // tpt_render_adaptive (adaptive.hip): the sums' snapshot at half a tile's samples (3 planes, 12 B
+    // per pixel), the active tiles' list, the tiles' error estimates and sample counts, with pinned
+    // host copies.  Kept between calls.
+    DevBuf<float> ad_snap, ad_err;
+    DevBuf<uint32_t> ad_tiles;
+    DevBuf<int32_t> ad_spp;
+    HostPinned<float> ad_err_h;
+    HostPinned<uint32_t> ad_tiles_h;
+    HostPinned<int32_t> ad_spp_h;
 
     ~tpt_scene() {
         DeviceGuard g(device);

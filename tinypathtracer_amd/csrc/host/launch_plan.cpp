@@ -49,7 +49,11 @@ LaunchPlan plan_launches(const PlanInput& in) {
     // strong-scaled C2 at N = 8 (259 K pixels per GPU, slowest rank) 314 -> 250 ms;
     // at N = 4 (518 K) four lanes lose (463 vs 328 ms: four times the waves), so
     // the chip is the bound.
-    const double launch_pix = (double)W * (double)std::max(bh, 1) * (double)nf;
+    const bool tiles = in.n_tiles >= 0;   // a listed launch
+    if (tiles && ((in.flags & TPT_FLAG_WAVEFRONT) || in.listed || in.band_count != 1 || in.band_index != 0 || nf != 1 || bh != H))
+        return plan_error("a tile list takes the whole frame: one frame, no bands, not the wavefront variant");
+    const double launch_pix =
+        tiles ? 256.0 * (double)std::max(in.n_tiles, 1) : (double)W * (double)std::max(bh, 1) * (double)nf;
     const double resident = (double)in.resident_lanes;
     // (the wavefront variant has no lane modes: tpt.h, lanes_per_pixel is not used there)
     const bool wavefront = (in.flags & TPT_FLAG_WAVEFRONT) != 0;
@@ -67,7 +71,7 @@ LaunchPlan plan_launches(const PlanInput& in) {
                                                    in.n_materials, in.n_faces, in.max_depth, in.any_emitter}).key;
     pl.pair_kernel = kTraceFamily[variant.family].lanes == 2;
     pl.wg_rows = kTraceFamily[variant.family].tile_rows;   // the trace grid's y extent is (band row blocks) x frames
-    if (!wavefront && (size_t)((bh + pl.wg_rows - 1) / pl.wg_rows) * nf > 65535)
+    if (!wavefront && !tiles && (size_t)((bh + pl.wg_rows - 1) / pl.wg_rows) * nf > 65535)
         return plan_error("frame batch too large for one launch");
     // Shallow trees (few triangles) make a traversal short against a shading
     // pass, so passes are batched harder there: tir (6 triangles) refill 16
@@ -102,7 +106,7 @@ LaunchPlan plan_launches(const PlanInput& in) {
     // 10 +4.1 %, 30 +3.7 %, 5 +2.1 %, 3 +1.9 %).
     pl.xcd_run = 0;
 #ifndef TPT_XCD_RUNS_OFF   // (A/B builds: round-robin workgroups on every scene)
-    if (in.n_faces > 16384) {
+    if (in.n_faces > 16384 && !tiles) {
         const int gx = (W + 15) / 16, per = gx / 8;
         if (gx % 8 == 0)
             for (int g = std::min(per, 10); g >= 2 && pl.xcd_run == 0; --g)
@@ -131,7 +135,7 @@ LaunchPlan plan_launches(const PlanInput& in) {
         // (clamped: below 4 pixels the quotient is past an int)
         chunk = (int)std::min(2147483647.0, std::max(1.0, std::floor(4096.0 * 2073600.0 / launch_pix)));
         const bool forced = in.pipe_sets > 0;
-        nset = forced ? in.pipe_sets : 3;
+        nset = tiles ? 1 : (forced ? in.pipe_sets : 3);
         // (pair mode: 16 -- C3 4096 spp, 256-spp chunks: 8,180 vs 8,016-8,032 Mrays/s with 8,
         // 7,743 with 4; C3 + IS 6,322 vs 6,206-6,267)
         const int per_set = in.pipe_chunks > 0 ? in.pipe_chunks : (pl.pair_kernel ? 16 : 8);

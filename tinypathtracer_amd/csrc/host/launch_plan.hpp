@@ -41,6 +41,10 @@ struct PlanInput {
     bool quad_fits = false;             // tpt::trace_quad_fits of the call's TraceArgs
     int32_t max_depth = 8;              // tpt_params
     bool any_emitter = true;            // some triangle of the scene emits
+    // >= 0: a listed launch over this many 16x16-pixel tiles of the whole frame (TraceArgs tile_list;
+    // tpt_render_adaptive): the lane-mode and drained-launch rules key on 256 * n_tiles pixels, no XCD
+    // runs, one band set on one stream, its spp chunked as for one set
+    int32_t n_tiles = -1;
 };
 
 struct PlanLaunch {

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
     // screen locality of a single frame (node reuse in L1/L2)
     const int nfr = a.n_frames > 0 ? a.n_frames : 1;
     int bx = (int)blockIdx.x / NB, part = (int)blockIdx.x % NB;
-    const int by = (int)blockIdx.y;
+    int by = (int)blockIdx.y;
     // XCD runs (scenes larger than an XCD's 4 MiB L2): blocks b and b + 8 share
     // an XCD.  Within each row of workgroups XCD k gets runs of xcd_run
     // adjacent tiles instead of every 8th tile, so its resident tiles see less
@@ -149,6 +149,18 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
         part = (b >> 3) % NB;
         tile_id = m * 8 + (b & 7);
         bx = ((m / g) * 8 + k) * g + m % g;
+    }
+    // Listed launch (TraceArgs tile_list): a one-dimensional grid over 16x16-pixel tiles of the
+    // whole frame.  P workgroups render a listed tile: the SX x SY workgroup tiles it holds (pair
+    // mode 1 x 2, four lanes per pixel 2 x 2), NB parts each.  Only bx, by and part come from the
+    // list -- one uniform load -- and everything below is the unlisted launch's.
+    if (a.tile_list) {
+        constexpr int SX = 16 / V::fam.tile_w, SY = 16 / V::fam.tile_rows, P = NB * SX * SY;
+        const int q = (int)blockIdx.x % P, sub = q / NB;
+        const uint32_t t = a.tile_list[(int)blockIdx.x / P];
+        part = q % NB;
+        bx = (int)(t & 0xffffu) * SX + sub % SX;
+        by = (int)(t >> 16) * SY + sub / SX;
     }
     const int wave = part * WGW + (tid >> 6);   // the wave's sub-tile of its tile, 0..3
     const int frame = by % nfr;
@@ -1206,6 +1218,13 @@ static hipError_t launch_one(const TraceArgs& a_in, const LaunchCtx& c) {
     // four lanes per pixel: the quads' stacks must lie in LDS whole
     if (V::QUAD && l.stack_slots < a.stack_depth + 3) return hipErrorInvalidValue;
     if (c.dry) return hipSuccess;
+    if (a.tile_list) {   // a listed launch: the tiles' workgroups in list order, no XCD runs
+        constexpr unsigned P = (4 / WGW) * (16 / V::fam.tile_w) * (16 / V::fam.tile_rows);
+        a.xcd_run = 0;
+        if (a.n_tiles <= 0) return hipSuccess;
+        hipLaunchKernelGGL(kern, dim3((unsigned)a.n_tiles * P), dim3(64 * WGW), l.bytes, c.s, a);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(kern, dim3(tiles.x * (4 / WGW), tiles.y), dim3(64 * WGW), l.bytes, c.s, a);
     return hipGetLastError();
 }

@@ -8,6 +8,7 @@
 //              [--frames F [--progressive]] [--aov] [--denoise [iterations]]
 //              [--temporal] [--yaw DEG] [--svgf [iterations]] [--aov-path [bounces]]
 //              [--move OBJ DX DY DZ] [--spin OBJ DEG]
+//              [--adaptive TARGET [--min-spp N] [--max-spp N]]
 // --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
 // <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
 // a-trous filter of the written frame (tpt_denoise, the hosts' defaults; with
@@ -22,6 +23,12 @@
 // <out>_albedo.pfm, <out>_normal.pfm and <out>_depth.pfm are written from the path buffers,
 // with <out>_bounces.pfm, and --denoise / --svgf take them as guides; --temporal keeps the
 // first-hit buffers, whose surface it reprojects.
+// --adaptive TARGET renders every 16x16-pixel tile until its error estimate is below TARGET
+// (tpt_render_adaptive), from --min-spp (default 16) to at most --max-spp (default 1024, min-spp
+// times a power of two) samples; --spp is not used.  <out>_spp.pfm holds every pixel's sample
+// count.  --aov, --aov-path, --denoise and --svgf run on its frame as on a fixed-spp one; not with
+// --temporal, --progressive, --frames, --yaw or --truck (one frame from the scene's camera), and
+// --min-spp / --max-spp are refused without it.
 // --yaw DEG turns the camera about its own origin and up axis by DEG per frame.
 // --move OBJ DX DY DZ translates object OBJ (its index in the scene's object order: the
 // mesh nodes of the glTF file in node order) by (DX, DY, DZ) world units per frame; --spin
@@ -89,7 +96,7 @@ const char* kUsage =
     "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]] "
     "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]] "
     "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG] [--truck DX DY DZ] "
-    "[--temporal-path [bounces]]\n";
+    "[--temporal-path [bounces]] [--adaptive TARGET [--min-spp N] [--max-spp N]]\n";
 
 // The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
 tpt::Camera yawed(const tpt::Camera& base, double deg) {
@@ -167,6 +174,11 @@ int main(int argc, char** argv) {
     int W = 1920, H = 1080, spp = 64, depth = 8, device = 0, frames = 1;
     bool progressive = false, aov = false, denoise = false, temporal = false, svgf = false, aov_path = false;
     int path_bounces = 8;
+    bool adaptive = false;               // --adaptive: tiles rendered to a target error
+    float ad_target = 0.0f;
+    int ad_min = 16, ad_max = 1024;
+    bool ad_range = false;               // --min-spp or --max-spp given
+    tpt_adaptive_stats ad_stats{};
     double yaw = 0.0;
     double truck[3] = {0.0, 0.0, 0.0};   // --truck: the camera's world-space shift per frame
     bool temporal_path = false;          // --temporal-path: accumulate on mirror-path guides
@@ -209,6 +221,9 @@ int main(int argc, char** argv) {
             temporal = temporal_path = true;   // an optional bounce cap follows
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') path_bounces = std::stoi(argv[++i]);
         }
+        else if (a == "--adaptive") { adaptive = true; ad_target = std::stof(next()); }
+        else if (a == "--min-spp") { ad_range = true; ad_min = std::stoi(next()); }
+        else if (a == "--max-spp") { ad_range = true; ad_max = std::stoi(next()); }
         else if (a == "--yaw") yaw = std::stod(next());
         else if (a == "--truck") {
             for (double& v : truck) v = std::stod(next());
@@ -245,6 +260,16 @@ int main(int argc, char** argv) {
     }
     if (temporal && progressive) {   // progressive is already the exact accumulation of an unmoving camera
         std::fprintf(stderr, "--temporal cannot be combined with --progressive\n");
+        return 2;
+    }
+    const bool camera_moves = yaw != 0.0 || truck[0] != 0.0 || truck[1] != 0.0 || truck[2] != 0.0;
+    if (adaptive && (temporal || progressive || frames != 1 || camera_moves)) {
+        std::fprintf(stderr, "--adaptive renders one frame: not with --temporal, --progressive, --frames, --yaw "
+                             "or --truck\n");
+        return 2;
+    }
+    if (ad_range && !adaptive) {
+        std::fprintf(stderr, "--min-spp and --max-spp need --adaptive TARGET\n");
         return 2;
     }
     try {
@@ -306,6 +331,15 @@ int main(int argc, char** argv) {
             }
             write_pfm(out + "_temporal.pfm", acc, W, H, 3);
             write_ppm(out + "_temporal.ppm", fb, W, H);
+        } else if (adaptive) {
+            const int tx = (W + 15) / 16, ty = (H + 15) / 16;
+            std::vector<int32_t> tile_spp((size_t)tx * ty);
+            ad_stats = pt.doTraceAdaptive(d, cam, f.bgra.data(), ad_min, ad_max, ad_target, seed, depth,
+                                          f.radiance.data(), tile_spp.data());
+            std::vector<float> px((size_t)W * H);
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x) px[(size_t)y * W + x] = (float)tile_spp[(size_t)(y / 16) * tx + x / 16];
+            write_pfm(out + "_spp.pfm", px, W, H, 1);
         } else {
             for (int i = 0; i < frames; ++i) {
                 if (yaw != 0.0 || truck[0] != 0.0 || truck[1] != 0.0 || truck[2] != 0.0)
@@ -346,6 +380,15 @@ int main(int argc, char** argv) {
                 write_pfm(out + "_svgf.pfm", clean, W, H, 3);
                 write_ppm(out + "_svgf.ppm", fb, W, H);
             }
+        }
+        if (adaptive) {
+            std::printf("{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"target\": %g, \"min_spp\": %d, "
+                        "\"max_spp\": %d, \"mean_spp\": %.2f, \"passes\": %d, \"unconverged_tiles\": %d, "
+                        "\"rays\": %llu, \"trace_ms\": %.3f, \"error_ms\": %.3f, \"out\": \"%s.ppm\"}\n",
+                        scene_file.c_str(), W, H, (double)ad_target, ad_min, ad_max,
+                        (double)ad_stats.samples / (double)ad_stats.pixels, ad_stats.passes, ad_stats.unconverged_tiles,
+                        (unsigned long long)ad_stats.traversals, ad_stats.trace_ms, ad_stats.error_ms, out.c_str());
+            return 0;
         }
         const tpt_stats& s = f.stats;
         std::printf("{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %llu, \"rays\": %llu, "
