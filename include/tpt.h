@@ -258,6 +258,21 @@ tpt_status tpt_scene_set_build_threads(tpt_scene* scene, int32_t threads);
  * range past the scene's object count. */
 tpt_status tpt_scene_set_transforms(tpt_scene* scene, uint32_t first_object, uint32_t n_objects,
                                     const float* vert_trans, const float* normal_trans);
+/* New object-space positions for the global vertex ids [first_vertex, first_vertex +
+ * n_vertices): xyz, 3 floats each, as tpt_scene_desc's vertices.  normals: nullable; null:
+ * the stored normals stay as they are.  Each pointer may be host or device memory (of the
+ * scene's device), detected per pointer as tpt_scene_create does.  Topology (indices, lut),
+ * materials and matrices are untouched.  A pending tpt_scene_build_async is joined and
+ * superseded, and the scene is unbuilt afterwards: call tpt_scene_build or
+ * tpt_scene_build_async before the next render.  The rebuilt scene is the scene
+ * tpt_scene_create + tpt_scene_build make of a desc holding these vertices, bit for bit
+ * (tpt_scene_read_world, tpt_scene_read_bvh, rendered frames).  A progressive accumulation
+ * does not survive it, as for tpt_scene_set_transforms.  The build is a full rebuild, not a
+ * refit (DESIGN.md section 5 "Deforming meshes").
+ * TPT_ERR_INVALID_ARG (nothing changes): null scene or vertices, n_vertices == 0, a range
+ * past the scene's vertex count, a device buffer of another device. */
+tpt_status tpt_scene_set_vertices(tpt_scene* scene, uint32_t first_vertex, uint32_t n_vertices,
+                                  const float* vertices, const float* normals);
 void tpt_scene_destroy(tpt_scene* scene);
 
 /* Equirect environment, RGBA8, row 0 = bottom (FreeImage order), already in
@@ -477,7 +492,7 @@ tpt_status tpt_denoise(tpt_scene* scene, int32_t width, int32_t height, const fl
  * before its scene.  It holds two sets of three float4 planes (accumulated colour +
  * history length; normal + depth; luminance moments + material id), 96 B per pixel,
  * and up to 56 B per pixel more to stage host buffers (tpt_temporal_motion: 68 B), 4 B
- * per face and 96 B per object.  After tpt_history_create and after tpt_history_reset
+ * per face and 96 B per object (tpt_temporal_deform: 24 B per vertex more).  After tpt_history_create and after tpt_history_reset
  * there is no state: the next tpt_temporal starts over. */
 typedef struct tpt_history tpt_history;
 tpt_status tpt_history_create(tpt_scene* scene, int32_t width, int32_t height, tpt_history** out);
@@ -551,8 +566,38 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* camera, const float* r
  * Everything else is tpt_temporal's, the refusals too (and a missing face guide).
  * Not tracked: shading that changes because something else moved -- a moved object's shadow
  * or its reflection on a wall that stood still is reprojected as if nothing had happened,
- * and `alpha` is what bounds that lag.  Lights do not move and meshes do not deform. */
+ * and `alpha` is what bounds that lag.  Lights do not move; meshes that deform are
+ * tpt_temporal_deform's. */
 tpt_status tpt_temporal_motion(tpt_history* h, const tpt_camera* camera, const float* radiance_in,
+                               const tpt_aov* guides, const tpt_temporal_params* params,
+                               float* radiance_out, float* variance_out, float* history_len_out,
+                               float* motion_out, uint8_t* bgra_out, tpt_temporal_stats* stats);
+
+/* tpt_temporal for a scene whose vertices moved (tpt_scene_set_vertices; or whose objects
+ * moved, tpt_scene_set_transforms: the world vertices hold the matrices) since the previous
+ * tpt_temporal_deform call on this history.  The caller has rebuilt the scene the history was
+ * created from and rendered `guides` (tpt_render_aov's first-hit buffers, not the mirror-path
+ * ones) from it.  Unlike the other temporal entry points this one reads the scene's world
+ * buffers: an unbuilt scene is refused, a pending tpt_scene_build_async is waited for.
+ * The history keeps a snapshot of the scene's world vertices and normals (24 B per vertex,
+ * allocated at the first call), copied device to device on the scene's stream at the end of
+ * every call.  It is the previous frame's only if no other call on this history -- another
+ * temporal entry point, or tpt_history_reset -- came in between; otherwise, with a valid
+ * history, every hit pixel is disoccluded for that one frame and misses reproject as ever.
+ * A hit pixel's face id f names its triangle, indices[3f..3f+2].  If the triangle's 9 world
+ * position floats and 9 world normal floats are bit-equal to the snapshot's, the pixel takes
+ * tpt_temporal's path untouched: with nothing deformed the outputs and the new state are
+ * tpt_temporal's bit for bit.  Otherwise (u, v) are the barycentrics of the pixel-centre ray on
+ * the current triangle, w = 1 - u - v, and with a', b', c', na', nb', nc' the snapshot's corners
+ *   X' = (w a' + u b') + v c',   ne = normalize((w na' + u nb') + v nc'):
+ * X' is projected into the previous camera and measured against the previous origin, and the
+ * normal test compares the previous frame's normals with ne.  A hit pixel is disoccluded when
+ * its face id is outside [0, n_faces), its triangle is flat (determinant 0) or u, v or X' is
+ * not finite.  guides, motion_out and everything else are tpt_temporal_motion's, the refusals
+ * too (and an unbuilt scene).  DESIGN.md section 5 "Deforming meshes" holds the definition.
+ * Not tracked: a deforming object's shadow and its reflections (in mirrors too), reprojected as
+ * if nothing had happened; topology changes.  Lights do not move. */
+tpt_status tpt_temporal_deform(tpt_history* h, const tpt_camera* camera, const float* radiance_in,
                                const tpt_aov* guides, const tpt_temporal_params* params,
                                float* radiance_out, float* variance_out, float* history_len_out,
                                float* motion_out, uint8_t* bgra_out, tpt_temporal_stats* stats);

@@ -90,6 +90,15 @@ public:
         built_ = false;
         return *this;
     }
+    // New object-space positions (xyz each) for vertices first, first + 1, ...
+    // (tpt_scene_set_vertices; normals null: the stored ones stay; host or device memory).  The
+    // scene is unbuilt afterwards: build() comes next.
+    DeviceScene& setVertices(uint32_t first, uint32_t n_vertices, const float* vertices,
+                             const float* normals = nullptr) {
+        check(tpt_scene_set_vertices(scene_.get(), first, n_vertices, vertices, normals));
+        built_ = false;
+        return *this;
+    }
     bool built() const { return built_; }
     tpt_scene* handle() const { return scene_.get(); }
     uint32_t nFaces() const { return n_faces_; }
@@ -409,6 +418,20 @@ public:
                                       const tpt_temporal_params& params = defaultTemporal()) {
         tpt_temporal_stats st{};
         check(tpt_temporal_motion(history.handle(), &camera.c, radiance_in, &guides, &params, radiance_out, variance,
+                                  history_len, motion, framebuffer, &st));
+        return st;
+    }
+
+    // temporal() for a scene whose vertices moved since the previous temporalDeform() on
+    // `history` (tpt_temporal_deform: setVertices + build, then this frame's render and feature
+    // buffers, `face` included).  The history's scene must be built.  motion as temporalMotion's.
+    tpt_temporal_stats temporalDeform(History& history, const Camera& camera, const float* radiance_in,
+                                      const tpt_aov& guides, float* radiance_out, float* variance = nullptr,
+                                      float* history_len = nullptr, float* motion = nullptr,
+                                      uint8_t* framebuffer = nullptr,
+                                      const tpt_temporal_params& params = defaultTemporal()) {
+        tpt_temporal_stats st{};
+        check(tpt_temporal_deform(history.handle(), &camera.c, radiance_in, &guides, &params, radiance_out, variance,
                                   history_len, motion, framebuffer, &st));
         return st;
     }

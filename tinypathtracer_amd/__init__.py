@@ -276,6 +276,28 @@ class DeviceScene:
         self.built = False
         return self
 
+    def set_vertices(self, first: int, vertices, normals=None):
+        """New object-space positions for vertices first, first + 1, ... (tpt_scene_set_vertices):
+        vertices [n, 3] float32 like Scene.vertices; normals likewise, or None to keep the stored
+        ones.  Each a numpy array or a torch CUDA tensor of the scene's device.  Topology,
+        materials and matrices stay; the scene is unbuilt afterwards, so build() comes next.  A
+        progressive accumulation does not survive it.  self.scene keeps the arrays it was made of."""
+        def plane(a):
+            if a is None:
+                return None
+            if not hasattr(a, "data_ptr"):       # numpy, or anything numpy can read
+                return np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+            if str(a.dtype) != "torch.float32" or not a.is_contiguous() or a.numel() % 3:
+                raise ValueError("set_vertices: a contiguous float32 tensor of xyz triples")
+            return a
+        count = lambda a: a.size // 3 if isinstance(a, np.ndarray) else a.numel() // 3
+        v, n = plane(vertices), plane(normals)
+        if n is not None and count(n) != count(v):
+            raise ValueError(f"normals: need {count(v)} vertices, got {count(n)}")
+        check(lib().tpt_scene_set_vertices(self.handle, int(first), count(v), _addr(v), _addr(n)))
+        self.built = False
+        return self
+
     def read_bvh(self):
         nf = self.scene.n_faces
         nodes = np.zeros(2 * nf - 1, NODE_DTYPE)
@@ -808,7 +830,8 @@ class PathTracer:
                  normal_min: float = TEMPORAL_DEFAULTS["normal_min"],
                  max_history: int = TEMPORAL_DEFAULTS["max_history"],
                  demodulate: bool = TEMPORAL_DEFAULTS["demodulate"], out=None, variance=None, history_len=None,
-                 framebuffer=None, flags: int = 0, stats=None, motion: bool = False, motion_out=None):
+                 framebuffer=None, flags: int = 0, stats=None, motion: bool = False, motion_out=None,
+                 deform: bool = False):
         """Temporal reprojection and accumulation (tpt_temporal, DESIGN.md section 5
         "Post-pass"): this frame's `radiance` [H, W, 3] and its feature buffers
         aov["normal"], aov["depth"], aov["material"] (and aov["albedo"] with
@@ -823,15 +846,20 @@ class PathTracer:
         since the previous call (DeviceScene.set_transforms + build, then this frame's
         render and feature buffers); aov["face"] is needed too, and motion_out, an
         optional [H, W, 2] float32 buffer, receives each pixel's reprojected minus its own
-        coordinates in pixels."""
+        coordinates in pixels.
+        deform=True (tpt_temporal_deform): vertices of the history's scene may have moved since
+        the previous deform=True call (DeviceScene.set_vertices + build); the scene must be
+        built; aov["face"] and motion_out as for motion=True."""
         W, H = self.m_width, self.m_height
-        if motion_out is not None and not motion:
-            raise ValueError("motion_out needs motion=True")
+        if motion and deform:
+            raise ValueError("motion and deform are two entry points: pick one")
+        if motion_out is not None and not (motion or deform):
+            raise ValueError("motion_out needs motion=True or deform=True")
         if (history.width, history.height) != (W, H):
             raise ValueError(f"the history is {history.width} x {history.height}, the frame {W} x {H}")
         _check_plane("radiance", radiance, W, H)
         g = _take_guides(aov, (("albedo",) if demodulate else ()) + ("normal", "depth", "material") +
-                         (("face",) if motion else ()), W, H)
+                         (("face",) if motion or deform else ()), W, H)
         if out is None:
             out = np.zeros((H, W, 3), np.float32)
         _check_plane("radiance", out, W, H)
@@ -843,10 +871,11 @@ class PathTracer:
                                 int(flags) | (_lib.TEMPORAL_DEMODULATE if demodulate else 0))
         st = _lib.TemporalStats()
         cam = camera.to_c()
-        if motion:
-            check(lib().tpt_temporal_motion(history.handle, C.byref(cam), _addr(radiance), C.byref(g), C.byref(p),
-                                            _addr(out), _addr(variance), _addr(history_len), _addr(motion_out),
-                                            _addr(framebuffer), C.byref(st)))
+        if motion or deform:
+            entry = lib().tpt_temporal_motion if motion else lib().tpt_temporal_deform
+            check(entry(history.handle, C.byref(cam), _addr(radiance), C.byref(g), C.byref(p),
+                        _addr(out), _addr(variance), _addr(history_len), _addr(motion_out),
+                        _addr(framebuffer), C.byref(st)))
         else:
             check(lib().tpt_temporal(history.handle, C.byref(cam), _addr(radiance), C.byref(g), C.byref(p), _addr(out),
                                      _addr(variance), _addr(history_len), _addr(framebuffer), C.byref(st)))

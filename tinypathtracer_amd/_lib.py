@@ -165,6 +165,7 @@ SIGNATURES = [
     ("tpt_scene_build_async", C.c_int, [C.c_void_p]),
     ("tpt_scene_set_build_threads", C.c_int, [C.c_void_p, C.c_int32]),
     ("tpt_scene_set_transforms", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("tpt_scene_set_vertices", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("tpt_scene_destroy", None, [C.c_void_p]),
     ("tpt_env_create", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
     ("tpt_env_destroy", None, [C.c_void_p]),
@@ -197,6 +198,9 @@ SIGNATURES = [
                                C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(TemporalStats)]),
     ("tpt_temporal_motion", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(Aov),
+                                      C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(TemporalStats)]),
+    ("tpt_temporal_deform", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(Aov),
                                       C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.POINTER(TemporalStats)]),
     ("tpt_temporal_path", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(Aov), C.c_void_p, C.c_void_p,

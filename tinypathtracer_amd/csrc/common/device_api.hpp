@@ -406,6 +406,22 @@ struct TemporalPathArgs {
 };
 hipError_t launch_temporal_path(const TemporalArgs& a, const TemporalPathArgs& pa, hipStream_t s);
 
+// post.hip: what the variant that follows deforming meshes (tpt_temporal_deform) reads and writes
+// on top of TemporalArgs: the scene's topology and world buffers as they are now, and the
+// history's snapshot of the world buffers as they were at the previous call.
+struct DeformArgs {
+    const int32_t* face;                 // W*H: this frame's face ids (-1 on a miss)
+    const uint32_t* indices;             // 3 per face
+    const float* wverts;                 // 3 per vertex: the scene's world positions
+    const float* wnorms;                 // 3 per vertex: its world normals
+    const float* prev_wverts;            // the snapshot's positions (read only where snap_valid)
+    const float* prev_wnorms;            // the snapshot's normals
+    float* motion_out;                   // nullable, W*H*2
+    int32_t n_faces;
+    int32_t snap_valid;                  // 0: the snapshot is not the previous call's: hit pixels are disoccluded
+};
+hipError_t launch_temporal_deform(const TemporalArgs& a, const DeformArgs& de, hipStream_t s);
+
 // post.hip: the variance-guided a-trous filter (tpt_denoise_svgf; DESIGN.md section 5
 // "Post-pass").  tpt_denoise's planes, the colour plane's fourth component carrying the
 // variance: colour = (r, g, b, v), guide = (n.xyz, z).

@@ -471,9 +471,9 @@ struct tpt_scene {
     }
 };
 
-// tpt_temporal's and tpt_temporal_motion's state (post.hip k_temporal, k_temporal_motion): two
-// sets of three float4 planes that ping-pong, the previous call's camera and object
-// transforms, device staging of host buffers.
+// The temporal entry points' state (post.hip k_temporal, k_temporal_motion, k_temporal_path,
+// k_temporal_deform): two sets of three float4 planes that ping-pong, the previous call's camera
+// and object transforms, device staging of host buffers.
 struct tpt_history {
     tpt_scene* scene = nullptr;             // the stream; outlives the history's last tpt_temporal
     int device = 0;
@@ -501,6 +501,12 @@ struct tpt_history {
     DevBuf<float4> points[2];
     DevBuf<int32_t> st_bounces;
     DevBuf<float> st_points;
+    // tpt_temporal_deform: the scene's world vertices and normals as they were at the end of the
+    // last tpt_temporal_deform call (24 B per vertex, allocated at the first one).  Every call on
+    // the history and every reset advances `serial`; the snapshot is the previous call's only
+    // while snap_serial is still the current serial.
+    DevBuf<float> snap_verts, snap_norms;
+    uint64_t serial = 0, snap_serial = ~0ull;
     hipEvent_t ev[2] = {nullptr, nullptr};
 
     ~tpt_history() {

@@ -1,6 +1,6 @@
 // api_post.cpp -- the post-pass entry points of the C-ABI (post.hip): tpt_render_aov, tpt_render_aov_path,
-// tpt_render_aov_path_points, tpt_denoise, tpt_history_*, tpt_temporal, tpt_temporal_motion, tpt_temporal_path
-// and tpt_denoise_svgf.  Each takes its buffers from either
+// tpt_render_aov_path_points, tpt_denoise, tpt_history_*, tpt_temporal, tpt_temporal_motion, tpt_temporal_path,
+// tpt_temporal_deform and tpt_denoise_svgf.  Each takes its buffers from either
 // side: host buffers go through the device staging the scene / history keeps
 // (api_internal.hpp Staging).
 #include <cmath>
@@ -283,6 +283,7 @@ tpt_status tpt_history_reset(tpt_history* h) {
     if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
     h->valid = false;
     h->prev_vert_trans.clear();
+    ++h->serial;   // tpt_temporal_deform's snapshot is no longer the previous call's
     return TPT_OK;
 }
 
@@ -295,12 +296,14 @@ struct PathInputs {
     float point_tol;
 };
 
-// tpt_temporal (motion false: face guide and motion_out unused), tpt_temporal_motion and
-// tpt_temporal_path (path not null; never with motion)
+// tpt_temporal (motion false: face guide and motion_out unused), tpt_temporal_motion,
+// tpt_temporal_path (path not null; never with motion) and tpt_temporal_deform (deform; never
+// with motion or path)
 static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const float* radiance_in,
                                 const tpt_aov* guides, const tpt_temporal_params* p, float* radiance_out,
                                 float* variance_out, float* history_len_out, float* motion_out, uint8_t* bgra_out,
-                                tpt_temporal_stats* stats, bool motion, const PathInputs* path = nullptr) {
+                                tpt_temporal_stats* stats, bool motion, const PathInputs* path = nullptr,
+                                bool deform = false) {
     if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
     if (!cam) return fail(TPT_ERR_INVALID_ARG, "null camera");
     if (!radiance_in) return fail(TPT_ERR_INVALID_ARG, "null radiance_in");
@@ -312,6 +315,8 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
         return fail(TPT_ERR_INVALID_ARG, "temporal accumulation needs the normal, depth and material guides");
     if (motion && !guides->face)
         return fail(TPT_ERR_INVALID_ARG, "motion-aware accumulation needs the face guides too");
+    if (deform && !guides->face)
+        return fail(TPT_ERR_INVALID_ARG, "accumulation on deforming meshes needs the face guides too");
     if (demod && !guides->albedo)
         return fail(TPT_ERR_INVALID_ARG, "TPT_TEMPORAL_DEMODULATE needs the albedo guides");
     if (!(p->alpha > 0.0f && p->alpha <= 1.0f)) return fail(TPT_ERR_INVALID_ARG, "alpha must be in (0, 1]");
@@ -324,6 +329,15 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
         return fail(TPT_ERR_INVALID_ARG, "accumulation through mirrors needs the bounce counts and the terminal points");
     if (path && !(path->point_tol > 0.0f)) return fail(TPT_ERR_INVALID_ARG, "point_tol must be > 0");
     tpt_scene* s = h->scene;
+    if (deform) {
+        // the only entry point that reads the scene's world buffers
+        if (!s->built) return fail(TPT_ERR_INVALID_ARG, "scene not built: tpt_temporal_deform reads its world vertices");
+        const tpt_status bs = finish_pending(s);
+        if (bs != TPT_OK) return bs;
+    }
+    // the snapshot is the previous call's only if that call was tpt_temporal_deform
+    const bool snap_valid = deform && h->snap_verts.p && h->snap_serial == h->serial;
+    ++h->serial;
     DeviceGuard g(s->device);
     hipStream_t st = s->stream;
     const int W = h->width, H = h->height;
@@ -370,6 +384,21 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
         HIP_OR_FAIL(sg.in(h->st_face, guides->face, npix, &mo.face));
         HIP_OR_FAIL(sg.out(h->st_motion, motion_out, 2 * npix, &mo.motion_out));
     }
+    tpt::DeformArgs de{};
+    const size_t nv3 = 3 * (size_t)s->n_vertices;
+    if (deform) {
+        HIP_OR_FAIL(h->snap_verts.alloc(nv3));
+        HIP_OR_FAIL(h->snap_norms.alloc(nv3));
+        de.indices = s->indices.p;
+        de.wverts = s->wverts.p;
+        de.wnorms = s->wnorms.p;
+        de.prev_wverts = h->snap_verts.p;
+        de.prev_wnorms = h->snap_norms.p;
+        de.n_faces = s->n_faces;
+        de.snap_valid = snap_valid ? 1 : 0;
+        HIP_OR_FAIL(sg.in(h->st_face, guides->face, npix, &de.face));
+        HIP_OR_FAIL(sg.out(h->st_motion, motion_out, 2 * npix, &de.motion_out));
+    }
     tpt::TemporalPathArgs pa{};
     if (path) {
         for (auto& plane : h->points)
@@ -399,8 +428,13 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
     HIP_OR_FAIL(hipEventRecord(h->ev[0], st));
     HIP_OR_FAIL(path     ? tpt::launch_temporal_path(a, pa, st)
                 : motion ? tpt::launch_temporal_motion(a, mo, st)
+                : deform ? tpt::launch_temporal_deform(a, de, st)
                          : tpt::launch_temporal(a, st));
     HIP_OR_FAIL(hipEventRecord(h->ev[1], st));
+    if (deform) {   // the world buffers as this call saw them, for the next one
+        HIP_OR_FAIL(hipMemcpyAsync(h->snap_verts.p, s->wverts.p, nv3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_OR_FAIL(hipMemcpyAsync(h->snap_norms.p, s->wnorms.p, nv3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
     HIP_OR_FAIL(sg.finish());
     HIP_OR_FAIL(h->count.fetch(st));
     HIP_OR_FAIL(hipStreamSynchronize(st));
@@ -410,6 +444,7 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
     h->valid = true;
     if (!invert4(cam->c2w, h->prev_inv)) h->valid = false;   // a singular c2w: nothing can be reprojected into it
     h->prev = cc;
+    if (deform) h->snap_serial = h->serial;
     if (stats) {
         HIP_OR_FAIL(elapsed_ms(h->ev[0], h->ev[1], &stats->kernel_ms));
         stats->reprojected = h->count.sum(0);
@@ -430,6 +465,16 @@ tpt_status tpt_temporal_motion(tpt_history* h, const tpt_camera* cam, const floa
                                tpt_temporal_stats* stats) {
     return temporal_pass(h, cam, radiance_in, guides, p, radiance_out, variance_out, history_len_out, motion_out,
                          bgra_out, stats, true);
+}
+
+// tpt_temporal for a scene whose vertices moved (post.hip k_temporal_deform; DESIGN.md section 5
+// "Deforming meshes").
+tpt_status tpt_temporal_deform(tpt_history* h, const tpt_camera* cam, const float* radiance_in, const tpt_aov* guides,
+                               const tpt_temporal_params* p, float* radiance_out, float* variance_out,
+                               float* history_len_out, float* motion_out, uint8_t* bgra_out,
+                               tpt_temporal_stats* stats) {
+    return temporal_pass(h, cam, radiance_in, guides, p, radiance_out, variance_out, history_len_out, motion_out,
+                         bgra_out, stats, false, nullptr, true);
 }
 
 // tpt_temporal on mirror-path guides (post.hip k_temporal_path; DESIGN.md section 5 "Temporal

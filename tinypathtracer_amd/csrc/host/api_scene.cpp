@@ -657,6 +657,36 @@ tpt_status tpt_scene_set_transforms(tpt_scene* s, uint32_t first, uint32_t n, co
     return TPT_OK;
 }
 
+// New object-space positions (and normals) for some vertices.  Topology, materials and matrices
+// stay: the next build transforms the vertices again and rebuilds the BVH from them.
+tpt_status tpt_scene_set_vertices(tpt_scene* s, uint32_t first, uint32_t n, const float* vertices,
+                                  const float* normals) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (!vertices) return fail(TPT_ERR_INVALID_ARG, "null vertices");
+    if (n == 0) return fail(TPT_ERR_INVALID_ARG, "n_vertices must be > 0");
+    if ((uint64_t)first + (uint64_t)n > (uint64_t)s->n_vertices)
+        return fail(TPT_ERR_INVALID_ARG, "vertex range past the scene's vertex count");
+    DeviceGuard g(s->device);
+    // each pointer host or device memory, as tpt_scene_create takes them; a device buffer is
+    // copied device to device on the scene's stream, so it must live on the scene's device
+    int v_owner = -1, n_owner = -1;
+    const bool verts_dev = is_device_ptr(vertices, &v_owner), norms_dev = is_device_ptr(normals, &n_owner);
+    if ((v_owner >= 0 && v_owner != s->device) || (n_owner >= 0 && n_owner != s->device))
+        return fail(TPT_ERR_INVALID_ARG, "device vertex/normal buffers must live on the scene's device");
+    if (s->trees) s->trees->join();   // a pending asynchronous build is superseded, as by the next build
+    s->pending = false;
+    s->built = false;
+    s->acc_valid = false;             // a progressive accumulation's sums belong to the scene as it was
+    const size_t off = 3 * (size_t)first, bytes = 3 * (size_t)n * sizeof(float);
+    HIP_OR_FAIL(hipMemcpyAsync(s->vertices.p + off, vertices, bytes,
+                               verts_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+    if (normals)
+        HIP_OR_FAIL(hipMemcpyAsync(s->normals.p + off, normals, bytes,
+                                   norms_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+    HIP_OR_FAIL(hipStreamSynchronize(s->stream));   // (the caller's arrays are only read during the call)
+    return TPT_OK;
+}
+
 tpt_status tpt_scene_set_build_threads(tpt_scene* s, int32_t threads) {
     if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
     s->build_threads = threads;

@@ -19,9 +19,10 @@
 //    between two colour planes, no atomics.  Each tap is two 16-B loads per lane;
 //    a wave of the direct kernel is a 64-pixel row segment, so its lanes read
 //    1 KiB of contiguous addresses per plane at every step size.
-//  * k_temporal / k_temporal_motion / k_temporal_path (temporal_kernel.hpp): reprojection and
-//    accumulation across frames (tpt_temporal; tpt_temporal_motion, which follows objects that
-//    moved; tpt_temporal_path, which follows reflections in mirrors).
+//  * k_temporal / k_temporal_motion / k_temporal_path / k_temporal_deform (temporal_kernel.hpp):
+//    reprojection and accumulation across frames (tpt_temporal; tpt_temporal_motion, which follows
+//    objects that moved; tpt_temporal_path, which follows reflections in mirrors;
+//    tpt_temporal_deform, which follows meshes whose vertices moved).
 //  * k_svgf_pack / k_svgf_estimate / k_svgf_atrous / k_svgf_atrous_lds /
 //    k_svgf_resolve: the variance-guided filter (tpt_denoise_svgf) on the same two
 //    planes, the variance in the colour plane's fourth component.
@@ -382,6 +383,9 @@ constexpr float kMinWsum = 1.0f / 16.0f;     // least sum of valid bilinear weig
 // which leave all four instantiations' instructions as they were.
 // A third compilation, with TPT_TEMPORAL_PATH, is k_temporal_path (tpt_temporal_path): the
 // pass on mirror-path guides, which compares bounce counts and terminal points as well.
+// A fourth, with TPT_TEMPORAL_DEFORM, is k_temporal_deform (tpt_temporal_deform): the pass
+// that follows deforming meshes through the previous frame's vertices.
+#define TPT_TEMPORAL_DEFORM 0
 #define TPT_TEMPORAL_PATH 0
 #define TPT_TEMPORAL_MOTION 0
 #include "temporal_kernel.hpp"
@@ -394,6 +398,12 @@ constexpr float kMinWsum = 1.0f / 16.0f;     // least sum of valid bilinear weig
 #define TPT_TEMPORAL_PATH 1
 #include "temporal_kernel.hpp"
 #undef TPT_TEMPORAL_PATH
+#undef TPT_TEMPORAL_DEFORM
+#define TPT_TEMPORAL_PATH 0
+#define TPT_TEMPORAL_DEFORM 1
+#include "temporal_kernel.hpp"
+#undef TPT_TEMPORAL_DEFORM
+#undef TPT_TEMPORAL_PATH
 #undef TPT_TEMPORAL_MOTION
 
 hipError_t launch_temporal_motion(const TemporalArgs& a, const MotionArgs& mo, hipStream_t s) {
@@ -404,6 +414,9 @@ hipError_t launch_temporal(const TemporalArgs& a, hipStream_t s) {
 }
 hipError_t launch_temporal_path(const TemporalArgs& a, const TemporalPathArgs& pa, hipStream_t s) {
     return launch_tiles_or_rows(a.tiles != 0, k_temporal_path<true>, 0, k_temporal_path<false>, a.width, a.height, s, a, pa);
+}
+hipError_t launch_temporal_deform(const TemporalArgs& a, const DeformArgs& de, hipStream_t s) {
+    return launch_tiles_or_rows(a.tiles != 0, k_temporal_deform<true>, 0, k_temporal_deform<false>, a.width, a.height, s, a, de);
 }
 
 // ---- the variance-guided a-trous filter (Schied et al. 2017; DESIGN.md section 5 "Post-pass" holds the definition) ----

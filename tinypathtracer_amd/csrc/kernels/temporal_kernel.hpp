@@ -1,6 +1,7 @@
 // temporal_kernel.hpp -- the text of k_temporal, included by post.hip once as it is, once with
-// TPT_TEMPORAL_MOTION as k_temporal_motion and once with TPT_TEMPORAL_PATH as k_temporal_path.
-// No include guard: it is meant to be read three times.
+// TPT_TEMPORAL_MOTION as k_temporal_motion, once with TPT_TEMPORAL_PATH as k_temporal_path and
+// once with TPT_TEMPORAL_DEFORM as k_temporal_deform.  No include guard: it is meant to be read
+// four times.
 
 // One lane per pixel, one launch per frame.  The lane reads its pixel of the caller's
 // planes (3-float planes directly: a pack step would write and read them once more),
@@ -27,8 +28,22 @@
 // plane-3 gathers are issued with the others, behind a wave-level ballot of k > 0: a wave
 // without a mirror pixel moves k_temporal's bytes and the 4-byte k.  With k = 0 everywhere
 // every added test passes and the arithmetic is k_temporal's: the same bits.
+//
+// TPT_TEMPORAL_DEFORM (k_temporal_deform; DESIGN.md section 5 "Deforming meshes"): a hit pixel
+// reads its face id, the face's three vertex indices and, per corner, the world position and
+// normal as the scene holds them now and as the history's snapshot held them at the previous call:
+// 3 + 36 words, the 36 issued together once the indices are there and ahead of their use, as the
+// taps' loads are.  Neighbouring lanes share faces, so most of it is a broadcast from L2.  A
+// triangle whose 18 words are bit-equal to the snapshot's takes k_temporal's path untouched (the
+// test-and-skip that kMotionIdentity is for k_temporal_motion: with nothing deformed, the same
+// bits).  Otherwise the pixel-centre ray's barycentrics on the current triangle (rayHitTriangle's
+// arithmetic, geometry_queries.h:65-86, without its range tests) are applied to the snapshot's
+// corners: X' is where that point of that triangle was, ne the normal it had.  `mo` is DeformArgs
+// here: the face plane and motion_out go by the names the motion variant's blocks use.
 template <bool TILES>
-#if TPT_TEMPORAL_MOTION
+#if TPT_TEMPORAL_DEFORM
+__global__ __launch_bounds__(256) void k_temporal_deform(TemporalArgs a, DeformArgs mo) {
+#elif TPT_TEMPORAL_MOTION
 __global__ __launch_bounds__(256) void k_temporal_motion(TemporalArgs a, MotionArgs mo) {
 #elif TPT_TEMPORAL_PATH
 __global__ __launch_bounds__(256) void k_temporal_path(TemporalArgs a, TemporalPathArgs pa) {
@@ -57,7 +72,7 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
         V3 pe = v3(0.0f, 0.0f, 0.0f);                      // where the path ended (k > 0 only)
         if (kb > 0) pe = v3(pa.points[3 * p], pa.points[3 * p + 1], pa.points[3 * p + 2]);
 #endif
-#if TPT_TEMPORAL_MOTION
+#if TPT_TEMPORAL_MOTION || TPT_TEMPORAL_DEFORM
         const int face = mo.face[p];
         float mvx = 0.0f, mvy = 0.0f;                      // where the pixel came from, minus where it is
 #endif
@@ -72,7 +87,61 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
             V3 ro, rd;   // the pixel-centre ray of the current camera: k_aov's
             centre_ray(a, x, y, ro, rd);
             // a hit reprojects its world position, a miss its direction (a point at infinity)
-#if TPT_TEMPORAL_MOTION
+#if TPT_TEMPORAL_DEFORM
+            V3 X = hit ? ro + (z * rd) : rd;
+            V3 ne = n;                                     // the normal as the previous frame held it
+            bool tracked = true;
+            if (hit) {
+                // (the face id is compared before it indexes anything)
+                tracked = mo.snap_valid != 0 && (unsigned)face < (unsigned)mo.n_faces;
+                if (tracked) {
+                    const uint32_t* ix = mo.indices + 3 * (size_t)face;
+                    const size_t i0 = 3 * (size_t)ix[0], i1 = 3 * (size_t)ix[1], i2 = 3 * (size_t)ix[2];
+                    // all 36 words before the first is used: one round trip, not twelve
+                    float cv[9], pv[9], pn[9], cn[9];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        cv[k] = mo.wverts[i0 + k];
+                        cv[3 + k] = mo.wverts[i1 + k];
+                        cv[6 + k] = mo.wverts[i2 + k];
+                        pv[k] = mo.prev_wverts[i0 + k];
+                        pv[3 + k] = mo.prev_wverts[i1 + k];
+                        pv[6 + k] = mo.prev_wverts[i2 + k];
+                        pn[k] = mo.prev_wnorms[i0 + k];
+                        pn[3 + k] = mo.prev_wnorms[i1 + k];
+                        pn[6 + k] = mo.prev_wnorms[i2 + k];
+                        cn[k] = mo.wnorms[i0 + k];
+                        cn[3 + k] = mo.wnorms[i1 + k];
+                        cn[6 + k] = mo.wnorms[i2 + k];
+                    }
+                    int differ = 0;
+#pragma unroll
+                    for (int k = 0; k < 9; ++k)
+                        differ |= (__float_as_int(cv[k]) ^ __float_as_int(pv[k])) | (__float_as_int(cn[k]) ^ __float_as_int(pn[k]));
+                    if (differ != 0) {
+                        const V3 v0 = v3(cv[0], cv[1], cv[2]);
+                        const V3 e1 = v3(cv[3], cv[4], cv[5]) - v0, e2 = v3(cv[6], cv[7], cv[8]) - v0;
+                        const V3 tv = ro - v0;
+                        const V3 pp = cross(rd, e2);
+                        const V3 qq = cross(tv, e1);
+                        const float denom = dot(pp, e1);
+                        const float id = 1.0f / denom;
+                        const float u = dot(pp, tv) * id;
+                        const float v = dot(qq, rd) * id;
+                        const float w = 1.0f - u - v;
+                        X = ((w * v3(pv[0], pv[1], pv[2])) + (u * v3(pv[3], pv[4], pv[5]))) + (v * v3(pv[6], pv[7], pv[8]));
+                        const V3 gn = ((w * v3(pn[0], pn[1], pn[2])) + (u * v3(pn[3], pn[4], pn[5]))) + (v * v3(pn[6], pn[7], pn[8]));
+                        // a square root and divisions, not frsqrt: its 2e-3 would decide the normal rule
+                        const float len = fsqrt(norm2(gn));
+                        ne = v3(gn.x / len, gn.y / len, gn.z / len);
+                        // a flat triangle (the determinant the triangle test rejects) and whatever is
+                        // not finite: u and v in X' make it non-finite when they are
+                        tracked = denom != 0.0f && __builtin_isfinite(u) && __builtin_isfinite(v) &&
+                                  __builtin_isfinite(X.x) && __builtin_isfinite(X.y) && __builtin_isfinite(X.z);
+                    }
+                }
+            }
+#elif TPT_TEMPORAL_MOTION
             V3 X = hit ? ro + (z * rd) : rd;
             V3 ne = n;                                     // the normal as the previous frame held it
             bool tracked = true;
@@ -102,7 +171,7 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
             mat4_vec4(a.prev_inv, X.x, X.y, X.z, hit ? 1.0f : 0.0f, loc);
             float dist = 0.0f;
             if (hit) dist = fsqrt(norm2(X - v3(a.prev_origin[0], a.prev_origin[1], a.prev_origin[2])));
-#if TPT_TEMPORAL_MOTION
+#if TPT_TEMPORAL_MOTION || TPT_TEMPORAL_DEFORM
             if (loc[2] < 0.0f && tracked) {
 #else
             if (loc[2] < 0.0f) {
@@ -113,7 +182,7 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
                 const float rx = rintf(fx), ry = rintf(fy);
                 if (fabsf(fx - rx) < kSnap) fx = rx;
                 if (fabsf(fy - ry) < kSnap) fy = ry;
-#if TPT_TEMPORAL_MOTION
+#if TPT_TEMPORAL_MOTION || TPT_TEMPORAL_DEFORM
                 if (__builtin_isfinite(fx) && __builtin_isfinite(fy)) {
                     mvx = fx - (float)x;
                     mvy = fy - (float)y;
@@ -168,7 +237,7 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
                         if (hit) {
                             const float4 g = s1[t];
                             ok = ok && fabsf(g.w - dist) <= a.depth_tol * dist &&
-#if TPT_TEMPORAL_MOTION
+#if TPT_TEMPORAL_MOTION || TPT_TEMPORAL_DEFORM
                                  (g.x * ne.x + g.y * ne.y) + g.z * ne.z >= a.normal_min;
 #else
                                  (g.x * n.x + g.y * n.y) + g.z * n.z >= a.normal_min;
@@ -225,7 +294,7 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
         }
         if (a.variance_out) a.variance_out[p] = fmaxf(m2 - m1 * m1, 0.0f);
         if (a.history_out) a.history_out[p] = N;
-#if TPT_TEMPORAL_MOTION
+#if TPT_TEMPORAL_MOTION || TPT_TEMPORAL_DEFORM
         if (mo.motion_out) {
             mo.motion_out[2 * p] = mvx;
             mo.motion_out[2 * p + 1] = mvy;

@@ -7,7 +7,7 @@
 //              [--seed S] [--env equirect.jpg|.ppm|--sky] [--out prefix] [--device i]
 //              [--frames F [--progressive]] [--aov] [--denoise [iterations]]
 //              [--temporal] [--yaw DEG] [--svgf [iterations]] [--aov-path [bounces]]
-//              [--move OBJ DX DY DZ] [--spin OBJ DEG]
+//              [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP]
 //              [--adaptive TARGET [--min-spp N] [--max-spp N]]
 // --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
 // <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
@@ -36,6 +36,10 @@
 // bounding box (with both, it turns first).  Either needs --frames and --temporal: every
 // frame sets the transforms (tpt_scene_set_transforms), rebuilds, renders, and goes
 // through tpt_temporal_motion, which follows the moved objects.
+// --wave OBJ AMP displaces every vertex of object OBJ along its own object-space normal by
+// AMP sin(6 y_obj + frame) in frame `frame` (a deformation no matrix describes), under the same
+// conditions as --move: every frame sets the vertices (tpt_scene_set_vertices), rebuilds, renders,
+// and goes through tpt_temporal_deform, which follows the deformed mesh (and --move / --spin too).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -95,7 +99,7 @@ const char* kUsage =
     "usage: %s scene.gltf [--width W] [--height H] [--spp N] [--depth D] [--seed S] "
     "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]] "
     "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]] "
-    "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG] [--truck DX DY DZ] "
+    "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP] [--truck DX DY DZ] "
     "[--temporal-path [bounces]] [--adaptive TARGET [--min-spp N] [--max-spp N]]\n";
 
 // The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
@@ -163,6 +167,43 @@ void moved_matrix(const ObjectMotion& om, const float* m0, int frame, float* out
     }
 }
 
+// --wave: object `object`'s vertices are the ids [first, first + rest.size() / 3) (those of
+// that range its faces do not name keep their place)
+struct ObjectWave {
+    uint32_t object = 0;
+    double amp = 0.0;
+    uint32_t first = 0;
+    std::vector<float> rest;        // the loaded positions of the range
+    std::vector<uint8_t> mine;      // per vertex of the range: named by a face of the object
+};
+
+void wave_range(const tpt_scene_desc& d, ObjectWave& ow) {
+    const uint32_t begin = (uint32_t)d.lut[ow.object].begin,
+                   end = ow.object + 1 < d.n_objects ? (uint32_t)d.lut[ow.object + 1].begin : d.n_faces;
+    uint32_t lo = d.n_vertices, hi = 0;
+    for (uint32_t i = 3 * begin; i < 3 * end; ++i) {
+        lo = std::min(lo, d.indices[i]);
+        hi = std::max(hi, d.indices[i]);
+    }
+    if (lo > hi) throw std::runtime_error("--wave: the object has no faces");
+    ow.first = lo;
+    ow.rest.assign(d.vertices + 3 * (size_t)lo, d.vertices + 3 * ((size_t)hi + 1));
+    ow.mine.assign((size_t)hi - lo + 1, 0);
+    for (uint32_t i = 3 * begin; i < 3 * end; ++i) ow.mine[d.indices[i] - lo] = 1;
+}
+
+// Frame `frame`'s positions of the range: rest + AMP sin(6 y + frame) n, in float; frame 0 is
+// displaced too (sin(6 y) is not 0), so every frame of a run is one pose of the same wave
+void waved_vertices(const tpt_scene_desc& d, const ObjectWave& ow, int frame, std::vector<float>& out) {
+    out = ow.rest;
+    for (size_t k = 0; k < ow.mine.size(); ++k) {
+        if (!ow.mine[k]) continue;
+        const float* n = d.normals + 3 * ((size_t)ow.first + k);
+        const float s = (float)(ow.amp * std::sin(6.0 * (double)ow.rest[3 * k + 1] + (double)frame));
+        for (int r = 0; r < 3; ++r) out[3 * k + r] = ow.rest[3 * k + r] + s * n[r];
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -183,6 +224,7 @@ int main(int argc, char** argv) {
     double truck[3] = {0.0, 0.0, 0.0};   // --truck: the camera's world-space shift per frame
     bool temporal_path = false;          // --temporal-path: accumulate on mirror-path guides
     std::vector<ObjectMotion> motions;   // --move / --spin, one entry per object named
+    std::vector<ObjectWave> waves;       // --wave, one entry per option
     auto motion_of = [&](uint32_t object) -> ObjectMotion& {
         for (auto& om : motions)
             if (om.object == object) return om;
@@ -236,6 +278,11 @@ int main(int argc, char** argv) {
             ObjectMotion& om = motion_of((uint32_t)std::stoul(next()));
             om.spin = std::stod(next());
         }
+        else if (a == "--wave") {
+            waves.emplace_back();
+            waves.back().object = (uint32_t)std::stoul(next());
+            waves.back().amp = std::stod(next());
+        }
         else if (a == "--denoise") {
             denoise = true;   // an optional iteration count follows
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn_iterations = std::stoi(argv[++i]);
@@ -256,6 +303,18 @@ int main(int argc, char** argv) {
     }
     if (!motions.empty() && temporal_path) {   // tpt_temporal_path does not follow moving objects
         std::fprintf(stderr, "--move and --spin cannot be combined with --temporal-path\n");
+        return 2;
+    }
+    if (!waves.empty() && progressive) {   // as --move
+        std::fprintf(stderr, "--wave cannot be combined with --progressive\n");
+        return 2;
+    }
+    if (!waves.empty() && (!temporal || frames < 2)) {
+        std::fprintf(stderr, "--wave needs --frames F (F > 1) and --temporal\n");
+        return 2;
+    }
+    if (!waves.empty() && temporal_path) {   // tpt_temporal_path does not follow deforming meshes
+        std::fprintf(stderr, "--wave cannot be combined with --temporal-path\n");
         return 2;
     }
     if (temporal && progressive) {   // progressive is already the exact accumulation of an unmoving camera
@@ -289,6 +348,10 @@ int main(int argc, char** argv) {
             if (om.object >= scene.desc().n_objects) throw std::runtime_error("--move / --spin: no such object");
             world_box_centre(scene.desc(), om.object, om.centre);
         }
+        for (auto& ow : waves) {
+            if (ow.object >= scene.desc().n_objects) throw std::runtime_error("--wave: no such object");
+            wave_range(scene.desc(), ow);
+        }
         tpt::Frame f;
         f.width = W;
         f.height = H;
@@ -312,6 +375,11 @@ int main(int argc, char** argv) {
                     moved_matrix(om, scene.desc().vert_trans + 16 * (size_t)om.object, i, m);
                     if (i > 0) d.setTransforms(om.object, 1, m);
                 }
+                for (const auto& ow : waves) {
+                    std::vector<float> v;
+                    waved_vertices(scene.desc(), ow, i, v);
+                    d.setVertices(ow.first, (uint32_t)ow.mine.size(), v.data());
+                }
                 if (!d.built()) d.build();
                 f.stats = pt.doTrace(d, cam, f.bgra.data(), spp, base + (uint64_t)i, depth, f.radiance.data());
                 if (temporal_path) {   // the path buffers with their terminal points, every frame
@@ -323,7 +391,10 @@ int main(int argc, char** argv) {
                     continue;
                 }
                 g = pt.renderAOV(d, cam);
-                if (motions.empty())
+                if (!waves.empty())
+                    pt.temporalDeform(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(),
+                                      nullptr, fb.data());
+                else if (motions.empty())
                     pt.temporal(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(), fb.data());
                 else
                     pt.temporalMotion(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(),
