@@ -249,8 +249,8 @@ tpt_status tpt_scene_set_build_threads(tpt_scene* scene, int32_t threads);
  * computed from vert_trans as the glTF loader computes it (the inverse transpose of the
  * linear part).  The vertices stay on the device; the matrices are uploaded on the scene's
  * stream, a pending tpt_scene_build_async is joined and superseded, and the scene is
- * unbuilt afterwards: call tpt_scene_build or tpt_scene_build_async before the next
- * render.  The rebuilt scene is the scene tpt_scene_create + tpt_scene_build make of a
+ * unbuilt afterwards: call tpt_scene_build, tpt_scene_build_async or tpt_scene_refit before
+ * the next render.  The rebuilt scene is the scene tpt_scene_create + tpt_scene_build make of a
  * desc with these matrices, bit for bit (world vertices, BVH, rendered frames).  A
  * progressive accumulation (TPT_FLAG_ACCUMULATE) does not survive it: its sums belong to
  * the scene as it was, so render the next frame without the flag.
@@ -263,16 +263,55 @@ tpt_status tpt_scene_set_transforms(tpt_scene* scene, uint32_t first_object, uin
  * the stored normals stay as they are.  Each pointer may be host or device memory (of the
  * scene's device), detected per pointer as tpt_scene_create does.  Topology (indices, lut),
  * materials and matrices are untouched.  A pending tpt_scene_build_async is joined and
- * superseded, and the scene is unbuilt afterwards: call tpt_scene_build or
- * tpt_scene_build_async before the next render.  The rebuilt scene is the scene
+ * superseded, and the scene is unbuilt afterwards: call tpt_scene_build,
+ * tpt_scene_build_async or tpt_scene_refit before the next render.  The rebuilt scene is the scene
  * tpt_scene_create + tpt_scene_build make of a desc holding these vertices, bit for bit
  * (tpt_scene_read_world, tpt_scene_read_bvh, rendered frames).  A progressive accumulation
- * does not survive it, as for tpt_scene_set_transforms.  The build is a full rebuild, not a
- * refit (DESIGN.md section 5 "Deforming meshes").
+ * does not survive it, as for tpt_scene_set_transforms.  tpt_scene_build is a full rebuild;
+ * tpt_scene_refit (below) keeps the trees' topology and recomputes their boxes on the device
+ * (DESIGN.md section 5 "Deforming meshes", "BVH refit").
  * TPT_ERR_INVALID_ARG (nothing changes): null scene or vertices, n_vertices == 0, a range
  * past the scene's vertex count, a device buffer of another device. */
 tpt_status tpt_scene_set_vertices(tpt_scene* scene, uint32_t first_vertex, uint32_t n_vertices,
                                   const float* vertices, const float* normals);
+/* What a tpt_scene_refit did, and the number a caller decides a rebuild by. */
+typedef struct tpt_refit_stats {
+    int32_t rebuilt;      /* 1: the call fell back to a full tpt_scene_build */
+    int32_t launches;     /* kernels the call launched (a fallback's build kernels are not counted) */
+    int32_t slivers;      /* sliver triangles found (trace.hip "Culling") */
+    float cull_eps;       /* the recomputed cull slack */
+    double ms;            /* device time of the call, by events on the scene's stream */
+    double cost;          /* the main 4-wide tree now: the summed surface areas of all child boxes of all
+                           * its nodes over the surface area of the union of the root's child boxes
+                           * (areas and sum in double, a fixed order: the same value every run) */
+    double cost_built;    /* the same quantity as the last full build left it */
+} tpt_refit_stats;
+/* In place of tpt_scene_build after tpt_scene_set_vertices and / or tpt_scene_set_transforms:
+ * leaves the scene built, with no host tree work.  Kept from the last full build: the triangle
+ * order (the sorted Morton keys tpt_scene_read_bvh returns are then stale), the LBVH topology,
+ * the topology, links and emitter bits of both 4-wide SAH trees, the stack depth.  Recomputed
+ * on the device, on the scene's stream: the world vertices and normals (bit for bit a
+ * rebuild's), the leaf boxes, the triangle and shading records, every LBVH node box, every
+ * child box of every 4-wide node (a leaf child: the exact leaf box; an inner child: the exact
+ * min/max union of that node's child boxes), one kernel launch per tree level, deepest
+ * first.  Recomputed on the host from small read-backs: the boxes' finiteness, the cull slack,
+ * the sliver list (only when there are slivers do the leaf boxes come back), the emitter
+ * boxes.  A progressive accumulation does not survive it.
+ * A full tpt_scene_build runs inside the call (stats->rebuilt = 1) when the scene holds no
+ * complete build (never built, or an asynchronous build superseded by a tpt_scene_set_*
+ * before its trees were uploaded), when it was built without the SAH tree (one triangle, or
+ * non-finite boxes), or when the refit meets a non-finite world vertex or box.  A pending
+ * asynchronous build that was not superseded is finished first.
+ * Against a rebuild: where two different triangles are hit at a bit-equal closest t, the
+ * kernel's tie rule picks the larger sorted position, and after a refit the positions are
+ * those of the last full build, so such a ray may return the other triangle.  Every other
+ * ray returns the same hit bit for bit (the hit depends only on the leaves' exact boxes and
+ * positions, wide_bvh.cpp).  The trees' quality degrades as the deformation grows: the
+ * library takes no decision from stats->cost / cost_built, the caller does (DESIGN.md
+ * section 5 "BVH refit" has a rule of thumb).  Not provided: partial (dirty-subtree) refits,
+ * topology changes, re-sorting.
+ * stats: nullable.  TPT_ERR_INVALID_ARG: null scene. */
+tpt_status tpt_scene_refit(tpt_scene* scene, tpt_refit_stats* stats);
 void tpt_scene_destroy(tpt_scene* scene);
 
 /* Equirect environment, RGBA8, row 0 = bottom (FreeImage order), already in
@@ -708,6 +747,13 @@ tpt_status tpt_denoise_svgf(tpt_scene* scene, int32_t width, int32_t height, con
 /* Introspection for tests: copy back the built BVH in the reference node
  * layout (bvh.cuh:52-58, 36 B/node, 2F-1 nodes) and the sorted Morton keys. */
 tpt_status tpt_scene_read_bvh(tpt_scene* scene, void* nodes36, int64_t* keys);
+/* The same for the resident 4-wide traversal trees, as uploaded or refitted: *n_main nodes of
+ * the main tree, then *n_emit of the emissive-triangle tree (its links count from *n_main),
+ * 32 floats each (inner4 layout: child k's box in floats 6k..6k+5, the four links' bits in
+ * floats 24..27).  nodes: nullable; written only when cap >= *n_main + *n_emit.  After
+ * tpt_scene_refit the nodes36 boxes and these are the refitted ones; the keys are the last
+ * full build's. */
+tpt_status tpt_scene_read_wide(tpt_scene* scene, float* nodes, int32_t cap, int32_t* n_main, int32_t* n_emit);
 /* World-space vertices / normals after tpt_scene_build (n_vertices*3 each). */
 tpt_status tpt_scene_read_world(tpt_scene* scene, float* wverts, float* wnorms);
 /* Per-pixel RNG states after setupRandSeed for the first n pixels: 6 words
@@ -769,6 +815,14 @@ tpt_status tpt_debug_step_latency(tpt_scene* scene, uint32_t n, const float* ori
  * not written), or -1.  threads as in tpt_scene_set_build_threads. */
 int32_t tpt_wide_tree_build(int32_t n, const float* leaf_box, const uint32_t* leaf_emit, float* nodes,
                             int32_t cap, int32_t* stack_need, int32_t threads);
+/* Host-only: the levels of such a tree, which is numbered breadth-first (n_nodes nodes of 32
+ * floats; id_base: the id its links give its first node, 0 for tpt_wide_tree_build's output).
+ * Level l is the nodes [level_begin[l], level_begin[l + 1]) counted from the tree's first;
+ * every inner child of a level-l node lies in level l + 1.  tpt_scene_refit launches one
+ * kernel per level.  Returns the level count L and writes L + 1 entries when cap >= L + 1;
+ * -1: null nodes, n_nodes <= 0, or nodes that are not numbered level by level. */
+int32_t tpt_wide_tree_levels(const float* nodes, int32_t n_nodes, int32_t id_base, int32_t* level_begin,
+                             int32_t cap);
 
 /* Host-only: for each of n_objects the way from this frame's world back into the previous
  * one's, from the objects' local-to-world matrices then (prev16) and now (cur16; 16 floats

@@ -99,6 +99,14 @@ public:
         built_ = false;
         return *this;
     }
+    // In place of build() after setVertices / setTransforms (tpt_scene_refit): the last full
+    // build's topology with every box recomputed on the device; a full build where it must be.
+    // stats->cost / cost_built is the caller's signal for a rebuild.
+    DeviceScene& refit(tpt_refit_stats* stats = nullptr) {
+        check(tpt_scene_refit(scene_.get(), stats));
+        built_ = true;
+        return *this;
+    }
     bool built() const { return built_; }
     tpt_scene* handle() const { return scene_.get(); }
     uint32_t nFaces() const { return n_faces_; }

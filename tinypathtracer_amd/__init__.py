@@ -298,6 +298,27 @@ class DeviceScene:
         self.built = False
         return self
 
+    def refit(self) -> dict:
+        """In place of build() after set_vertices / set_transforms (tpt_scene_refit): the trees'
+        topology and the triangle order of the last full build stay, every box is recomputed on
+        the device.  Falls back to a full build where it must (never built, no SAH tree, a
+        non-finite vertex).  Returns tpt_refit_stats as a dict: rebuilt, launches, slivers,
+        cull_eps, ms, cost, cost_built -- cost / cost_built is the caller's signal for a rebuild."""
+        st = _lib.RefitStats()
+        check(lib().tpt_scene_refit(self.handle, C.byref(st)))
+        self.built = True
+        return st.as_dict()
+
+    def read_wide(self):
+        """The resident 4-wide traversal trees (tpt_scene_read_wide): (main [n_main, 32],
+        emissive [n_emit, 32]) float32, as uploaded or refitted; links are the int32 bits of
+        columns 24..27."""
+        nm, ne = C.c_int32(0), C.c_int32(0)
+        check(lib().tpt_scene_read_wide(self.handle, None, 0, C.byref(nm), C.byref(ne)))
+        nodes = np.zeros((nm.value + ne.value, 32), np.float32)
+        check(lib().tpt_scene_read_wide(self.handle, _ptr(nodes), len(nodes), C.byref(nm), C.byref(ne)))
+        return nodes[:nm.value], nodes[nm.value:]
+
     def read_bvh(self):
         nf = self.scene.n_faces
         nodes = np.zeros(2 * nf - 1, NODE_DTYPE)

@@ -98,6 +98,14 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RefitStats(C.Structure):
+    _fields_ = [("rebuilt", C.c_int32), ("launches", C.c_int32), ("slivers", C.c_int32), ("cull_eps", C.c_float),
+                ("ms", C.c_double), ("cost", C.c_double), ("cost_built", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("target", C.c_float), ("flags", C.c_int32)]
 
@@ -166,6 +174,10 @@ SIGNATURES = [
     ("tpt_scene_set_build_threads", C.c_int, [C.c_void_p, C.c_int32]),
     ("tpt_scene_set_transforms", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("tpt_scene_set_vertices", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("tpt_scene_refit", C.c_int, [C.c_void_p, C.POINTER(RefitStats)]),
+    ("tpt_scene_read_wide", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32)]),
+    ("tpt_wide_tree_levels", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     ("tpt_scene_destroy", None, [C.c_void_p]),
     ("tpt_env_create", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
     ("tpt_env_destroy", None, [C.c_void_p]),
@@ -272,11 +284,12 @@ def lib():
                               f"`make -C {HERE}` or __graft_entry__.build()")
         L = C.CDLL(LIB_PATH)
         # TPT_LIB (tools/gpu_abn.sh A/B of an older build) may name a library that
-        # predates the newest debug entry points or tpt_render_adaptive (an A/B against the
-        # build before it); the product library must export all
+        # predates the newest debug entry points, tpt_render_adaptive or the refit entry points
+        # (an A/B against the build before them); the product library must export all
         older = bool(os.environ.get("TPT_LIB"))
+        _NEWEST = ("tpt_render_adaptive", "tpt_scene_refit", "tpt_scene_read_wide", "tpt_wide_tree_levels")
         for name, res, args in SIGNATURES:
-            if older and (name.startswith("tpt_debug_") or name == "tpt_render_adaptive") and not hasattr(L, name):
+            if older and (name.startswith("tpt_debug_") or name in _NEWEST) and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res

@@ -206,6 +206,26 @@ hipError_t launch_build(BuildBuffers& b, hipStream_t s);
 // |coordinate| of any vertex as a double (positive doubles order as integers).
 hipError_t launch_sliver_scan(const float4* tri, int32_t n, uint8_t* sliver, unsigned long long* coord_max,
                               hipStream_t s);
+// Refit (tpt_scene_refit): what launch_build left resident -- fids_sorted, children, parent, the
+// node depths in `flags`, emit, the links of inner4 -- stays; wverts / wnorms (zeroed by the
+// caller), leaf_box, node_box, inner, the boxes of inner4, tri, shade and nodes36 are
+// recomputed from vertices and the matrices.  max_depth[1] is nonzero afterwards when a face
+// has a non-finite world vertex or an inner-node child box is not finite.
+struct RefitPlan {
+    uint32_t tree_depth;                 // the LBVH's deepest leaf (BuildBuffers::out_max_depth of the build)
+    // Level l of a 4-wide tree is the inner4 ids [lv[l], lv[l + 1]) (tpt_wide_tree_levels, plus
+    // the tree's first id); n_lv levels.  The emissive tree may have none (n_lv_emit = 0).
+    const int32_t* lv_main;
+    int32_t n_lv_main;
+    const int32_t* lv_emit;
+    int32_t n_lv_emit;
+};
+// *launches is advanced by the kernels launched
+hipError_t launch_refit(BuildBuffers& b, const RefitPlan& p, int32_t* launches, hipStream_t s);
+// out[0] = the sum over the main tree's n_main nodes of their child boxes' areas (double, a
+// fixed order), out[1] = the area of the union of the root's child boxes; terms: n_main doubles
+hipError_t launch_wide_cost(const float4* inner4, int32_t n_main, double* terms, double* out, int32_t* launches,
+                            hipStream_t s);
 
 // wavefront.hip: the wavefront / ray-queue variant (TPT_FLAG_WAVEFRONT).  The
 // queues are split into kWfShards shards (one per XCD) of shard_cap entries.  Slots

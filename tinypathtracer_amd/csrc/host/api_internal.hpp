@@ -346,6 +346,20 @@ struct tpt_scene {
     std::unique_ptr<HostTrees> trees;       // the host half of the builds
     bool pending = false;                   // tpt_scene_build_async's host half runs / is not uploaded yet
     uint32_t pending_need = 0;              // its stack bound before the trees
+    // tpt_scene_refit: whether the device holds a complete full build (set where a build
+    // completes, cleared where one starts; tpt_scene_set_* leave it), the level ranges of the two
+    // 4-wide trees as inner4 ids (lv[l] .. lv[l + 1]; empty: none, or not level-ordered), the
+    // tree cost as the last full build left it (measured by the first refit after it) and the
+    // cost kernels' buffers
+    bool resident = false;
+    int32_t n_emit4 = 0;                    // nodes of the emissive-triangle tree (from emit_root)
+    std::vector<int32_t> lv_main, lv_emit;
+    bool cost_built_valid = false;
+    double cost_built = 0.0;
+    DevBuf<double> cost_terms, cost_out;    // per main-tree node; (sum, root area) as built and as refitted
+    HostPinned<double> h_cost;
+    HostPinned<float> h_eroot;              // the emissive tree's root node, read back for emit_box
+    HostPinned<uint32_t> h_nonfinite;
     // inputs
     DevBuf<uint32_t> indices;
     DevBuf<float> vertices, normals, vert_trans, normal_trans;

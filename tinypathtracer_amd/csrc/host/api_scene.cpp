@@ -1,5 +1,6 @@
 // api_scene.cpp -- the scene and env handles of the C-ABI: tpt_scene_create, the
-// (asynchronous) build with its host trees, tpt_env_create / tpt_env_load.
+// (asynchronous) build with its host trees, the refit that keeps them
+// (tpt_scene_refit), tpt_env_create / tpt_env_load.
 //
 // Replaces the reference's Scene::copySceneToDevice (src/mesh.cu:309-397).
 #include <chrono>
@@ -194,6 +195,8 @@ int emitter_boxes(const float* root, float* out) {
 // Uploads a finished HostTrees job and completes the scene (the stack bound).
 tpt_status upload_host_trees(tpt_scene* s, HostTrees& j, uint32_t* wide_need) {
     if (j.st != TPT_OK) return fail(j.st, j.msg);
+    s->lv_main.clear();
+    s->lv_emit.clear();
     if (j.main_ok()) {
         HIP_OR_FAIL(hipMemcpyAsync(s->inner4.p, j.w4.data(), j.w4.size() * sizeof(float), hipMemcpyHostToDevice,
                                    s->stream));
@@ -205,8 +208,20 @@ tpt_status upload_host_trees(tpt_scene* s, HostTrees& j, uint32_t* wide_need) {
         HIP_OR_FAIL(hipMemcpyAsync(s->inner4.p + 8 * (size_t)s->n4, j.e4.data(), j.e4.size() * sizeof(float),
                                    hipMemcpyHostToDevice, s->stream));
         s->emit_root = s->n4;
+        s->n_emit4 = j.ne4;
         s->n_emit_box = emitter_boxes(j.e4.data(), s->emit_box);
         *wide_need = std::max(*wide_need, (uint32_t)j.eneed);
+    }
+    // a refit's launches (tpt_scene_refit), while the copies run: one level of a tree each.
+    // Trees that are not level-ordered leave lv_main empty, and a refit rebuilds.
+    try {
+        if (j.main_ok() && tpt::wide_tree_levels(j.w4.data(), j.n4, 0, s->lv_main) < 1) s->lv_main.clear();
+        if (j.emit_ok() && !s->lv_main.empty()) {
+            if (tpt::wide_tree_levels(j.e4.data(), j.ne4, s->emit_root, s->lv_emit) < 1) s->lv_main.clear();
+            for (int32_t& v : s->lv_emit) v += s->emit_root;
+        }
+    } catch (const std::bad_alloc&) {
+        s->lv_main.clear();
     }
     HIP_OR_FAIL(hipStreamSynchronize(s->stream));   // (the host buffers are freed after this)
     return TPT_OK;
@@ -219,48 +234,97 @@ tpt_status finish_stack(tpt_scene* s, uint32_t wide_need) {
     s->stack_depth = (int32_t)std::max<uint32_t>(std::max<uint32_t>(s->tree_depth + 2, wide_need), 2);
     if (s->stack_depth > 160) return fail(TPT_ERR_INVALID_ARG, "BVH deeper than the LDS stack supports");
     s->built = true;
+    s->resident = true;
     return TPT_OK;
 }
 
-tpt_status scene_build(tpt_scene* s, bool async) {
-    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
-    if (s->trees) s->trees->join();   // a previous asynchronous build still running: its trees are superseded
-    s->pending = false;
-    s->built = false;
-    DeviceGuard g(s->device);
-    const size_t n = (size_t)s->n_faces, nn = 2 * n - 1, nv = (size_t)s->n_vertices;
-    size_t sort_bytes = 0;
-    HIP_OR_FAIL(tpt::build_sort_tmp_bytes((int32_t)n, &sort_bytes));
-    HIP_OR_FAIL(s->wverts.alloc(3 * nv));
-    HIP_OR_FAIL(s->wnorms.alloc(3 * nv));
-    HIP_OR_FAIL(hipMemsetAsync(s->wverts.p, 0, 3 * nv * sizeof(float), s->stream));
-    HIP_OR_FAIL(hipMemsetAsync(s->wnorms.p, 0, 3 * nv * sizeof(float), s->stream));
-    HIP_OR_FAIL(s->keys.alloc(n));
-    HIP_OR_FAIL(s->keys_sorted.alloc(n));
-    HIP_OR_FAIL(s->fids.alloc(n));
-    HIP_OR_FAIL(s->fids_sorted.alloc(n));
-    HIP_OR_FAIL(s->leaf_box.alloc(6 * n));
-    HIP_OR_FAIL(s->children.alloc(std::max<size_t>(n - 1, 1)));
-    HIP_OR_FAIL(s->parent.alloc(nn));
-    HIP_OR_FAIL(s->node_box.alloc(6 * nn));
-    HIP_OR_FAIL(s->flags.alloc(nn));
-    HIP_OR_FAIL(s->max_depth.alloc(3));
-    HIP_OR_FAIL(s->bfs_keys.alloc(std::max<size_t>(n - 1, 1)));
-    HIP_OR_FAIL(s->bfs_keys_sorted.alloc(std::max<size_t>(n - 1, 1)));
-    HIP_OR_FAIL(s->bfs_ids.alloc(std::max<size_t>(n - 1, 1)));
-    HIP_OR_FAIL(s->bfs_ids_sorted.alloc(std::max<size_t>(n - 1, 1)));
-    HIP_OR_FAIL(s->bfs_newid.alloc(std::max<size_t>(n - 1, 1)));
-    HIP_OR_FAIL(s->emit.alloc(nn));
-    HIP_OR_FAIL(s->sort_tmp.alloc(std::max<size_t>(sort_bytes, 16)));
-    HIP_OR_FAIL(s->inner.alloc(4 * std::max<size_t>(n - 1, 1)));
-    HIP_OR_FAIL(s->inner4.alloc(8 * std::max<size_t>(n - 1, 1)));
-    HIP_OR_FAIL(s->tri.alloc(tpt::tri_float4s(n)));
-    HIP_OR_FAIL(s->shade.alloc(3 * n));
-    HIP_OR_FAIL(s->nodes36.alloc(36 * nn));
-    HIP_OR_FAIL(hipMemsetAsync(s->parent.p, 0, nn * sizeof(uint32_t), s->stream));
-    PhaseClock clk(std::getenv("TPT_BUILD_TIMING") != nullptr);
+// The traversal-exactness inputs both scene_build and tpt_scene_refit derive from k_sliver_scan
+// (trace.hip "Culling").  The culls' absolute position slack: 4 ulps of the largest world coordinate.
+float cull_eps_of(double max_coord) {
+    if (!(std::isfinite(max_coord) && max_coord > 0.0)) return 0.0f;
+    int ex = 0;
+    (void)std::frexp(max_coord, &ex);             // max_coord < 2^ex
+    return (float)std::ldexp(4.0, ex - 24);       // 4 ulps of a float below 2^ex
+}
 
-    tpt::BuildBuffers b{};
+// The sliver list and its groups from the flagged positions `sl` (reordered), the leaf boxes and
+// the emitter flags by position; uploads them and sets n_sliver_groups.
+tpt_status upload_slivers(tpt_scene* s, std::vector<int>& sl, const float* lbox, const uint32_t* lemit) {
+    s->n_sliver_groups = 0;
+    if (sl.empty()) return TPT_OK;
+    // groups 1..: split the list at the median of the longest centroid axis
+    // while a group holds more than 8 slivers and there are < 8 groups;
+    // group 0 is the union of all (tested first by every ray)
+    std::vector<std::pair<int, int>> grp{{0, (int)sl.size()}};
+    auto cen = [&](int p, int k) { return lbox[6 * p + k] + lbox[6 * p + 3 + k]; };
+    for (bool split = true; split && grp.size() < 8;) {
+        split = false;
+        size_t big = 0;
+        for (size_t g = 1; g < grp.size(); ++g)
+            if (grp[g].second - grp[g].first > grp[big].second - grp[big].first) big = g;
+        const int b0 = grp[big].first, b1 = grp[big].second;
+        if (b1 - b0 <= 8) break;
+        float lo[3] = {kInfF, kInfF, kInfF}, hi[3] = {-kInfF, -kInfF, -kInfF};
+        for (int i = b0; i < b1; ++i)
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = std::min(lo[k], cen(sl[i], k));
+                hi[k] = std::max(hi[k], cen(sl[i], k));
+            }
+        int ax = 0;
+        for (int k = 1; k < 3; ++k)
+            if (hi[k] - lo[k] > hi[ax] - lo[ax]) ax = k;
+        const int mid = (b0 + b1) / 2;
+        std::nth_element(sl.begin() + b0, sl.begin() + mid, sl.begin() + b1,
+                         [&](int x, int y) { return cen(x, ax) < cen(y, ax); });
+        grp[big] = {b0, mid};
+        grp.push_back({mid, b1});
+        split = true;
+    }
+    grp.insert(grp.begin(), {0, (int)sl.size()});   // group 0: the union
+    std::vector<float4> gb(2 * grp.size());
+    std::vector<float4> lst(2 * sl.size());   // exact leaf box, position | emissive << 30
+    for (size_t i = 0; i < sl.size(); ++i) {
+        const int32_t e = sl[i] | (lemit[sl[i]] ? (1 << 30) : 0);
+        float fe;
+        std::memcpy(&fe, &e, 4);
+        const float* b = &lbox[6 * sl[i]];
+        lst[2 * i] = make_float4(b[0], b[1], b[2], fe);
+        lst[2 * i + 1] = make_float4(b[3], b[4], b[5], 0.0f);
+    }
+    for (size_t g = 0; g < grp.size(); ++g) {
+        float lo[3] = {kInfF, kInfF, kInfF}, hi[3] = {-kInfF, -kInfF, -kInfF};
+        for (int i = grp[g].first; i < grp[g].second; ++i)
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = std::min(lo[k], lbox[6 * sl[i] + k]);
+                hi[k] = std::max(hi[k], lbox[6 * sl[i] + 3 + k]);
+            }
+        int32_t first = grp[g].first, count = grp[g].second - grp[g].first;
+        float ff, fc;
+        std::memcpy(&ff, &first, 4);
+        std::memcpy(&fc, &count, 4);
+        gb[2 * g] = make_float4(lo[0], lo[1], lo[2], ff);
+        gb[2 * g + 1] = make_float4(hi[0], hi[1], hi[2], fc);
+    }
+    HIP_OR_FAIL(s->sliver_groups.upload(gb.data(), gb.size(), s->stream));
+    HIP_OR_FAIL(s->sliver_list.upload(lst.data(), lst.size(), s->stream));
+    HIP_OR_FAIL(hipStreamSynchronize(s->stream));   // (gb and lst are freed below)
+    s->n_sliver_groups = (int32_t)grp.size();
+    return TPT_OK;
+}
+
+// The positions k_sliver_scan flagged and the largest coordinate's bits behind them (n flags,
+// then the 8 bytes of coord_max), as both callers read them back
+void read_sliver_scan(const uint8_t* lsliver, size_t n, std::vector<int>& sl, double* max_coord) {
+    sl.clear();
+    for (size_t p = 0; p < n; ++p)
+        if (lsliver[p]) sl.push_back((int)p);
+    unsigned long long mbits = 0;
+    std::memcpy(&mbits, lsliver + n, sizeof mbits);
+    std::memcpy(max_coord, &mbits, sizeof *max_coord);
+}
+
+// The scene's buffers as the build and refit kernels take them
+void fill_build_buffers(tpt_scene* s, size_t sort_bytes, tpt::BuildBuffers& b) {
     b.n_faces = s->n_faces;
     b.n_vertices = s->n_vertices;
     b.n_objects = s->n_objects;
@@ -297,6 +361,50 @@ tpt_status scene_build(tpt_scene* s, bool async) {
     b.tri = s->tri.p;
     b.shade = s->shade.p;
     b.nodes36 = s->nodes36.p;
+}
+
+tpt_status scene_build(tpt_scene* s, bool async) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (s->trees) s->trees->join();   // a previous asynchronous build still running: its trees are superseded
+    s->pending = false;
+    s->built = false;
+    s->resident = false;           // (finish_stack sets it again)
+    s->cost_built_valid = false;
+    DeviceGuard g(s->device);
+    const size_t n = (size_t)s->n_faces, nn = 2 * n - 1, nv = (size_t)s->n_vertices;
+    size_t sort_bytes = 0;
+    HIP_OR_FAIL(tpt::build_sort_tmp_bytes((int32_t)n, &sort_bytes));
+    HIP_OR_FAIL(s->wverts.alloc(3 * nv));
+    HIP_OR_FAIL(s->wnorms.alloc(3 * nv));
+    HIP_OR_FAIL(hipMemsetAsync(s->wverts.p, 0, 3 * nv * sizeof(float), s->stream));
+    HIP_OR_FAIL(hipMemsetAsync(s->wnorms.p, 0, 3 * nv * sizeof(float), s->stream));
+    HIP_OR_FAIL(s->keys.alloc(n));
+    HIP_OR_FAIL(s->keys_sorted.alloc(n));
+    HIP_OR_FAIL(s->fids.alloc(n));
+    HIP_OR_FAIL(s->fids_sorted.alloc(n));
+    HIP_OR_FAIL(s->leaf_box.alloc(6 * n));
+    HIP_OR_FAIL(s->children.alloc(std::max<size_t>(n - 1, 1)));
+    HIP_OR_FAIL(s->parent.alloc(nn));
+    HIP_OR_FAIL(s->node_box.alloc(6 * nn));
+    HIP_OR_FAIL(s->flags.alloc(nn));
+    HIP_OR_FAIL(s->max_depth.alloc(3));
+    HIP_OR_FAIL(s->bfs_keys.alloc(std::max<size_t>(n - 1, 1)));
+    HIP_OR_FAIL(s->bfs_keys_sorted.alloc(std::max<size_t>(n - 1, 1)));
+    HIP_OR_FAIL(s->bfs_ids.alloc(std::max<size_t>(n - 1, 1)));
+    HIP_OR_FAIL(s->bfs_ids_sorted.alloc(std::max<size_t>(n - 1, 1)));
+    HIP_OR_FAIL(s->bfs_newid.alloc(std::max<size_t>(n - 1, 1)));
+    HIP_OR_FAIL(s->emit.alloc(nn));
+    HIP_OR_FAIL(s->sort_tmp.alloc(std::max<size_t>(sort_bytes, 16)));
+    HIP_OR_FAIL(s->inner.alloc(4 * std::max<size_t>(n - 1, 1)));
+    HIP_OR_FAIL(s->inner4.alloc(8 * std::max<size_t>(n - 1, 1)));
+    HIP_OR_FAIL(s->tri.alloc(tpt::tri_float4s(n)));
+    HIP_OR_FAIL(s->shade.alloc(3 * n));
+    HIP_OR_FAIL(s->nodes36.alloc(36 * nn));
+    HIP_OR_FAIL(hipMemsetAsync(s->parent.p, 0, nn * sizeof(uint32_t), s->stream));
+    PhaseClock clk(std::getenv("TPT_BUILD_TIMING") != nullptr);
+
+    tpt::BuildBuffers b{};
+    fill_build_buffers(s, sort_bytes, b);
     {
         const hipError_t be = tpt::launch_build(b, s->stream);
         if (be != hipSuccess && b.out_max_depth >= tpt::kMaxLbvhDepth)
@@ -319,6 +427,7 @@ tpt_status scene_build(tpt_scene* s, bool async) {
     uint32_t wide_need = 3 * ((td + 1) / 2) + 1;
     s->wide_tree = 0;
     s->emit_root = -1;
+    s->n_emit4 = 0;
     s->n_emit_box = 0;
     s->slivers = 0;
     s->n_sliver_groups = 0;
@@ -352,78 +461,13 @@ tpt_status scene_build(tpt_scene* s, bool async) {
         HIP_OR_FAIL(hipStreamSynchronize(s->stream));
         clk.mark("readback");
         std::vector<int> sl;
-        for (size_t p = 0; p < n; ++p)
-            if (lsliver[p]) sl.push_back((int)p);
-        unsigned long long mbits = 0;
-        std::memcpy(&mbits, lsliver + n, sizeof mbits);
         double max_coord = 0.0;
-        std::memcpy(&max_coord, &mbits, sizeof max_coord);
+        read_sliver_scan(lsliver, n, sl, &max_coord);
         s->slivers = (int32_t)sl.size();
-        s->cull_eps = 0.0f;
-        if (std::isfinite(max_coord) && max_coord > 0.0) {
-            int ex = 0;
-            (void)std::frexp(max_coord, &ex);                     // max_coord < 2^ex
-            s->cull_eps = (float)std::ldexp(4.0, ex - 24);        // 4 ulps of a float below 2^ex
-        }
-        s->n_sliver_groups = 0;
-        if (!sl.empty()) {
-            // groups 1..: split the list at the median of the longest centroid axis
-            // while a group holds more than 8 slivers and there are < 8 groups;
-            // group 0 is the union of all (tested first by every ray)
-            std::vector<std::pair<int, int>> grp{{0, (int)sl.size()}};
-            auto cen = [&](int p, int k) { return lbox[6 * p + k] + lbox[6 * p + 3 + k]; };
-            for (bool split = true; split && grp.size() < 8;) {
-                split = false;
-                size_t big = 0;
-                for (size_t g = 1; g < grp.size(); ++g)
-                    if (grp[g].second - grp[g].first > grp[big].second - grp[big].first) big = g;
-                const int b0 = grp[big].first, b1 = grp[big].second;
-                if (b1 - b0 <= 8) break;
-                float lo[3] = {kInfF, kInfF, kInfF}, hi[3] = {-kInfF, -kInfF, -kInfF};
-                for (int i = b0; i < b1; ++i)
-                    for (int k = 0; k < 3; ++k) {
-                        lo[k] = std::min(lo[k], cen(sl[i], k));
-                        hi[k] = std::max(hi[k], cen(sl[i], k));
-                    }
-                int ax = 0;
-                for (int k = 1; k < 3; ++k)
-                    if (hi[k] - lo[k] > hi[ax] - lo[ax]) ax = k;
-                const int mid = (b0 + b1) / 2;
-                std::nth_element(sl.begin() + b0, sl.begin() + mid, sl.begin() + b1,
-                                 [&](int x, int y) { return cen(x, ax) < cen(y, ax); });
-                grp[big] = {b0, mid};
-                grp.push_back({mid, b1});
-                split = true;
-            }
-            grp.insert(grp.begin(), {0, (int)sl.size()});   // group 0: the union
-            std::vector<float4> gb(2 * grp.size());
-            std::vector<float4> lst(2 * sl.size());   // exact leaf box, position | emissive << 30
-            for (size_t i = 0; i < sl.size(); ++i) {
-                const int32_t e = sl[i] | (lemit[sl[i]] ? (1 << 30) : 0);
-                float fe;
-                std::memcpy(&fe, &e, 4);
-                const float* b = &lbox[6 * sl[i]];
-                lst[2 * i] = make_float4(b[0], b[1], b[2], fe);
-                lst[2 * i + 1] = make_float4(b[3], b[4], b[5], 0.0f);
-            }
-            for (size_t g = 0; g < grp.size(); ++g) {
-                float lo[3] = {kInfF, kInfF, kInfF}, hi[3] = {-kInfF, -kInfF, -kInfF};
-                for (int i = grp[g].first; i < grp[g].second; ++i)
-                    for (int k = 0; k < 3; ++k) {
-                        lo[k] = std::min(lo[k], lbox[6 * sl[i] + k]);
-                        hi[k] = std::max(hi[k], lbox[6 * sl[i] + 3 + k]);
-                    }
-                int32_t first = grp[g].first, count = grp[g].second - grp[g].first;
-                float ff, fc;
-                std::memcpy(&ff, &first, 4);
-                std::memcpy(&fc, &count, 4);
-                gb[2 * g] = make_float4(lo[0], lo[1], lo[2], ff);
-                gb[2 * g + 1] = make_float4(hi[0], hi[1], hi[2], fc);
-            }
-            HIP_OR_FAIL(s->sliver_groups.upload(gb.data(), gb.size(), s->stream));
-            HIP_OR_FAIL(s->sliver_list.upload(lst.data(), lst.size(), s->stream));
-            HIP_OR_FAIL(hipStreamSynchronize(s->stream));   // (gb and lst are freed below)
-            s->n_sliver_groups = (int32_t)grp.size();
+        s->cull_eps = cull_eps_of(max_coord);
+        {
+            const tpt_status ss = upload_slivers(s, sl, lbox, lemit);
+            if (ss != TPT_OK) return ss;
         }
         clk.mark("slivers");
         if (!s->trees) {
@@ -461,6 +505,127 @@ tpt_status scene_build(tpt_scene* s, bool async) {
         clk.mark("upload");
     }
     return finish_stack(s, wide_need);
+}
+
+// tpt_refit_stats.cost of the resident main tree into cost_out[2 * slot], [2 * slot + 1]
+tpt_status enqueue_cost(tpt_scene* s, int slot, int32_t* launches) {
+    HIP_OR_FAIL(s->cost_terms.alloc((size_t)s->n4));
+    HIP_OR_FAIL(s->cost_out.alloc(4));
+    HIP_OR_FAIL(s->h_cost.alloc(4));
+    HIP_OR_FAIL(tpt::launch_wide_cost(s->inner4.p, s->n4, s->cost_terms.p, s->cost_out.p + 2 * slot, launches, s->stream));
+    HIP_OR_FAIL(hipMemcpyAsync(s->h_cost.p + 2 * slot, s->cost_out.p + 2 * slot, 2 * sizeof(double),
+                               hipMemcpyDeviceToHost, s->stream));
+    return TPT_OK;
+}
+double cost_ratio(const double* c) { return c[1] > 0.0 ? c[0] / c[1] : 0.0; }
+
+// The end of every tpt_scene_refit: the stats, with the device time between the two events
+tpt_status refit_done(tpt_scene* s, tpt_refit_stats* st, tpt_refit_stats& r) {
+    HIP_OR_FAIL(hipEventRecord(s->ev[1], s->stream));
+    HIP_OR_FAIL(hipEventSynchronize(s->ev[1]));
+    float ms = 0.0f;
+    HIP_OR_FAIL(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+    r.ms = ms;
+    r.slivers = s->slivers;
+    r.cull_eps = s->cull_eps;
+    if (st) *st = r;
+    return TPT_OK;
+}
+
+// The fallback: a full build, and (with an SAH tree) its cost, which is then the built one
+tpt_status refit_rebuild(tpt_scene* s, tpt_refit_stats* st, tpt_refit_stats& r) {
+    r.rebuilt = 1;
+    const tpt_status bs = scene_build(s, false);
+    if (bs != TPT_OK) return bs;
+    if (s->wide_tree && s->n4 > 0) {
+        const tpt_status cs = enqueue_cost(s, 0, &r.launches);
+        if (cs != TPT_OK) return cs;
+        HIP_OR_FAIL(hipStreamSynchronize(s->stream));
+        s->cost_built = cost_ratio(s->h_cost.p);
+        s->cost_built_valid = true;
+        r.cost = r.cost_built = s->cost_built;
+    }
+    return refit_done(s, st, r);
+}
+
+tpt_status scene_refit(tpt_scene* s, tpt_refit_stats* st) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    tpt_refit_stats r{};
+    {   // a pending build that no tpt_scene_set_* superseded is finished first
+        const tpt_status ps = finish_pending(s);
+        if (ps != TPT_OK) return ps;
+    }
+    DeviceGuard g(s->device);
+    s->acc_valid = false;   // a progressive accumulation's sums belong to the scene as it was
+    HIP_OR_FAIL(hipEventRecord(s->ev[0], s->stream));
+    const size_t n = (size_t)s->n_faces, nv = (size_t)s->n_vertices;
+    if (!s->resident || !s->wide_tree || n < 2 || s->lv_main.empty() || s->n4 <= 0) return refit_rebuild(s, st, r);
+    s->built = false;
+    if (!s->cost_built_valid) {   // the trees are still the build's: their cost, before a box changes
+        const tpt_status cs = enqueue_cost(s, 0, &r.launches);
+        if (cs != TPT_OK) return cs;
+    }
+    tpt::BuildBuffers b{};
+    fill_build_buffers(s, 0, b);
+    HIP_OR_FAIL(hipMemsetAsync(s->wverts.p, 0, 3 * nv * sizeof(float), s->stream));
+    HIP_OR_FAIL(hipMemsetAsync(s->wnorms.p, 0, 3 * nv * sizeof(float), s->stream));
+    tpt::RefitPlan plan{};
+    plan.tree_depth = s->tree_depth;
+    plan.lv_main = s->lv_main.data();
+    plan.n_lv_main = (int32_t)s->lv_main.size() - 1;
+    plan.lv_emit = s->lv_emit.data();
+    plan.n_lv_emit = s->lv_emit.empty() ? 0 : (int32_t)s->lv_emit.size() - 1;
+    HIP_OR_FAIL(tpt::launch_refit(b, plan, &r.launches, s->stream));
+    HIP_OR_FAIL(hipMemsetAsync(s->coord_max.p, 0, sizeof(unsigned long long), s->stream));
+    HIP_OR_FAIL(tpt::launch_sliver_scan(s->tri.p, (int32_t)n, s->sliver_flags.p, s->coord_max.p, s->stream));
+    ++r.launches;
+    {
+        const tpt_status cs = enqueue_cost(s, 1, &r.launches);
+        if (cs != TPT_OK) return cs;
+    }
+    // the small read-backs, then the one synchronisation: the non-finite word, the sliver flags
+    // with the largest coordinate, the emissive tree's root node
+    HIP_OR_FAIL(s->h_nonfinite.alloc(1));
+    HIP_OR_FAIL(s->h_eroot.alloc(32));
+    uint8_t* const lsliver = s->h_sliver.p;   // (n + 8 bytes since the build)
+    HIP_OR_FAIL(hipMemcpyAsync(s->h_nonfinite.p, s->max_depth.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_OR_FAIL(hipMemcpyAsync(lsliver, s->sliver_flags.p, n, hipMemcpyDeviceToHost, s->stream));
+    HIP_OR_FAIL(hipMemcpyAsync(lsliver + n, s->coord_max.p, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                               s->stream));
+    if (s->emit_root >= 0)
+        HIP_OR_FAIL(hipMemcpyAsync(s->h_eroot.p, s->inner4.p + 8 * (size_t)s->emit_root, 32 * sizeof(float),
+                                   hipMemcpyDeviceToHost, s->stream));
+    HIP_OR_FAIL(hipStreamSynchronize(s->stream));
+    if (!s->cost_built_valid) {
+        s->cost_built = cost_ratio(s->h_cost.p);
+        s->cost_built_valid = true;
+    }
+    if (s->h_nonfinite.p[0] != 0) return refit_rebuild(s, st, r);   // a non-finite vertex or box: what a build makes of it
+    s->boxes_finite = 1;
+    std::vector<int> sl;
+    double max_coord = 0.0;
+    try {
+        read_sliver_scan(lsliver, n, sl, &max_coord);
+    } catch (const std::bad_alloc&) {
+        return fail(TPT_ERR_OOM, "refit: host allocation failed");
+    }
+    s->slivers = (int32_t)sl.size();
+    s->cull_eps = cull_eps_of(max_coord);
+    s->n_sliver_groups = 0;
+    if (!sl.empty()) {
+        // slivers are rare: only then do the leaf boxes come back (the emitter flags by position
+        // are the build's, still in the pinned staging)
+        HIP_OR_FAIL(hipMemcpyAsync(s->h_lbox.p, s->node_box.p + 6 * (n - 1), 6 * n * sizeof(float),
+                                   hipMemcpyDeviceToHost, s->stream));
+        HIP_OR_FAIL(hipStreamSynchronize(s->stream));
+        const tpt_status ss = upload_slivers(s, sl, s->h_lbox.p, s->h_lemit.p);
+        if (ss != TPT_OK) return ss;
+    }
+    if (s->emit_root >= 0) s->n_emit_box = emitter_boxes(s->h_eroot.p, s->emit_box);
+    r.cost = cost_ratio(s->h_cost.p + 2);
+    r.cost_built = s->cost_built;
+    s->built = true;
+    return refit_done(s, st, r);
 }
 
 }  // namespace
@@ -696,6 +861,27 @@ tpt_status tpt_scene_set_build_threads(tpt_scene* s, int32_t threads) {
 tpt_status tpt_scene_build(tpt_scene* s) { return scene_build(s, false); }
 
 tpt_status tpt_scene_build_async(tpt_scene* s) { return scene_build(s, true); }
+
+tpt_status tpt_scene_refit(tpt_scene* s, tpt_refit_stats* stats) { return scene_refit(s, stats); }
+
+tpt_status tpt_scene_read_wide(tpt_scene* s, float* nodes, int32_t cap, int32_t* n_main, int32_t* n_emit) {
+    if (!s || !s->built) return fail(TPT_ERR_INVALID_ARG, "scene not built");
+    {
+        const tpt_status bs = finish_pending(s);
+        if (bs != TPT_OK) return bs;
+    }
+    // (without the SAH tree inner4 holds the LBVH's even-depth view: n4 nodes, no emissive tree)
+    const int32_t nm = s->n4;
+    const int32_t ne = s->emit_root >= 0 ? s->n_emit4 : 0;
+    if (n_main) *n_main = nm;
+    if (n_emit) *n_emit = ne;
+    if (nodes && cap >= nm + ne && nm + ne > 0) {
+        DeviceGuard g(s->device);
+        HIP_OR_FAIL(hipStreamSynchronize(s->stream));
+        HIP_OR_FAIL(hipMemcpy(nodes, s->inner4.p, 32 * sizeof(float) * (size_t)(nm + ne), hipMemcpyDeviceToHost));
+    }
+    return TPT_OK;
+}
 
 void tpt_scene_destroy(tpt_scene* s) { delete s; }
 

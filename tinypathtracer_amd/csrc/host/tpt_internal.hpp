@@ -94,6 +94,8 @@ struct WideParams {
 int usable_cores();
 int build_wide_sah(const std::vector<int>& pos, const float* leaf_box, const uint32_t* leaf_emit, int leaf_base,
                    int id_base, HostFloats& out, int* stack_need, const WideParams& prm);
+// the level ranges of its breadth-first numbering (wide_bvh.cpp; tpt_wide_tree_levels)
+int wide_tree_levels(const float* nodes, int n_nodes, int id_base, std::vector<int32_t>& begin);
 
 }  // namespace tpt
 

@@ -964,7 +964,58 @@ int build_wide_sah(const std::vector<int>& pos, const float* leaf_box, const uin
     return total;
 }
 
+// The level ranges of a breadth-first 4-wide tree (build_wide_sah's output, `n_nodes` nodes of 32
+// floats whose first has the id `id_base`): level l is the nodes [begin[l], begin[l + 1]),
+// counted from the tree's first node, the root alone in level 0.  A child link whose id lies in
+// [id_base, id_base + n_nodes) is an inner child; every other id is a leaf.  Returns the level
+// count, or -1 when the nodes are not numbered that way: an inner child outside the next
+// level, a level that is not one contiguous run of ids, nodes no level reaches.  A refit
+// (build.hip launch_refit) runs one launch per level and relies on exactly this.
+int wide_tree_levels(const float* nodes, int n_nodes, int id_base, std::vector<int32_t>& begin) {
+    begin.clear();
+    if (!nodes || n_nodes <= 0 || id_base < 0) return -1;
+    begin.push_back(0);
+    int lo = 0, hi = 1;
+    while (true) {
+        begin.push_back(hi);
+        int64_t count = 0;
+        int cmin = n_nodes, cmax = -1;
+        for (int i = lo; i < hi; ++i) {
+            int32_t links[4];
+            std::memcpy(links, nodes + 32 * (size_t)i + 24, sizeof links);
+            for (int k = 0; k < 4; ++k) {
+                if (links[k] < 0) continue;
+                const int64_t rel = (int64_t)(links[k] & ((1 << 30) - 1)) - id_base;
+                if (rel < 0 || rel >= n_nodes) continue;   // a leaf
+                if (rel < hi) return -1;
+                cmin = std::min(cmin, (int)rel);
+                cmax = std::max(cmax, (int)rel);
+                ++count;
+            }
+        }
+        if (count == 0) break;
+        if (cmin != hi || (int64_t)cmax - cmin + 1 != count) return -1;
+        lo = hi;
+        hi = cmax + 1;
+    }
+    if (hi != n_nodes) return -1;
+    return (int)begin.size() - 1;
+}
+
 }  // namespace tpt
+
+extern "C" int32_t tpt_wide_tree_levels(const float* nodes, int32_t n_nodes, int32_t id_base, int32_t* level_begin,
+                                        int32_t cap) {
+    std::vector<int32_t> begin;
+    int lv = -1;
+    try {
+        lv = tpt::wide_tree_levels(nodes, n_nodes, id_base, begin);
+    } catch (const std::exception&) {
+        return -1;
+    }
+    if (lv > 0 && level_begin && lv + 1 <= cap) std::memcpy(level_begin, begin.data(), begin.size() * sizeof(int32_t));
+    return lv;
+}
 
 extern "C" int32_t tpt_wide_tree_build(int32_t n, const float* leaf_box, const uint32_t* leaf_emit, float* nodes,
                                        int32_t cap, int32_t* stack_need, int32_t threads) {

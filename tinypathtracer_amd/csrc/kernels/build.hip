@@ -81,15 +81,25 @@ __device__ __forceinline__ uint64_t expand_bits(uint64_t u) {   // bvh.cu:14-21
     return u;
 }
 
-__global__ void k_morton(BuildBuffers b) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= b.n_faces) return;
+// BBox(v0,v1,v2) of face f's world vertices (k_morton, and k_refit_leaves after a vertex update);
+// returns whether all nine coordinates are finite
+__device__ __forceinline__ bool face_box(const BuildBuffers& b, int f, V3& mn, V3& mx) {
     const float* w = b.wverts;
     const uint32_t i0 = b.indices[3 * f], i1 = b.indices[3 * f + 1], i2 = b.indices[3 * f + 2];
     const V3 p0 = v3(w[3 * i0], w[3 * i0 + 1], w[3 * i0 + 2]);
     const V3 p1 = v3(w[3 * i1], w[3 * i1 + 1], w[3 * i1 + 2]);
     const V3 p2 = v3(w[3 * i2], w[3 * i2 + 1], w[3 * i2 + 2]);
-    const V3 mn = vmin(vmin(p0, p1), p2), mx = vmax(vmax(p0, p1), p2);   // BBox(v0,v1,v2)
+    mn = vmin(vmin(p0, p1), p2);
+    mx = vmax(vmax(p0, p1), p2);
+    return isfinite(p0.x) && isfinite(p0.y) && isfinite(p0.z) && isfinite(p1.x) && isfinite(p1.y) &&
+           isfinite(p1.z) && isfinite(p2.x) && isfinite(p2.y) && isfinite(p2.z);
+}
+
+__global__ void k_morton(BuildBuffers b) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= b.n_faces) return;
+    V3 mn, mx;
+    face_box(b, f, mn, mx);
     const V3 c = 0.5f * (mn + mx);                                       // BBox::center
     b.keys[f] = expand_bits(float_to_21int(c.x)) | (expand_bits(float_to_21int(c.y)) << 1) |
                 (expand_bits(float_to_21int(c.z)) << 2);
@@ -452,6 +462,202 @@ hipError_t launch_build(BuildBuffers& b, hipStream_t s) {
     TPT_TRY(hipMemcpyAsync(&nonfinite, b.max_depth + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     TPT_TRY(hipStreamSynchronize(s));
     b.out_boxes_finite = nonfinite ? 0u : 1u;
+    return hipSuccess;
+}
+
+// ---- refit (tpt_scene_refit): the boxes of a kept topology from moved vertices -------------
+//
+// The triangle order, the LBVH links and depths, and the links of the 4-wide trees stay as the
+// last full build left them; every box is recomputed.  Kernel boundaries are the only ordering
+// between tree levels: one launch per LBVH depth (k_union_level, as the build) and one per level
+// of the 4-wide trees, deepest first.  No flag, counter or other hand-off inside a launch.
+
+// Leaf boxes from the world vertices, by face id (leaf_box) and at the kept sorted position
+// (node_box).  One lane per position.  A face with a non-finite vertex raises the build's
+// non-finite word (max_depth[1]): min/max can drop a NaN, the flag cannot.
+__global__ __launch_bounds__(256) void k_refit_leaves(BuildBuffers b) {
+    const int n = b.n_faces;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t fid = b.fids_sorted[j];
+    V3 mn, mx;
+    const bool fin = face_box(b, (int)fid, mn, mx);
+    float* lb = b.leaf_box + 6 * (size_t)fid;
+    float* nb = b.node_box + 6 * ((size_t)(n - 1) + j);
+    lb[0] = mn.x; lb[1] = mn.y; lb[2] = mn.z;
+    lb[3] = mx.x; lb[4] = mx.y; lb[5] = mx.z;
+    nb[0] = mn.x; nb[1] = mn.y; nb[2] = mn.z;
+    nb[3] = mx.x; nb[4] = mx.y; nb[5] = mx.z;
+    if (!fin) atomicOr(b.max_depth + 1, 1u);
+}
+
+constexpr int kLinkIdMask = (1 << 30) - 1;   // a child link without its emitter bit
+
+// The 24 box floats of a 4-wide node as six float4, and its links
+struct Wide4 {
+    float f[24];
+    int link[4];
+};
+__device__ __forceinline__ Wide4 wide4_load(const float4* __restrict__ q) {
+    Wide4 w;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const float4 v = q[k];
+        w.f[4 * k] = v.x; w.f[4 * k + 1] = v.y; w.f[4 * k + 2] = v.z; w.f[4 * k + 3] = v.w;
+    }
+    const float4 l = q[6];
+    w.link[0] = __float_as_int(l.x); w.link[1] = __float_as_int(l.y);
+    w.link[2] = __float_as_int(l.z); w.link[3] = __float_as_int(l.w);
+    return w;
+}
+
+// One level of both 4-wide trees: the nodes [a0, a1) of the main tree and [b0, b1) of the
+// emissive-triangle tree (either range may be empty), one lane per node.  A leaf child takes
+// the exact leaf box at its position (its link is the LBVH node id), an inner child the exact
+// min/max union of the child boxes of its node, which the previous launch wrote (it lies one
+// level deeper); an unused slot keeps the build's zero box.  Links and padding are not written.
+__global__ __launch_bounds__(256) void k_refit_wide_level(float4* __restrict__ inner4,
+                                                          const float* __restrict__ node_box, int nint, int a0, int a1,
+                                                          int b0, int b1) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int na = a1 - a0;
+    if (t >= na + (b1 - b0)) return;
+    const int node = t < na ? a0 + t : b0 + (t - na);
+    float4* q = inner4 + 8 * (size_t)node;
+    const float4 l = q[6];
+    const int link[4] = {__float_as_int(l.x), __float_as_int(l.y), __float_as_int(l.z), __float_as_int(l.w)};
+    float f[24];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float* o = f + 6 * k;
+        const int c = link[k] & kLinkIdMask;
+        if (link[k] < 0 || c > 2 * nint) {   // (no node has an id past the last leaf's, 2 (F - 1))
+#pragma unroll
+            for (int j = 0; j < 6; ++j) o[j] = 0.0f;
+            continue;
+        }
+        if (c >= nint) {
+            const float* bx = node_box + 6 * (size_t)c;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) o[j] = bx[j];
+        } else {
+            const Wide4 w = wide4_load(inner4 + 8 * (size_t)c);
+            o[0] = o[1] = o[2] = __builtin_inff();
+            o[3] = o[4] = o[5] = -__builtin_inff();
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                if (w.link[kk] < 0) continue;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    o[j] = fmn(o[j], w.f[6 * kk + j]);
+                    o[3 + j] = fmx(o[3 + j], w.f[6 * kk + 3 + j]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) q[k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
+}
+
+// Box::area of wide_bvh.cpp: in double, 0 for an inverted or NaN extent
+__device__ __forceinline__ double box_area_d(const float* b) {
+    const double dx = (double)b[3] - b[0], dy = (double)b[4] - b[1], dz = (double)b[5] - b[2];
+    if (!(dx >= 0.0) || !(dy >= 0.0) || !(dz >= 0.0)) return 0.0;
+    return 2.0 * (dx * dy + dy * dz + dz * dx);
+}
+
+// tpt_refit_stats.cost, first half: per main-tree node the summed areas of its child boxes, child
+// 0 first.  One lane per node.
+__global__ __launch_bounds__(256) void k_wide_cost_terms(const float4* __restrict__ inner4, int n_main,
+                                                         double* __restrict__ terms) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_main) return;
+    const Wide4 w = wide4_load(inner4 + 8 * (size_t)i);
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (w.link[k] >= 0) a += box_area_d(w.f + 6 * k);
+    terms[i] = a;
+}
+
+// Second half, one workgroup: lane t adds terms t, t + 256, ... in that order, then a pairwise
+// tree over the 256 partial sums -- a fixed order, so the same sum every run.  out[0] = the
+// sum, out[1] = the area of the union of the root's child boxes.
+__global__ __launch_bounds__(256) void k_wide_cost_sum(const double* __restrict__ terms, int n_main,
+                                                       const float4* __restrict__ inner4, double* __restrict__ out) {
+    __shared__ double part[256];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n_main; i += 256) a += terms[i];
+    part[threadIdx.x] = a;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const Wide4 r = wide4_load(inner4);
+        float u[6] = {__builtin_inff(), __builtin_inff(), __builtin_inff(),
+                      -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+        for (int k = 0; k < 4; ++k) {
+            if (r.link[k] < 0) continue;
+            for (int j = 0; j < 3; ++j) {
+                u[j] = fmn(u[j], r.f[6 * k + j]);
+                u[3 + j] = fmx(u[3 + j], r.f[6 * k + 3 + j]);
+            }
+        }
+        out[0] = part[0];
+        out[1] = box_area_d(u);
+    }
+}
+
+hipError_t launch_wide_cost(const float4* inner4, int32_t n_main, double* terms, double* out, int32_t* launches,
+                            hipStream_t s) {
+    if (n_main <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_wide_cost_terms, dim3((unsigned)((n_main + 255) / 256)), dim3(256), 0, s, inner4, n_main,
+                       terms);
+    TPT_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_wide_cost_sum, dim3(1), dim3(256), 0, s, (const double*)terms, n_main, inner4, out);
+    TPT_TRY(hipGetLastError());
+    *launches += 2;
+    return hipSuccess;
+}
+
+hipError_t launch_refit(BuildBuffers& b, const RefitPlan& p, int32_t* launches, hipStream_t s) {
+    const int n = b.n_faces;
+    const int nn = 2 * n - 1;
+    if (n < 2 || p.n_lv_main < 1) return hipErrorInvalidValue;
+    const dim3 blk(256);
+    auto grid = [](int m) { return dim3((unsigned)((m + 255) / 256)); };
+    const uint32_t* depth = b.flags;   // the build's node depths, still resident
+    TPT_TRY(hipMemsetAsync(b.max_depth + 1, 0, sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_transform, grid(n), blk, 0, s, b);
+    TPT_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_refit_leaves, grid(n), blk, 0, s, b);
+    TPT_TRY(hipGetLastError());
+    *launches += 2;
+    for (int level = (int)p.tree_depth - 1; level >= 0; --level) {   // as launch_build
+        hipLaunchKernelGGL(k_union_level, grid(n - 1), blk, 0, s, b, depth, (uint32_t)level);
+        TPT_TRY(hipGetLastError());
+        ++*launches;
+    }
+    hipLaunchKernelGGL(k_pack_inner, grid(n - 1), blk, 0, s, b);
+    TPT_TRY(hipGetLastError());
+    ++*launches;
+    for (int d = (p.n_lv_main > p.n_lv_emit ? p.n_lv_main : p.n_lv_emit) - 1; d >= 0; --d) {
+        const int a0 = d < p.n_lv_main ? p.lv_main[d] : 0, a1 = d < p.n_lv_main ? p.lv_main[d + 1] : 0;
+        const int b0 = d < p.n_lv_emit ? p.lv_emit[d] : 0, b1 = d < p.n_lv_emit ? p.lv_emit[d + 1] : 0;
+        hipLaunchKernelGGL(k_refit_wide_level, grid((a1 - a0) + (b1 - b0)), blk, 0, s, b.inner4,
+                           (const float*)b.node_box, n - 1, a0, a1, b0, b1);
+        TPT_TRY(hipGetLastError());
+        ++*launches;
+    }
+    hipLaunchKernelGGL(k_pack_leaf, grid(n), blk, 0, s, b);
+    TPT_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_pack_shade, grid(n), blk, 0, s, b);
+    TPT_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_pack_nodes36, grid(nn), blk, 0, s, b);
+    TPT_TRY(hipGetLastError());
+    *launches += 3;
     return hipSuccess;
 }
 

@@ -7,7 +7,7 @@
 //              [--seed S] [--env equirect.jpg|.ppm|--sky] [--out prefix] [--device i]
 //              [--frames F [--progressive]] [--aov] [--denoise [iterations]]
 //              [--temporal] [--yaw DEG] [--svgf [iterations]] [--aov-path [bounces]]
-//              [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP]
+//              [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP] [--refit]
 //              [--adaptive TARGET [--min-spp N] [--max-spp N]]
 // --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
 // <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
@@ -40,6 +40,9 @@
 // AMP sin(6 y_obj + frame) in frame `frame` (a deformation no matrix describes), under the same
 // conditions as --move: every frame sets the vertices (tpt_scene_set_vertices), rebuilds, renders,
 // and goes through tpt_temporal_deform, which follows the deformed mesh (and --move / --spin too).
+// --refit (with --move / --spin / --wave): the frames after the first refit the BVH
+// (tpt_scene_refit) instead of rebuilding it, and each prints its tree cost against the built
+// one and the refit's device time on stderr.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -99,7 +102,7 @@ const char* kUsage =
     "usage: %s scene.gltf [--width W] [--height H] [--spp N] [--depth D] [--seed S] "
     "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]] "
     "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]] "
-    "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP] [--truck DX DY DZ] "
+    "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP] [--refit] [--truck DX DY DZ] "
     "[--temporal-path [bounces]] [--adaptive TARGET [--min-spp N] [--max-spp N]]\n";
 
 // The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
@@ -225,6 +228,7 @@ int main(int argc, char** argv) {
     bool temporal_path = false;          // --temporal-path: accumulate on mirror-path guides
     std::vector<ObjectMotion> motions;   // --move / --spin, one entry per object named
     std::vector<ObjectWave> waves;       // --wave, one entry per option
+    bool refit = false;                  // --refit: frames after the first refit instead of rebuilding
     auto motion_of = [&](uint32_t object) -> ObjectMotion& {
         for (auto& om : motions)
             if (om.object == object) return om;
@@ -283,6 +287,7 @@ int main(int argc, char** argv) {
             waves.back().object = (uint32_t)std::stoul(next());
             waves.back().amp = std::stod(next());
         }
+        else if (a == "--refit") refit = true;
         else if (a == "--denoise") {
             denoise = true;   // an optional iteration count follows
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn_iterations = std::stoi(argv[++i]);
@@ -315,6 +320,10 @@ int main(int argc, char** argv) {
     }
     if (!waves.empty() && temporal_path) {   // tpt_temporal_path does not follow deforming meshes
         std::fprintf(stderr, "--wave cannot be combined with --temporal-path\n");
+        return 2;
+    }
+    if (refit && motions.empty() && waves.empty()) {   // nothing moves: nothing to refit
+        std::fprintf(stderr, "--refit needs --move, --spin or --wave\n");
         return 2;
     }
     if (temporal && progressive) {   // progressive is already the exact accumulation of an unmoving camera
@@ -379,6 +388,13 @@ int main(int argc, char** argv) {
                     std::vector<float> v;
                     waved_vertices(scene.desc(), ow, i, v);
                     d.setVertices(ow.first, (uint32_t)ow.mine.size(), v.data());
+                }
+                if (!d.built() && refit && i > 0) {
+                    tpt_refit_stats rs{};
+                    d.refit(&rs);
+                    std::fprintf(stderr, "frame %d: refit%s cost %.4f / built %.4f = %.4f, %.3f ms\n", i,
+                                 rs.rebuilt ? " (rebuilt)" : "", rs.cost, rs.cost_built,
+                                 rs.cost_built > 0.0 ? rs.cost / rs.cost_built : 0.0, rs.ms);
                 }
                 if (!d.built()) d.build();
                 f.stats = pt.doTrace(d, cam, f.bgra.data(), spp, base + (uint64_t)i, depth, f.radiance.data());
