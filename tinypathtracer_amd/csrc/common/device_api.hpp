@@ -135,6 +135,14 @@ struct TraceArgs {
     // band list or band_cost, one frame, no XCD runs.  (Last in the struct: no other field moves.)
     const uint32_t* tile_list;
     int32_t n_tiles;
+    // Run-ahead (trace_variant.hpp trace_runs_ahead; variants compiled without it ignore both).
+    // ahead_max: the samples the same set's later launches will still give these pixels (0: its
+    // last launch, or off).  credit: nullable, one int per pixel and frame, indexed like one RNG
+    // plane: the samples of this launch's quota the pixel has already run (read), those of the
+    // later launches' it ran here (written).  Null: every lane runs exactly `samples`.
+    // (Appended: no other field moves; ahead_max fills the padding behind n_tiles.)
+    int32_t ahead_max;
+    int32_t* credit;
 };
 
 struct ResolveArgs {
@@ -271,6 +279,7 @@ hipError_t launch_wavefront(WfArgs w, uint32_t* h_count, hipEvent_t ev[2], int32
 constexpr int kTraceShapeWords = 6;
 hipError_t launch_trace(const TraceArgs& a, hipStream_t s, int32_t* shape = nullptr);
 bool trace_quad_fits(const TraceArgs& a);   // lanes_per_pixel 4: one-lane records, the quads' stacks fit in LDS
+bool trace_args_run_ahead(const TraceArgs& a);   // the variant launch_trace picks for `a` is compiled with run-ahead
 int trace_family_wgw(int family);           // tpt_debug_trace_wg_waves
 int trace_waves_per_simd();                 // the one-lane variants' __launch_bounds__ waves per SIMD
 hipError_t launch_trace_ptr(const void* a, hipStream_t s, int32_t* shape);   // a: const TraceArgs*

@@ -111,6 +111,17 @@ constexpr bool trace_key_legal(const TraceKey& k) {
     return !k.noemit || f.lanes == 2;   // NOEMIT is a pair-mode specialisation
 }
 
+// Run-ahead (k_trace, TraceArgs credit / ahead_max): when a set's spp is
+// cut into several launches, a lane that has run this launch's samples while another lane of
+// its wave still owes some goes on with the pixel's next samples, up to ahead_max, instead of
+// idling until the wave ends; the pixel's credit plane tells the set's next launch how many
+// of its samples are already done.  A pixel's samples still run in order on its own RNG
+// stream and sum in the same order, so the frame is bit-identical.  The one-lane
+// full-occupancy family's 8-level variants only: the others are compiled without it.  (The
+// 64-level variants measured -2.6 % with it at C4, tir at depth 32, where a tile's time is a few
+// pixels' long chains and the lanes that run ahead beside them slow those chains down.)
+constexpr bool trace_runs_ahead(TraceFamily f, bool deep) { return f == TF_LANE && !deep; }
+
 // The descriptor k_trace is instantiated with.
 template <TraceFamily F, int MAXD_, bool LIGHTS_, bool MTL_LDS_, typename StackT_, bool NOEMIT_>
 struct TraceVariant {
@@ -124,6 +135,8 @@ struct TraceVariant {
                           PAIR = fam.lanes == 2, DRAIN = F == TF_DRAIN, QUAD = fam.lanes == 4, NOEMIT = NOEMIT_;
     // the pruned unwind (below): the 2-word-record variants of the one-lane, DRAIN and four-lane families
     static constexpr bool PRUNE = !LIGHTS_ && ORDERED && !PAIR && !ENVIS;
+    // lanes run ahead across a set's sample chunks (trace_runs_ahead below)
+    static constexpr bool AHEAD = trace_runs_ahead(F, MAXD_ == 64);
     using StackT = StackT_;
 };
 

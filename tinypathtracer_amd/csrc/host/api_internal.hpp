@@ -380,6 +380,7 @@ struct tpt_scene {
     DevBuf<float4> inner, inner4, tri, shade;
     // frame state
     DevBuf<uint32_t> rng;
+    DevBuf<int32_t> credit;                 // run-ahead (TraceArgs::credit): one plane per frame, zero between calls
     DevBuf<float> accum, radiance_tmp;
     DevBuf<uint8_t> bgra_tmp;
     DevBuf<unsigned long long> counters, debug;

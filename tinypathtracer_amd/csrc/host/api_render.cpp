@@ -202,6 +202,7 @@ tpt_status render_planned(tpt_scene* s, const tpt::TraceArgs& a, const tpt_param
         if (plan.set_rows[k] <= 0) continue;
         tpt::TraceArgs ak = a;
         ak.samples = plan.launches[j].samples;
+        ak.ahead_max = a.credit ? plan.launches[j].ahead_max : 0;   // run-ahead: what this set's later launches give
         // XCD runs: chunk c of a set rotates the runs' XCDs by c (trace.hip prologue), so a
         // set whose few rows leave the per-launch rotation incomplete still spreads its heavy
         // columns over every XCD across its chunks
@@ -302,6 +303,7 @@ tpt_status tpt_render_frames(tpt_scene* s, const tpt_env* env, const tpt_camera*
     // per-frame state planes, frame f at offset f * (6|3) * npix
     HIP_OR_FAIL(s->rng.alloc(6 * npix * nf));
     HIP_OR_FAIL(s->accum.alloc(3 * npix * nf));
+    HIP_OR_FAIL(s->credit.alloc(npix * nf));
     HIP_OR_FAIL(s->counters.alloc(32));
     if (!resume) HIP_OR_FAIL(hipMemsetAsync(s->accum.p, 0, 3 * npix * nf * sizeof(float), st));   // thrust::fill (:534)
     HIP_OR_FAIL(hipMemsetAsync(s->counters.p, 0, 32 * sizeof(unsigned long long), st));
@@ -403,6 +405,27 @@ tpt_status tpt_render_frames(tpt_scene* s, const tpt_env* env, const tpt_camera*
     a.leaf_kb = plan.leaf_kb;
     a.xcd_run = plan.xcd_run;
     a.xcd_rot = 0;   // (per launch: render_planned)
+    // Run-ahead (trace_variant.hpp trace_runs_ahead): on when the variant these launches select is
+    // compiled with it and some set's spp is cut into several launches (the default pipeline, forced
+    // pipe_sets / pipe_chunks, an explicit spp_per_launch).  The sets render disjoint rows and a set's
+    // launches are stream-ordered, so the plane needs no atomics.  A set's last launch has ahead_max 0
+    // and leaves every pixel's credit at zero, so the plane is zero again at the end of the call and a
+    // TPT_FLAG_ACCUMULATE continuation starts from zero; it is zeroed here all the same, on the main
+    // stream, before render_planned forks to the sets' streams.
+    // band_cost with run-ahead: a band's cost moves between a set's launches, its sum over the call
+    // (what the caller reads) covers the same samples.
+    a.ahead_max = 0;   // (per launch: render_planned)
+    a.credit = nullptr;
+    bool chunked = false;
+    for (const tpt::PlanLaunch& l : plan.launches) chunked = chunked || l.ahead_max > 0;
+    bool ahead = chunked && !(p->flags & TPT_FLAG_WAVEFRONT) && tpt::trace_args_run_ahead(a);
+#ifdef TPT_PROFILE_PHASES
+    if (std::getenv("TPT_DEBUG_NO_AHEAD")) ahead = false;   // the lane-step split without it from the same build
+#endif
+    if (ahead && bh > 0) {
+        HIP_OR_FAIL(hipMemsetAsync(s->credit.p, 0, npix * nf * sizeof(int32_t), st));
+        a.credit = s->credit.p;
+    }
 
     double trace_ms = 0.0, kernel_ms = 0.0;
     int launches = 0;

@@ -165,6 +165,10 @@ LaunchPlan plan_launches(const PlanInput& in) {
             done += n;
         }
     }
+    // what each launch's set still has to give after it (launches lie set by set, in order)
+    for (size_t j = pl.launches.size(); j-- > 1;)
+        if (pl.launches[j - 1].set == pl.launches[j].set)
+            pl.launches[j - 1].ahead_max = pl.launches[j].samples + pl.launches[j].ahead_max;
     // set k renders bands band_index + k * band_count of the band_count * nset
     // interleave; of an explicit deal, list entries k, k + nset, ... (a short last
     // band, last in the list, stays last in its set)

@@ -49,6 +49,7 @@ struct PlanInput {
 
 struct PlanLaunch {
     int32_t set, samples;
+    int32_t ahead_max = 0;              // the samples of the same set's later launches (TraceArgs::ahead_max)
 };
 
 struct LaunchPlan {

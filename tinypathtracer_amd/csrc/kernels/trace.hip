@@ -238,14 +238,26 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
     rec.nlds = a.rec_lds_levels;
     rec.words = LIGHTS ? 5 : 2;
 
+    constexpr bool AHEAD = V::AHEAD;
     uint32_t st[6];
     V3 total = v3(0.0f, 0.0f, 0.0f);
+    int credit0 = 0;   // run-ahead: the samples of this launch's quota the pixel has already run
     if (active) {
 #pragma unroll
         for (int i = 0; i < 6; ++i) st[i] = g_rng[i * npix + off];
         total = v3(g_acc[off], g_acc[npix + off], g_acc[2 * npix + off]);
+        // (read here, beside the planes' loads: read after them it cost the flagship variant
+        // 8 more spilled VGPRs)
+        if constexpr (AHEAD) {
+            if (a.credit) credit0 = a.credit[(size_t)frame * npix + off];
+        }
     }
+    // Run-ahead (trace_variant.hpp): `remaining` counts this launch's quota down and goes on
+    // through zero for the samples a lane runs ahead; a pixel that ran ahead in the set's
+    // earlier launches starts with that much less, possibly with nothing left or less.
+    // (launch_one leaves ahead_max at 0 without a credit plane)
     int remaining = a.samples;
+    if constexpr (AHEAD) remaining -= credit0;
     int phase = PH_CAMERA;
     int depth = 0, li = 0;
     uint32_t mk = 0;   // material id | p-kind << 30 of the current bounce (PRUNE: | the path's ztop << 15)
@@ -588,6 +600,22 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
             }
             ready = false;
         }
+        // Run-ahead: a lane *owes* while it has samples of this launch's quota left to start or
+        // runs the last of them (remaining == 0 and not back at the camera; a sample run ahead
+        // has remaining < 0).  One ballot for the whole wave, here in uniform control flow
+        // (late in the pass: its result lives to the camera section only).
+        // Termination: remaining only falls and a dead lane stays dead, so a lane that has
+        // stopped owing never owes again; once no lane owes, the camera section below starts
+        // no sample, every lane that reaches it dies, and the samples in flight end as they
+        // always do.  Nothing waits: a lane at the camera either starts a sample or dies.
+        // ahead_lim (uniform): a lane back at the camera stops once remaining has fallen to it:
+        // 0 when no lane owes, else what the set's later launches still give, negated.
+        [[maybe_unused]] int ahead_lim = 0;
+        if constexpr (AHEAD) {
+            const bool owes_any =
+                __ballot(ts != TS_DEAD && (remaining > 0 || (remaining == 0 && phase != PH_CAMERA))) != 0ull;
+            ahead_lim = owes_any ? -a.ahead_max : 0;
+        }
         if (in_pass || woke) {
             if (PAIR && finish && pend >= 0) {
                 // the side lane still sums a level's shadow rays: wait for it (exchange below)
@@ -697,7 +725,9 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
             TPT_SEC(4)
             V3 to = r.o;
             if (phase == PH_CAMERA) {
-                if (remaining == 0) {
+                // run-ahead: with the quota done, one more sample while a lane of the wave
+                // still owes and the set's later launches have one left to give
+                if (AHEAD ? remaining <= ahead_lim : remaining == 0) {
                     ts = TS_DEAD;
                 } else {
                     --remaining;
@@ -905,6 +935,9 @@ __global__ __launch_bounds__(64 * V::WGW, V::WAVES) void k_trace(TraceArgs a) {
         g_acc[off] = total.x;
         g_acc[npix + off] = total.y;
         g_acc[2 * npix + off] = total.z;
+        if constexpr (AHEAD) {   // the samples run ahead: the set's next launch starts that many short
+            if (a.credit) a.credit[(size_t)frame * npix + off] = max(0, -remaining);
+        }
     }
     if (!lead) {   // QUAD: the pixel's work is counted once
         c_trav = c_inner = c_wide = c_leaf = c_shade = c_ovf = c_local = 0;
@@ -1199,6 +1232,8 @@ static hipError_t launch_one(const TraceArgs& a_in, const LaunchCtx& c) {
     // (16-pixel columns; four lanes per pixel keep the round-robin deal)
     if (a.xcd_run > 0 && (V::QUAD || tiles.x % 8 != 0 || (tiles.x / 8) % (unsigned)a.xcd_run != 0)) a.xcd_run = 0;
     const TraceLds l = trace_lds_layout(V::key, WGW, a.stack_depth, a.max_depth, a.n_materials, f.max_slots, f.max_levels);
+    if (!V::AHEAD) a.credit = nullptr;   // run-ahead: compiled into this variant, and with a plane to keep it in
+    if (!a.credit) a.ahead_max = 0;
     a.mtl_in_lds = V::MTL_LDS ? 1 : 0;
     a.lds_mtl_offset = l.mtl_offset;
     a.lds_nodes = 0;
@@ -1251,11 +1286,19 @@ int trace_waves_per_simd() { return kTraceFamily[TF_LANE].waves; }
 // the build's workgroup shape per family, in tpt_debug_trace_wg_waves' order
 int trace_family_wgw(int family) { return family >= 0 && family < kTracePublicFamilies ? kTraceFamily[family].wgw : 0; }
 
+static TraceSelection select_for(const TraceArgs& a) {
+    return select_trace_variant({(a.flags & TPT_FLAG_REF_ORDER) != 0, a.env_is != 0, a.pair != 0, a.quad != 0,
+                                 a.drained != 0, a.n_lights, a.n_materials, a.n_faces, a.max_depth, a.any_emitter != 0});
+}
+
 static hipError_t launch_trace_impl(const TraceArgs& a_in, hipStream_t s, bool dry, int32_t* shape) {
-    const TraceSelection sel = select_trace_variant(
-        {(a_in.flags & TPT_FLAG_REF_ORDER) != 0, a_in.env_is != 0, a_in.pair != 0, a_in.quad != 0, a_in.drained != 0,
-         a_in.n_lights, a_in.n_materials, a_in.n_faces, a_in.max_depth, a_in.any_emitter != 0});
+    const TraceSelection sel = select_for(a_in);
     return sel.error ? hipErrorInvalidValue : launch_key(trace_key_pack(sel.key), a_in, LaunchCtx{s, dry, shape});
+}
+
+bool trace_args_run_ahead(const TraceArgs& a) {
+    const TraceSelection sel = select_for(a);
+    return !sel.error && trace_runs_ahead(sel.key.family, sel.key.deep);
 }
 
 hipError_t launch_trace(const TraceArgs& a, hipStream_t s, int32_t* shape) { return launch_trace_impl(a, s, false, shape); }

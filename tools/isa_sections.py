@@ -84,7 +84,7 @@ def helper_ranges(src):
 
 
 def kernel_ranges(src):
-    k = src.find(r"^void k_trace\(")
+    k = src.find(r"^(__global__ .*)?void k_trace\(")   # (the signature may carry its attributes on the same line)
     loop_top = src.find(r"^    for \(;;\) \{", k)
     done = src.find(r"if \(in_pass\) \{", loop_top + 1)
     s = [src.find(rf"TPT_SEC\({i}\)", done) for i in range(1, 7)]
