@@ -538,6 +538,37 @@ tpt_status tpt_history_create(tpt_scene* scene, int32_t width, int32_t height, t
 tpt_status tpt_history_reset(tpt_history* h);
 void tpt_history_destroy(tpt_history* h);
 
+/* History clipping (DESIGN.md section 5 "History clipping" holds the definition): a setting of
+ * the history that every temporal entry point obeys, off by default.  The reprojection rules
+ * test geometry only, so what changes because something else moved -- a moved object's shadow,
+ * its reflection on a wall that stood still -- is reprojected as if nothing had happened.  With
+ * the clip on, each call first takes, per pixel and channel, the mean mu and the standard
+ * deviation sigma of the colour it accumulates over the pixels of a (2 radius + 1)^2 window that
+ * are similar to the centre (the same material -- and bounce count in tpt_temporal_path -- and on
+ * a hit a depth within the call's depth_tol of the centre's and a normal with n(q) . n(p) >=
+ * normal_min), and a reprojected pixel's gathered history colour is clamped to [mu - gamma
+ * sigma, mu + gamma sigma] before it is blended.  A history that the clamp moved has its length
+ * capped at max_history (before the + 1) and its luminance moments shifted to the clamped colour
+ * at their variance.  A window with fewer than four similar pixels gives no box.  The setting
+ * survives tpt_history_reset.  The box's two float4 planes, 32 B per pixel, are allocated at the
+ * first clipped call.  With the clip off every entry point launches exactly the kernels it
+ * launches without this feature.
+ * TPT_ERR_INVALID_ARG (nothing is changed): a null history, radius outside 1..3, gamma NaN,
+ * infinite or not > 0, max_history outside 1..65536, an unknown flag; a null out. */
+typedef struct {
+    int32_t radius;        /* 1..3: the window is (2 radius + 1)^2 pixels */
+    float   gamma;         /* finite, > 0: half-width of the box in standard deviations */
+    int32_t max_history;   /* 1..65536: a clipped pixel's history length is capped at this before the +1 */
+    int32_t flags;         /* 0; unknown bits are refused */
+} tpt_clip_params;
+typedef struct {
+    double   box_ms;       /* the box kernel's duration (HIP events); 0 when clipping is off */
+    uint64_t boxed;        /* pixels of the last call whose window gave a box (n >= 4) */
+    uint64_t clipped;      /* reprojected pixels of the last call whose history was moved by the clip */
+} tpt_clip_stats;
+tpt_status tpt_history_set_clip(tpt_history* h, const tpt_clip_params* p);   /* p null: off (the default) */
+tpt_status tpt_history_clip_stats(const tpt_history* h, tpt_clip_stats* out); /* of the last temporal call */
+
 #define TPT_TEMPORAL_DEMODULATE 0x1   /* accumulate radiance / max(albedo, 1e-3); multiply the current albedo back */
 #define TPT_TEMPORAL_TILES      0x2   /* A/B: lanes in 16x16 tiles instead of 64-pixel row segments
                                          (bit-identical output) */
@@ -605,8 +636,8 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* camera, const float* r
  * Everything else is tpt_temporal's, the refusals too (and a missing face guide).
  * Not tracked: shading that changes because something else moved -- a moved object's shadow
  * or its reflection on a wall that stood still is reprojected as if nothing had happened,
- * and `alpha` is what bounds that lag.  Lights do not move; meshes that deform are
- * tpt_temporal_deform's. */
+ * and `alpha` is what bounds that lag (tpt_history_set_clip shortens it).  Lights do not move;
+ * meshes that deform are tpt_temporal_deform's. */
 tpt_status tpt_temporal_motion(tpt_history* h, const tpt_camera* camera, const float* radiance_in,
                                const tpt_aov* guides, const tpt_temporal_params* params,
                                float* radiance_out, float* variance_out, float* history_len_out,
@@ -635,7 +666,8 @@ tpt_status tpt_temporal_motion(tpt_history* h, const tpt_camera* camera, const f
  * not finite.  guides, motion_out and everything else are tpt_temporal_motion's, the refusals
  * too (and an unbuilt scene).  DESIGN.md section 5 "Deforming meshes" holds the definition.
  * Not tracked: a deforming object's shadow and its reflections (in mirrors too), reprojected as
- * if nothing had happened; topology changes.  Lights do not move. */
+ * if nothing had happened (tpt_history_set_clip shortens that lag); topology changes.  Lights do
+ * not move. */
 tpt_status tpt_temporal_deform(tpt_history* h, const tpt_camera* camera, const float* radiance_in,
                                const tpt_aov* guides, const tpt_temporal_params* params,
                                float* radiance_out, float* variance_out, float* history_len_out,

@@ -42,6 +42,7 @@ struct BVHNode {
 };
 static_assert(sizeof(BVHNode) == 36, "BVHNode layout");
 static_assert(sizeof(tpt_aov_path_params) == 8 && sizeof(tpt_aov_path_stats) == 24, "tpt_aov_path_* layout");
+static_assert(sizeof(tpt_clip_params) == 16 && sizeof(tpt_clip_stats) == 24, "tpt_clip_* layout");
 
 class DeviceScene;
 
@@ -220,6 +221,17 @@ inline tpt_temporal_path_params defaultTemporalPath() {
     return p;
 }
 
+// The hosts' defaults of history clipping (History::setClip), by the sweep of tools/clip_quality.py
+// (DESIGN.md section 5 "History clipping")
+inline tpt_clip_params defaultClip() {
+    tpt_clip_params p{};
+    p.radius = 1;
+    p.gamma = 1.0f;
+    p.max_history = 4;
+    p.flags = 0;
+    return p;
+}
+
 // The hosts' defaults of the variance-guided filter (DESIGN.md section 5 "Post-pass":
 // sigma_lum by the sweep there, not the paper's 4)
 inline tpt_svgf_params defaultSVGF(int iterations = 5) {
@@ -243,6 +255,14 @@ public:
         h_.reset(h);
     }
     void reset() { check(tpt_history_reset(h_.get())); }   // the next temporal() starts over
+    // History clipping (tpt_history_set_clip): every later temporal call on this history clamps its
+    // reprojected history to the current frame's neighbourhood; nullptr turns it off (the default).
+    void setClip(const tpt_clip_params* params) { check(tpt_history_set_clip(h_.get(), params)); }
+    tpt_clip_stats clipStats() const {   // of the last temporal call
+        tpt_clip_stats st{};
+        check(tpt_history_clip_stats(h_.get(), &st));
+        return st;
+    }
     tpt_history* handle() const { return h_.get(); }
 
 private:

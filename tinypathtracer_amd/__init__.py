@@ -24,7 +24,7 @@ from ._lib import TPTError, build_identity, check, lib
 
 __all__ = ["Camera", "Scene", "DeviceScene", "BVH", "EnvLight", "PathTracer", "Frame", "TPTError",
            "procedural_sky", "version", "device_count", "build_identity", "NODE_DTYPE", "DENOISE_DEFAULTS",
-           "History", "TEMPORAL_DEFAULTS", "TEMPORAL_PATH_DEFAULTS", "motion_matrices", "ADAPTIVE_DEFAULTS"]
+           "History", "TEMPORAL_DEFAULTS", "TEMPORAL_PATH_DEFAULTS", "CLIP_DEFAULTS", "motion_matrices", "ADAPTIVE_DEFAULTS"]
 
 # BVHNode (include/bvh.cuh:52-58): parent, info{left,right | fid,placeHolder}, box
 NODE_DTYPE = np.dtype([("parent", "<u4"), ("a", "<i4"), ("b", "<i4"), ("bmin", "<f4", 3), ("bmax", "<f4", 3)])
@@ -582,6 +582,11 @@ _PLANES.update(variance=(1, "float32"), history_len=(1, "float32"), motion_out=(
 TEMPORAL_PATH_DEFAULTS = dict(TEMPORAL_DEFAULTS, point_tol=8.0)
 
 
+# History clipping (History.set_clip): by the sweep of tools/clip_quality.py (DESIGN.md section 5
+# "History clipping")
+CLIP_DEFAULTS = {"radius": 1, "gamma": 1.0, "max_history": 4}
+
+
 def motion_matrices(prev, cur):
     """tpt_motion_matrices: from the objects' local-to-world matrices of the previous frame
     and of this one ([n, 16] float32, column-major) the records tpt_temporal_motion works
@@ -619,6 +624,26 @@ class History:
         """The next temporal() starts over: every pixel disoccluded."""
         check(lib().tpt_history_reset(self.handle))
         return self
+
+    def set_clip(self, params=True, *, radius: int = CLIP_DEFAULTS["radius"], gamma: float = CLIP_DEFAULTS["gamma"],
+                 max_history: int = CLIP_DEFAULTS["max_history"]):
+        """History clipping (tpt_history_set_clip): every later temporal call on this history
+        clamps its reprojected history colour to mean +- gamma standard deviations of the current
+        frame's colours over the similar pixels of a (2 radius + 1)^2 window, and caps a clipped
+        pixel's history length at max_history.  set_clip(None) turns it off (the default); the
+        setting survives reset()."""
+        if params is None:
+            check(lib().tpt_history_set_clip(self.handle, None))
+        else:
+            p = _lib.ClipParams(int(radius), float(gamma), int(max_history), 0)
+            check(lib().tpt_history_set_clip(self.handle, C.byref(p)))
+        return self
+
+    def clip_stats(self) -> dict:
+        """box_ms, boxed, clipped of the last temporal call on this history (zeros with the clip off)."""
+        st = _lib.ClipStats()
+        check(lib().tpt_history_clip_stats(self.handle, C.byref(st)))
+        return st.as_dict()
 
     def close(self):
         if self.handle:

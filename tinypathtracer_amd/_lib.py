@@ -163,6 +163,17 @@ class TemporalStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ClipParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("gamma", C.c_float), ("max_history", C.c_int32), ("flags", C.c_int32)]
+
+
+class ClipStats(C.Structure):
+    _fields_ = [("box_ms", C.c_double), ("boxed", C.c_uint64), ("clipped", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # (name, restype, argtypes) -- every symbol include/tpt.h declares
 SIGNATURES = [
     ("tpt_version", C.c_char_p, []),
@@ -206,6 +217,8 @@ SIGNATURES = [
     ("tpt_history_create", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     ("tpt_history_reset", C.c_int, [C.c_void_p]),
     ("tpt_history_destroy", None, [C.c_void_p]),
+    ("tpt_history_set_clip", C.c_int, [C.c_void_p, C.POINTER(ClipParams)]),
+    ("tpt_history_clip_stats", C.c_int, [C.c_void_p, C.POINTER(ClipStats)]),
     ("tpt_temporal", C.c_int, [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(Aov),
                                C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(TemporalStats)]),

@@ -451,6 +451,42 @@ struct DeformArgs {
 };
 hipError_t launch_temporal_deform(const TemporalArgs& a, const DeformArgs& de, hipStream_t s);
 
+// post.hip: history clipping (tpt_history_set_clip; DESIGN.md section 5 "History clipping").
+// k_clip_box writes, per pixel, the box of the colours the temporal kernel accumulates over the
+// pixel's similar neighbours as two float4 planes: (lo.rgb, n) and (hi.rgb, 0), n the taps
+// counted; n < 4 gives lo = -inf, hi = +inf.  It reads the temporal call's own inputs.
+struct ClipBoxArgs {
+    int32_t width, height;
+    int32_t radius;                      // 1..3: the window is (2 radius + 1)^2 pixels
+    int32_t demodulate;
+    float depth_tol, normal_min;         // the temporal call's own
+    float gamma;                         // half-width of the box in standard deviations
+    const float* radiance_in;            // W*H*3
+    const float* albedo;                 // W*H*3 (read when demodulate)
+    const float* normal;                 // W*H*3
+    const float* depth;                  // W*H
+    const int32_t* material;             // W*H
+    const int32_t* bounces;              // nullable, W*H: tpt_temporal_path's k, compared as well
+    float4* lo;                          // (lo.rgb, n)
+    float4* hi;                          // (hi.rgb, 0)
+    unsigned long long* boxed;           // kTemporalSlots counters: pixels with n >= 4
+};
+hipError_t launch_clip_box(const ClipBoxArgs& a, hipStream_t s);
+
+// What the clipped compilations of the temporal kernels (k_temporal_clip, ...) take on top of
+// their twins' arguments: the two planes, the cap on a clipped pixel's history length and the
+// counter of the pixels whose history the clip moved.
+struct ClipArgs {
+    const float4* lo;
+    const float4* hi;
+    float clip_history;
+    unsigned long long* clipped;         // kTemporalSlots counters, as TemporalArgs::reprojected
+};
+hipError_t launch_temporal_clip(const TemporalArgs& a, const ClipArgs& cl, hipStream_t s);
+hipError_t launch_temporal_motion_clip(const TemporalArgs& a, const MotionArgs& mo, const ClipArgs& cl, hipStream_t s);
+hipError_t launch_temporal_path_clip(const TemporalArgs& a, const TemporalPathArgs& pa, const ClipArgs& cl, hipStream_t s);
+hipError_t launch_temporal_deform_clip(const TemporalArgs& a, const DeformArgs& de, const ClipArgs& cl, hipStream_t s);
+
 // post.hip: the variance-guided a-trous filter (tpt_denoise_svgf; DESIGN.md section 5
 // "Post-pass").  tpt_denoise's planes, the colour plane's fourth component carrying the
 // variance: colour = (r, g, b, v), guide = (n.xyz, z).

@@ -522,11 +522,22 @@ struct tpt_history {
     // while snap_serial is still the current serial.
     DevBuf<float> snap_verts, snap_norms;
     uint64_t serial = 0, snap_serial = ~0ull;
+    // tpt_history_set_clip: the setting (it survives a reset), k_clip_box's two planes (allocated at
+    // the first clipped call: +32 B per pixel), the counters of the boxed (set 0) and the clipped
+    // (set 1) pixels, the last call's figures and the box kernel's events
+    bool clip_on = false;
+    tpt_clip_params clip = {};
+    DevBuf<float4> clip_planes[2];
+    SpreadCounters clip_count;
+    tpt_clip_stats clip_stats = {};
+    hipEvent_t clip_ev[2] = {nullptr, nullptr};
     hipEvent_t ev[2] = {nullptr, nullptr};
 
     ~tpt_history() {
         DeviceGuard g(device);
         for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto& e : clip_ev)
             if (e) (void)hipEventDestroy(e);
     }
 };

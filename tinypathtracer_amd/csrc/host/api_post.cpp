@@ -1,5 +1,5 @@
 // api_post.cpp -- the post-pass entry points of the C-ABI (post.hip): tpt_render_aov, tpt_render_aov_path,
-// tpt_render_aov_path_points, tpt_denoise, tpt_history_*, tpt_temporal, tpt_temporal_motion, tpt_temporal_path,
+// tpt_render_aov_path_points, tpt_denoise, tpt_history_* (tpt_history_set_clip too), tpt_temporal, tpt_temporal_motion, tpt_temporal_path,
 // tpt_temporal_deform and tpt_denoise_svgf.  Each takes its buffers from either
 // side: host buffers go through the device staging the scene / history keeps
 // (api_internal.hpp Staging).
@@ -275,6 +275,7 @@ tpt_status tpt_history_create(tpt_scene* s, int32_t W, int32_t H, tpt_history** 
         HIP_OR_FAIL(h->h_records.alloc((size_t)s->n_objects * tpt::kMotionRecordFloats));
     }
     for (auto& e : h->ev) HIP_OR_FAIL(hipEventCreate(&e));
+    for (auto& e : h->clip_ev) HIP_OR_FAIL(hipEventCreate(&e));
     *out = h.release();
     return TPT_OK;
 }
@@ -288,6 +289,31 @@ tpt_status tpt_history_reset(tpt_history* h) {
 }
 
 void tpt_history_destroy(tpt_history* h) { delete h; }
+
+// History clipping (post.hip k_clip_box and the k_temporal*_clip kernels; DESIGN.md section 5
+// "History clipping"): a setting of the history that every temporal entry point obeys.
+tpt_status tpt_history_set_clip(tpt_history* h, const tpt_clip_params* p) {
+    if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
+    if (!p) {
+        h->clip_on = false;
+        return TPT_OK;
+    }
+    if (p->radius < 1 || p->radius > 3) return fail(TPT_ERR_INVALID_ARG, "clip radius must be 1..3");
+    if (!(std::isfinite(p->gamma) && p->gamma > 0.0f)) return fail(TPT_ERR_INVALID_ARG, "clip gamma must be finite and > 0");
+    if (p->max_history < 1 || p->max_history > 65536)
+        return fail(TPT_ERR_INVALID_ARG, "clip max_history must be 1..65536");
+    if (p->flags != 0) return fail(TPT_ERR_INVALID_ARG, "unknown clip flags");
+    h->clip = *p;
+    h->clip_on = true;
+    return TPT_OK;
+}
+
+tpt_status tpt_history_clip_stats(const tpt_history* h, tpt_clip_stats* out) {
+    if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
+    if (!out) return fail(TPT_ERR_INVALID_ARG, "null out");
+    *out = h->clip_stats;
+    return TPT_OK;
+}
 
 // What tpt_temporal_path passes on top of tpt_temporal's arguments.
 struct PathInputs {
@@ -425,11 +451,50 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
     pa.next_points = h->points[to].p;
     a.reprojected = h->count.set(0);
     HIP_OR_FAIL(h->count.zero(st));
+    const bool clip = h->clip_on;
+    tpt::ClipArgs cl{};
+    if (clip) {
+        // the box of this frame's colours, from the staged device copies of the inputs and ahead of
+        // the temporal kernel: radiance_out may be radiance_in
+        for (auto& plane : h->clip_planes) HIP_OR_FAIL(plane.alloc(npix));
+        HIP_OR_FAIL(h->clip_count.alloc(2));
+        tpt::ClipBoxArgs b{};
+        b.width = W;
+        b.height = H;
+        b.radius = h->clip.radius;
+        b.demodulate = a.demodulate;
+        b.depth_tol = a.depth_tol;
+        b.normal_min = a.normal_min;
+        b.gamma = h->clip.gamma;
+        b.radiance_in = a.radiance_in;
+        b.albedo = a.albedo;
+        b.normal = a.normal;
+        b.depth = a.depth;
+        b.material = a.material;
+        b.bounces = path ? pa.bounces : nullptr;
+        b.lo = h->clip_planes[0].p;
+        b.hi = h->clip_planes[1].p;
+        b.boxed = h->clip_count.set(0);
+        cl.lo = b.lo;
+        cl.hi = b.hi;
+        cl.clip_history = (float)h->clip.max_history;
+        cl.clipped = h->clip_count.set(1);
+        HIP_OR_FAIL(h->clip_count.zero(st));
+        HIP_OR_FAIL(hipEventRecord(h->clip_ev[0], st));
+        HIP_OR_FAIL(tpt::launch_clip_box(b, st));
+        HIP_OR_FAIL(hipEventRecord(h->clip_ev[1], st));
+    }
     HIP_OR_FAIL(hipEventRecord(h->ev[0], st));
-    HIP_OR_FAIL(path     ? tpt::launch_temporal_path(a, pa, st)
-                : motion ? tpt::launch_temporal_motion(a, mo, st)
-                : deform ? tpt::launch_temporal_deform(a, de, st)
-                         : tpt::launch_temporal(a, st));
+    if (clip)
+        HIP_OR_FAIL(path     ? tpt::launch_temporal_path_clip(a, pa, cl, st)
+                    : motion ? tpt::launch_temporal_motion_clip(a, mo, cl, st)
+                    : deform ? tpt::launch_temporal_deform_clip(a, de, cl, st)
+                             : tpt::launch_temporal_clip(a, cl, st));
+    else
+        HIP_OR_FAIL(path     ? tpt::launch_temporal_path(a, pa, st)
+                    : motion ? tpt::launch_temporal_motion(a, mo, st)
+                    : deform ? tpt::launch_temporal_deform(a, de, st)
+                             : tpt::launch_temporal(a, st));
     HIP_OR_FAIL(hipEventRecord(h->ev[1], st));
     if (deform) {   // the world buffers as this call saw them, for the next one
         HIP_OR_FAIL(hipMemcpyAsync(h->snap_verts.p, s->wverts.p, nv3 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -437,6 +502,7 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
     }
     HIP_OR_FAIL(sg.finish());
     HIP_OR_FAIL(h->count.fetch(st));
+    if (clip) HIP_OR_FAIL(h->clip_count.fetch(st));
     HIP_OR_FAIL(hipStreamSynchronize(st));
     // the new state, this camera and the scene's object transforms replace the old
     h->prev_vert_trans = s->h_vert_trans;
@@ -445,6 +511,12 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
     if (!invert4(cam->c2w, h->prev_inv)) h->valid = false;   // a singular c2w: nothing can be reprojected into it
     h->prev = cc;
     if (deform) h->snap_serial = h->serial;
+    h->clip_stats = tpt_clip_stats{};
+    if (clip) {
+        HIP_OR_FAIL(elapsed_ms(h->clip_ev[0], h->clip_ev[1], &h->clip_stats.box_ms));
+        h->clip_stats.boxed = h->clip_count.sum(0);
+        h->clip_stats.clipped = h->clip_count.sum(1);
+    }
     if (stats) {
         HIP_OR_FAIL(elapsed_ms(h->ev[0], h->ev[1], &stats->kernel_ms));
         stats->reprojected = h->count.sum(0);

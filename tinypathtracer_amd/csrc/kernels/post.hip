@@ -23,6 +23,9 @@
 //    reprojection and accumulation across frames (tpt_temporal; tpt_temporal_motion, which follows
 //    objects that moved; tpt_temporal_path, which follows reflections in mirrors;
 //    tpt_temporal_deform, which follows meshes whose vertices moved).
+//  * k_clip_box and the four k_temporal*_clip: history clipping (tpt_history_set_clip): the box
+//    of the current frame's colours around each pixel, LDS-staged, and the temporal kernels
+//    compiled once more with the clamp to it.
 //  * k_svgf_pack / k_svgf_estimate / k_svgf_atrous / k_svgf_atrous_lds /
 //    k_svgf_resolve: the variance-guided filter (tpt_denoise_svgf) on the same two
 //    planes, the variance in the colour plane's fourth component.
@@ -385,6 +388,7 @@ constexpr float kMinWsum = 1.0f / 16.0f;     // least sum of valid bilinear weig
 // pass on mirror-path guides, which compares bounce counts and terminal points as well.
 // A fourth, with TPT_TEMPORAL_DEFORM, is k_temporal_deform (tpt_temporal_deform): the pass
 // that follows deforming meshes through the previous frame's vertices.
+#define TPT_TEMPORAL_CLIP 0
 #define TPT_TEMPORAL_DEFORM 0
 #define TPT_TEMPORAL_PATH 0
 #define TPT_TEMPORAL_MOTION 0
@@ -405,6 +409,178 @@ constexpr float kMinWsum = 1.0f / 16.0f;     // least sum of valid bilinear weig
 #undef TPT_TEMPORAL_DEFORM
 #undef TPT_TEMPORAL_PATH
 #undef TPT_TEMPORAL_MOTION
+#undef TPT_TEMPORAL_CLIP
+// Four more, with TPT_TEMPORAL_CLIP: k_temporal_clip, k_temporal_motion_clip, k_temporal_path_clip
+// and k_temporal_deform_clip, the same four with history clipping (tpt_history_set_clip).  A
+// macro again and for the same reason: the four above stay what they were, instruction for
+// instruction (tools/kernel_diff.py against the commit before).
+#define TPT_TEMPORAL_CLIP 1
+#define TPT_TEMPORAL_DEFORM 0
+#define TPT_TEMPORAL_PATH 0
+#define TPT_TEMPORAL_MOTION 0
+#include "temporal_kernel.hpp"
+#undef TPT_TEMPORAL_MOTION
+#define TPT_TEMPORAL_MOTION 1
+#include "temporal_kernel.hpp"
+#undef TPT_TEMPORAL_MOTION
+#undef TPT_TEMPORAL_PATH
+#define TPT_TEMPORAL_MOTION 0
+#define TPT_TEMPORAL_PATH 1
+#include "temporal_kernel.hpp"
+#undef TPT_TEMPORAL_PATH
+#undef TPT_TEMPORAL_DEFORM
+#define TPT_TEMPORAL_PATH 0
+#define TPT_TEMPORAL_DEFORM 1
+#include "temporal_kernel.hpp"
+#undef TPT_TEMPORAL_DEFORM
+#undef TPT_TEMPORAL_PATH
+#undef TPT_TEMPORAL_MOTION
+#undef TPT_TEMPORAL_CLIP
+
+// The box of history clipping (DESIGN.md section 5 "History clipping" holds the definition):
+// 16x16 tiles; per pixel, the first two moments of the colour the temporal kernel accumulates
+// over the taps of the (2 R + 1)^2 window that are similar to the centre -- the same material
+// (and bounce count, PATH), and on a hit a depth within depth_tol of the centre's and a normal
+// with n(q) . n(p) >= normal_min -- taken about the centre's colour as k_svgf_estimate takes its:
+// exactly 0 variance on a constant window.  The tile and its halo of R pixels are staged in LDS
+// once per staged pixel as (c.rgb, bits(m)) and (n.xyz, z), PATH: and k; the demodulating
+// divisions are made there, not once per tap.  (16 + 2 R)^2 x 32 B (PATH: 36 B): 17.4 KB at most.
+// Halo pixels outside the frame are zero-filled and excluded by the in-frame predicate.  Fewer than
+// four taps give no box: lo = -inf, hi = +inf.
+template <int R, bool PATH>
+__global__ __launch_bounds__(256) void k_clip_box(ClipBoxArgs a) {
+    constexpr int T = 16 + 2 * R;
+    __shared__ LdsF4 sc_[T * T];
+    __shared__ LdsF4 sg_[T * T];
+    __shared__ int sk[PATH ? T * T : 1];
+    TPT_LDS LdsF4* sc = (TPT_LDS LdsF4*)sc_;
+    TPT_LDS LdsF4* sg = (TPT_LDS LdsF4*)sg_;
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int x0 = (int)blockIdx.x * 16 - R, y0 = (int)blockIdx.y * 16 - R;
+    // Two rounds of 256 staged pixels (T * T <= 484).  The loads of both are issued before the first is
+    // used: a staged pixel outside the frame, or past the tile, reads pixel 0 and is not kept, so no
+    // load waits behind a branch (the second round, which fills a quarter of the lanes at R = 1,
+    // otherwise starts only after the first round's LDS stores).
+    constexpr int ROUNDS = (T * T + 255) / 256;
+    static_assert(ROUNDS == 2, "k_clip_box stages its tile in two rounds");
+    bool in[ROUNDS];
+    V3 rad[ROUNDS], alb[ROUNDS], nrm[ROUNDS];
+    float z[ROUNDS];
+    int m[ROUNDS], k[ROUNDS];
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+        const int i = tid + 256 * r;
+        const int gx = x0 + i % T, gy = y0 + i / T;
+        in[r] = i < T * T && gx >= 0 && gx < a.width && gy >= 0 && gy < a.height;
+        const size_t q = in[r] ? (size_t)gy * (size_t)a.width + (size_t)gx : 0;
+        rad[r] = v3(a.radiance_in[3 * q], a.radiance_in[3 * q + 1], a.radiance_in[3 * q + 2]);
+        alb[r] = v3(1.0f, 1.0f, 1.0f);
+        if (a.demodulate) alb[r] = v3(a.albedo[3 * q], a.albedo[3 * q + 1], a.albedo[3 * q + 2]);
+        nrm[r] = v3(a.normal[3 * q], a.normal[3 * q + 1], a.normal[3 * q + 2]);
+        z[r] = a.depth[q];
+        m[r] = a.material[q];
+        k[r] = PATH ? a.bounces[q] : 0;
+    }
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+        const int i = tid + 256 * r;
+        if (i >= T * T) continue;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g = c;
+        if (in[r]) {
+            V3 cc = rad[r];
+            if (a.demodulate)   // k_temporal's arithmetic
+                cc = v3(cc.x / albedo_floor(alb[r].x), cc.y / albedo_floor(alb[r].y), cc.z / albedo_floor(alb[r].z));
+            c = make_float4(cc.x, cc.y, cc.z, __int_as_float(m[r]));
+            g = make_float4(nrm[r].x, nrm[r].y, nrm[r].z, z[r]);
+        }
+        lds_put(sc + i, c);
+        lds_put(sg + i, g);
+        if (PATH) sk[i] = in[r] ? k[r] : 0;
+    }
+    __syncthreads();
+    const int x = (int)blockIdx.x * 16 + tx, y = (int)blockIdx.y * 16 + ty;
+    const bool inside = x < a.width && y < a.height;
+    bool boxed = false;
+    if (inside) {
+        const int c0 = (ty + R) * T + tx + R;
+        const float4 cp = lds_f4(sc + c0), gp = lds_f4(sg + c0);
+        const int mp = __float_as_int(cp.w);
+        const int kp = PATH ? sk[c0] : 0;
+        const bool hit = mp >= 0;
+        const float ztol = a.depth_tol * gp.w;
+        float n = 0.0f;
+        float s1x = 0.0f, s1y = 0.0f, s1z = 0.0f, s2x = 0.0f, s2y = 0.0f, s2z = 0.0f;
+#pragma unroll
+        for (int dy = -R; dy <= R; ++dy) {
+            const bool row_in = y + dy >= 0 && y + dy < a.height;
+#pragma unroll
+            for (int dx = -R; dx <= R; ++dx) {
+                const int q = c0 + dy * T + dx;
+                const float4 cq = lds_f4(sc + q), gq = lds_f4(sg + q);
+                bool ok = row_in && x + dx >= 0 && x + dx < a.width && __float_as_int(cq.w) == mp;
+                if (PATH) ok = ok && sk[q] == kp;
+                if (hit) ok = ok && fabsf(gq.w - gp.w) <= ztol && (gq.x * gp.x + gq.y * gp.y) + gq.z * gp.z >= a.normal_min;
+                if (dx == 0 && dy == 0) ok = true;   // the centre always counts
+                if (!ok) continue;
+                const float ex = cq.x - cp.x, ey = cq.y - cp.y, ez = cq.z - cp.z;
+                n += 1.0f;
+                s1x += ex;
+                s1y += ey;
+                s1z += ez;
+                s2x += ex * ex;
+                s2y += ey * ey;
+                s2z += ez * ez;
+            }
+        }
+        float4 lo = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), n);
+        float4 hi = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), 0.0f);
+        boxed = n >= 4.0f;
+        if (boxed) {
+            const float mx = s1x / n, my = s1y / n, mz = s1z / n;
+            const float gx = a.gamma * fsqrt(fmaxf(s2x / n - mx * mx, 0.0f));
+            const float gy = a.gamma * fsqrt(fmaxf(s2y / n - my * my, 0.0f));
+            const float gz = a.gamma * fsqrt(fmaxf(s2z / n - mz * mz, 0.0f));
+            const float ux = cp.x + mx, uy = cp.y + my, uz = cp.z + mz;
+            lo = make_float4(ux - gx, uy - gy, uz - gz, n);
+            hi = make_float4(ux + gx, uy + gy, uz + gz, 0.0f);
+        }
+        const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
+        a.lo[p] = lo;
+        a.hi[p] = hi;
+    }
+    spread_count(a.boxed, tid, boxed);   // the statistic
+}
+
+template <int R>
+static hipError_t launch_clip_box_r(const ClipBoxArgs& a, hipStream_t s) {
+    if (a.bounces) hipLaunchKernelGGL((k_clip_box<R, true>), tile_grid(a.width, a.height), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_clip_box<R, false>), tile_grid(a.width, a.height), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_clip_box(const ClipBoxArgs& a, hipStream_t s) {
+    switch (a.radius) {
+        case 1: return launch_clip_box_r<1>(a, s);
+        case 2: return launch_clip_box_r<2>(a, s);
+        case 3: return launch_clip_box_r<3>(a, s);
+        default: return hipErrorInvalidValue;   // (tpt_history_set_clip refuses every other radius)
+    }
+}
+
+hipError_t launch_temporal_clip(const TemporalArgs& a, const ClipArgs& cl, hipStream_t s) {
+    return launch_tiles_or_rows(a.tiles != 0, k_temporal_clip<true>, 0, k_temporal_clip<false>, a.width, a.height, s, a, cl);
+}
+hipError_t launch_temporal_motion_clip(const TemporalArgs& a, const MotionArgs& mo, const ClipArgs& cl, hipStream_t s) {
+    return launch_tiles_or_rows(a.tiles != 0, k_temporal_motion_clip<true>, 0, k_temporal_motion_clip<false>, a.width, a.height,
+                                s, a, mo, cl);
+}
+hipError_t launch_temporal_path_clip(const TemporalArgs& a, const TemporalPathArgs& pa, const ClipArgs& cl, hipStream_t s) {
+    return launch_tiles_or_rows(a.tiles != 0, k_temporal_path_clip<true>, 0, k_temporal_path_clip<false>, a.width, a.height, s,
+                                a, pa, cl);
+}
+hipError_t launch_temporal_deform_clip(const TemporalArgs& a, const DeformArgs& de, const ClipArgs& cl, hipStream_t s) {
+    return launch_tiles_or_rows(a.tiles != 0, k_temporal_deform_clip<true>, 0, k_temporal_deform_clip<false>, a.width, a.height,
+                                s, a, de, cl);
+}
 
 hipError_t launch_temporal_motion(const TemporalArgs& a, const MotionArgs& mo, hipStream_t s) {
     return launch_tiles_or_rows(a.tiles != 0, k_temporal_motion<true>, 0, k_temporal_motion<false>, a.width, a.height, s, a, mo);

@@ -1,7 +1,7 @@
 // temporal_kernel.hpp -- the text of k_temporal, included by post.hip once as it is, once with
 // TPT_TEMPORAL_MOTION as k_temporal_motion, once with TPT_TEMPORAL_PATH as k_temporal_path and
-// once with TPT_TEMPORAL_DEFORM as k_temporal_deform.  No include guard: it is meant to be read
-// four times.
+// once with TPT_TEMPORAL_DEFORM as k_temporal_deform, and each of those once more with
+// TPT_TEMPORAL_CLIP.  No include guard: it is meant to be read eight times.
 
 // One lane per pixel, one launch per frame.  The lane reads its pixel of the caller's
 // planes (3-float planes directly: a pack step would write and read them once more),
@@ -40,8 +40,23 @@
 // arithmetic, geometry_queries.h:65-86, without its range tests) are applied to the snapshot's
 // corners: X' is where that point of that triangle was, ne the normal it had.  `mo` is DeformArgs
 // here: the face plane and motion_out go by the names the motion variant's blocks use.
+//
+// TPT_TEMPORAL_CLIP (k_temporal_clip, k_temporal_motion_clip, k_temporal_path_clip,
+// k_temporal_deform_clip; DESIGN.md section 5 "History clipping"): each of the four again, with
+// one more argument.  The lane reads its pixel of k_clip_box's two planes with its first loads and,
+// where it is reprojected, clamps the gathered history colour to the box before the blend; a
+// history that the clamp moved is capped at clip_history frames and its luminance moments are
+// shifted to the clamped colour's luminance at their variance.
 template <bool TILES>
-#if TPT_TEMPORAL_DEFORM
+#if TPT_TEMPORAL_CLIP && TPT_TEMPORAL_DEFORM
+__global__ __launch_bounds__(256) void k_temporal_deform_clip(TemporalArgs a, DeformArgs mo, ClipArgs cl) {
+#elif TPT_TEMPORAL_CLIP && TPT_TEMPORAL_MOTION
+__global__ __launch_bounds__(256) void k_temporal_motion_clip(TemporalArgs a, MotionArgs mo, ClipArgs cl) {
+#elif TPT_TEMPORAL_CLIP && TPT_TEMPORAL_PATH
+__global__ __launch_bounds__(256) void k_temporal_path_clip(TemporalArgs a, TemporalPathArgs pa, ClipArgs cl) {
+#elif TPT_TEMPORAL_CLIP
+__global__ __launch_bounds__(256) void k_temporal_clip(TemporalArgs a, ClipArgs cl) {
+#elif TPT_TEMPORAL_DEFORM
 __global__ __launch_bounds__(256) void k_temporal_deform(TemporalArgs a, DeformArgs mo) {
 #elif TPT_TEMPORAL_MOTION
 __global__ __launch_bounds__(256) void k_temporal_motion(TemporalArgs a, MotionArgs mo) {
@@ -62,11 +77,17 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
         y = (int)blockIdx.y * 4 + (int)threadIdx.y;
     }
     bool reproj = false;
+#if TPT_TEMPORAL_CLIP
+    bool clipped = false;
+#endif
     if (x < a.width && y < a.height) {
         const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
         // what the reprojection needs first, so that the taps' loads start early
         const float z = a.depth[p];
         const int m = a.material[p];
+#if TPT_TEMPORAL_CLIP
+        const float4 blo = cl.lo[p], bhi = cl.hi[p];       // the box: own-pixel loads, in flight with the first
+#endif
 #if TPT_TEMPORAL_PATH
         const int kb = pa.bounces[p];
         V3 pe = v3(0.0f, 0.0f, 0.0f);                      // where the path ended (k > 0 only)
@@ -272,6 +293,19 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
         float N = 1.0f, m1 = L, m2 = L * L;
         V3 C = c, out = in;
         if (reproj) {
+#if TPT_TEMPORAL_CLIP
+            // (fmaxf / fminf return the other operand for a NaN one: a NaN edge leaves the value as it is)
+            const V3 hcl = v3(fminf(fmaxf(hc.x, blo.x), bhi.x), fminf(fmaxf(hc.y, blo.y), bhi.y),
+                              fminf(fmaxf(hc.z, blo.z), bhi.z));
+            clipped = hcl.x != hc.x || hcl.y != hc.y || hcl.z != hc.z;
+            if (clipped) {
+                hc = make_float4(hcl.x, hcl.y, hcl.z, fminf(hc.w, cl.clip_history));
+                // the accumulated variance moves with the mean
+                const float v = fmaxf(hm2 - hm1 * hm1, 0.0f);
+                hm1 = (0.2126f * hcl.x + 0.7152f * hcl.y) + 0.0722f * hcl.z;
+                hm2 = v + hm1 * hm1;
+            }
+#endif
             N = fminf(hc.w + 1.0f, a.max_history);
             const float k = fmaxf(a.alpha, 1.0f / N);
             C = v3(hc.x + k * (c.x - hc.x), hc.y + k * (c.y - hc.y), hc.z + k * (c.z - hc.z));
@@ -303,5 +337,8 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
         if (a.bgra) write_bgr(a.bgra, a.width, a.height, (size_t)x, (size_t)y, out);
     }
     spread_count(a.reprojected, tid, reproj);   // the statistic
+#if TPT_TEMPORAL_CLIP
+    spread_count(cl.clipped, tid, clipped);
+#endif
 }
 

@@ -9,6 +9,7 @@
 //              [--temporal] [--yaw DEG] [--svgf [iterations]] [--aov-path [bounces]]
 //              [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP] [--refit]
 //              [--adaptive TARGET [--min-spp N] [--max-spp N]]
+//              [--clip [GAMMA]] [--clip-radius R] [--clip-history N]
 // --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
 // <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
 // a-trous filter of the written frame (tpt_denoise, the hosts' defaults; with
@@ -40,6 +41,12 @@
 // AMP sin(6 y_obj + frame) in frame `frame` (a deformation no matrix describes), under the same
 // conditions as --move: every frame sets the vertices (tpt_scene_set_vertices), rebuilds, renders,
 // and goes through tpt_temporal_deform, which follows the deformed mesh (and --move / --spin too).
+// --clip [GAMMA] (with --temporal or --temporal-path) turns history clipping on
+// (tpt_history_set_clip, the hosts' defaults): the reprojected history is clamped to mean +- GAMMA
+// standard deviations of the frame's colours around each pixel, so that a moved object's shadow
+// and its reflections stop lagging; --clip-radius R (1..3) and --clip-history N set the window and
+// the cap on a clipped pixel's history length.  Each frame prints its reprojected and clipped
+// pixel counts on stderr.
 // --refit (with --move / --spin / --wave): the frames after the first refit the BVH
 // (tpt_scene_refit) instead of rebuilding it, and each prints its tree cost against the built
 // one and the refit's device time on stderr.
@@ -103,7 +110,8 @@ const char* kUsage =
     "[--env file.jpg|file.ppm | --sky] [--out prefix] [--device i] [--frames F [--progressive]] "
     "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]] "
     "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP] [--refit] [--truck DX DY DZ] "
-    "[--temporal-path [bounces]] [--adaptive TARGET [--min-spp N] [--max-spp N]]\n";
+    "[--temporal-path [bounces]] [--adaptive TARGET [--min-spp N] [--max-spp N]] "
+    "[--clip [GAMMA]] [--clip-radius R] [--clip-history N]\n";
 
 // The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
 tpt::Camera yawed(const tpt::Camera& base, double deg) {
@@ -229,6 +237,8 @@ int main(int argc, char** argv) {
     std::vector<ObjectMotion> motions;   // --move / --spin, one entry per object named
     std::vector<ObjectWave> waves;       // --wave, one entry per option
     bool refit = false;                  // --refit: frames after the first refit instead of rebuilding
+    bool clip = false, clip_opts = false;   // --clip; --clip-radius or --clip-history given
+    tpt_clip_params clip_params = tpt::defaultClip();
     auto motion_of = [&](uint32_t object) -> ObjectMotion& {
         for (auto& om : motions)
             if (om.object == object) return om;
@@ -288,6 +298,13 @@ int main(int argc, char** argv) {
             waves.back().amp = std::stod(next());
         }
         else if (a == "--refit") refit = true;
+        else if (a == "--clip") {
+            clip = true;   // an optional gamma follows
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.'))
+                clip_params.gamma = std::stof(argv[++i]);
+        }
+        else if (a == "--clip-radius") { clip = clip_opts = true; clip_params.radius = std::stoi(next()); }
+        else if (a == "--clip-history") { clip = clip_opts = true; clip_params.max_history = std::stoi(next()); }
         else if (a == "--denoise") {
             denoise = true;   // an optional iteration count follows
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dn_iterations = std::stoi(argv[++i]);
@@ -324,6 +341,10 @@ int main(int argc, char** argv) {
     }
     if (refit && motions.empty() && waves.empty()) {   // nothing moves: nothing to refit
         std::fprintf(stderr, "--refit needs --move, --spin or --wave\n");
+        return 2;
+    }
+    if (clip && !temporal) {
+        std::fprintf(stderr, "--clip, --clip-radius and --clip-history need --temporal or --temporal-path\n");
         return 2;
     }
     if (temporal && progressive) {   // progressive is already the exact accumulation of an unmoving camera
@@ -372,6 +393,15 @@ int main(int argc, char** argv) {
         tpt::AOV g;
         if (temporal) {
             tpt::History hist(d, W, H);
+            if (clip) hist.setClip(&clip_params);
+            tpt_temporal_stats ts{};
+            auto report = [&](int i) {   // (the clip's figures, where it is on)
+                if (!clip) return;
+                const tpt_clip_stats cs = hist.clipStats();
+                std::fprintf(stderr, "frame %d: reprojected %llu, clipped %llu, boxed %llu, box %.3f ms\n", i,
+                             (unsigned long long)ts.reprojected, (unsigned long long)cs.clipped,
+                             (unsigned long long)cs.boxed, cs.box_ms);
+            };
             acc.resize((size_t)W * H * 3);
             var.resize((size_t)W * H);
             len.resize((size_t)W * H);
@@ -402,19 +432,21 @@ int main(int argc, char** argv) {
                     std::vector<int32_t> bounces;
                     std::vector<float> points;
                     g = pt.renderAOVPath(d, cam, path_bounces, &bounces, nullptr, &points);
-                    pt.temporalPath(hist, cam, f.radiance.data(), g.view(), bounces.data(), points.data(), acc.data(),
-                                    var.data(), len.data(), fb.data());
+                    ts = pt.temporalPath(hist, cam, f.radiance.data(), g.view(), bounces.data(), points.data(), acc.data(),
+                                         var.data(), len.data(), fb.data());
+                    report(i);
                     continue;
                 }
                 g = pt.renderAOV(d, cam);
                 if (!waves.empty())
-                    pt.temporalDeform(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(),
-                                      nullptr, fb.data());
+                    ts = pt.temporalDeform(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(),
+                                           nullptr, fb.data());
                 else if (motions.empty())
-                    pt.temporal(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(), fb.data());
+                    ts = pt.temporal(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(), fb.data());
                 else
-                    pt.temporalMotion(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(),
-                                      nullptr, fb.data());
+                    ts = pt.temporalMotion(hist, cam, f.radiance.data(), g.view(), acc.data(), var.data(), len.data(),
+                                           nullptr, fb.data());
+                report(i);
             }
             write_pfm(out + "_temporal.pfm", acc, W, H, 3);
             write_ppm(out + "_temporal.ppm", fb, W, H);
