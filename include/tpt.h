@@ -776,6 +776,55 @@ tpt_status tpt_denoise_svgf(tpt_scene* scene, int32_t width, int32_t height, con
                             const tpt_svgf_params* params, float* radiance_out, float* variance_out,
                             uint8_t* bgra_out, tpt_svgf_stats* stats);
 
+#define TPT_UPSAMPLE_DEMODULATE 0x1   /* interpolate radiance / max(albedo, 1e-3), multiply by the full-size albedo */
+
+typedef struct {
+    float   sigma_normal;    /* > 0 */
+    float   sigma_depth;     /* > 0, relative */
+    int32_t flags;           /* TPT_UPSAMPLE_* */
+} tpt_upsample_params;
+
+typedef struct {
+    double   kernel_ms;      /* the kernel's duration (HIP events) */
+    uint64_t fallback;       /* full-size pixels without an accepted tap */
+} tpt_upsample_stats;
+
+/* Guided (joint bilateral) upsampling of a low-size radiance frame to the full size, by the
+ * feature buffers of both sizes rendered from one camera (tpt_render at low_width x low_height
+ * covers the same sensor as at width x height).  The pass is defined in DESIGN.md section 5
+ * "Guided upsampling".  A full-size pixel takes the up to 2x2 low pixels of its bilinear
+ * footprint (found in integers: the tap set is exact) that hold its own material id, each
+ * weighted by its bilinear weight times tpt_denoise's normal and depth factors,
+ * exp(-|dn|^2 / sigma_normal^2) exp(-dz^2 / (sigma_depth^2 max(z(p)^2, 1e-12))), relative to
+ * the most similar of them, so that at least one weight survives; the output is their weighted
+ * mean.  A pixel none of whose taps holds its material falls back to the plain bilinear mean of
+ * the radiance as given (never demodulated) and is counted in stats->fallback.  With equal sizes,
+ * the same guides and no flag the output is the input bit for bit (a -0 comes out as +0); a
+ * constant low frame gives that constant bit for bit.
+ *   radiance_low: low_width*low_height*3 floats, row 0 = bottom.
+ *   guides_low / guides: the feature buffers at the low and at the full size: normal, depth and
+ *     material are required, albedo only with TPT_UPSAMPLE_DEMODULATE; face is ignored.
+ *     tpt_render_aov_path's buffers are taken unchanged, as the filters take them.
+ *   radiance_out: nullable, width*height*3 floats.  bgra_out: nullable, as tpt_denoise's.  At
+ *     least one of the two.
+ * Inputs and outputs may be host or device memory (detected per pointer; tpt_render's stream
+ * rule for device memory); all work is complete when the call returns.  `scene` supplies the
+ * device, the stream and the scratch; it need not be built.  The call keeps no plane per pixel:
+ * only host buffers are staged, in the buffers tpt_denoise and tpt_render_aov stage theirs in (up
+ * to 48 B per full-size and 44 B per low-size pixel), and 32 KiB of counters.  Deterministic: the
+ * only atomics are the integer counters of stats->fallback.  Non-finite input radiance is the
+ * caller's problem.
+ * TPT_ERR_INVALID_ARG (nothing is written): null scene / radiance_low / guides_low / guides /
+ * params, a missing normal, depth or material guide in either set, a missing albedo guide in
+ * either set under TPT_UPSAMPLE_DEMODULATE, a size <= 0, a low size larger than the full size, a
+ * side above 1,048,576, a sigma that is not > 0, an unknown flag, radiance_out and bgra_out both
+ * null. */
+tpt_status tpt_upsample(tpt_scene* scene, int32_t low_width, int32_t low_height,
+                        const float* radiance_low, const tpt_aov* guides_low,
+                        int32_t width, int32_t height, const tpt_aov* guides,
+                        const tpt_upsample_params* params,
+                        float* radiance_out, uint8_t* bgra_out, tpt_upsample_stats* stats);
+
 /* Introspection for tests: copy back the built BVH in the reference node
  * layout (bvh.cuh:52-58, 36 B/node, 2F-1 nodes) and the sorted Morton keys. */
 tpt_status tpt_scene_read_bvh(tpt_scene* scene, void* nodes36, int64_t* keys);

@@ -245,6 +245,26 @@ inline tpt_svgf_params defaultSVGF(int iterations = 5) {
     return p;
 }
 
+// The hosts' defaults of guided upsampling (PathTracer::upsample), chosen by the sweep of
+// tools/upsample_quality.py (DESIGN.md section 5 "Guided upsampling"), which started from
+// defaultDenoise's sigmas and kept sigma_normal
+inline tpt_upsample_params defaultUpsample() {
+    tpt_upsample_params p{};
+    p.sigma_normal = 0.3f;
+    p.sigma_depth = 0.2f;
+    p.flags = 0;
+    return p;
+}
+
+// The low frame size of an integer scale: ceil(width / scale) x ceil(height / scale)
+struct Size {
+    int width = 0, height = 0;
+};
+inline Size lowSize(int width, int height, int scale) {
+    if (width <= 0 || height <= 0 || scale <= 0) throw std::runtime_error("lowSize: width, height and scale must be > 0");
+    return Size{(width + scale - 1) / scale, (height + scale - 1) / scale};
+}
+
 // tpt_temporal's state across frames (tpt_history).  Declared after the
 // DeviceScene it was created from, so that it is destroyed first.
 class History {
@@ -490,6 +510,19 @@ public:
         tpt_svgf_stats st{};
         check(tpt_denoise_svgf(scene.handle(), m_width, m_height, radiance_in, &guides, variance, history_len, &params,
                                radiance_out, variance_out, framebuffer, &st));
+        return st;
+    }
+
+    // Guided upsampling (tpt_upsample) on the full-size tracer: radiance_low and guides_low are a
+    // render of this tracer's camera and its feature buffers at low_width x low_height (a tracer
+    // of that size: lowSize), guides the feature buffers at this tracer's size.  radiance_out and
+    // framebuffer are nullable, not both.  Pointers are host or device memory.
+    tpt_upsample_stats upsample(DeviceScene& scene, int low_width, int low_height, const float* radiance_low,
+                                const tpt_aov& guides_low, const tpt_aov& guides, float* radiance_out,
+                                uint8_t* framebuffer = nullptr, const tpt_upsample_params& params = defaultUpsample()) {
+        tpt_upsample_stats st{};
+        check(tpt_upsample(scene.handle(), low_width, low_height, radiance_low, &guides_low, m_width, m_height, &guides,
+                           &params, radiance_out, framebuffer, &st));
         return st;
     }
 

@@ -24,7 +24,8 @@ from ._lib import TPTError, build_identity, check, lib
 
 __all__ = ["Camera", "Scene", "DeviceScene", "BVH", "EnvLight", "PathTracer", "Frame", "TPTError",
            "procedural_sky", "version", "device_count", "build_identity", "NODE_DTYPE", "DENOISE_DEFAULTS",
-           "History", "TEMPORAL_DEFAULTS", "TEMPORAL_PATH_DEFAULTS", "CLIP_DEFAULTS", "motion_matrices", "ADAPTIVE_DEFAULTS"]
+           "History", "TEMPORAL_DEFAULTS", "TEMPORAL_PATH_DEFAULTS", "CLIP_DEFAULTS", "motion_matrices", "ADAPTIVE_DEFAULTS",
+           "UPSAMPLE_DEFAULTS", "low_size"]
 
 # BVHNode (include/bvh.cuh:52-58): parent, info{left,right | fid,placeHolder}, box
 NODE_DTYPE = np.dtype([("parent", "<u4"), ("a", "<i4"), ("b", "<i4"), ("bmin", "<f4", 3), ("bmax", "<f4", 3)])
@@ -608,6 +609,20 @@ SVGF_DEFAULTS = {"iterations": 5, "sigma_lum": 0.5, "sigma_normal": 0.3, "sigma_
                  "demodulate": True}
 
 
+# Guided upsampling (PathTracer.upsample): chosen by the sweep of tools/upsample_quality.py (DESIGN.md
+# section 5 "Guided upsampling"), which started from DENOISE_DEFAULTS' sigmas: sigma_depth 0.2 has the
+# lower error than 0.05 in 7 of its 8 columns, sigma_normal and demodulation move nothing on box
+UPSAMPLE_DEFAULTS = {"sigma_normal": 0.3, "sigma_depth": 0.2, "demodulate": False}
+
+
+def low_size(width: int, height: int, scale: int):
+    """The low frame size of an integer scale: (ceil(width / scale), ceil(height / scale))."""
+    width, height, scale = int(width), int(height), int(scale)
+    if width <= 0 or height <= 0 or scale <= 0:
+        raise ValueError(f"low_size: width, height and scale must be > 0, got {width}, {height}, {scale}")
+    return (width + scale - 1) // scale, (height + scale - 1) // scale
+
+
 class History:
     """tpt_temporal's state across frames (tpt_history): the accumulated colour, the
     history length, the luminance moments and the feature buffers of the previous
@@ -1010,6 +1025,47 @@ class PathTracer:
         check(lib().tpt_denoise_svgf(d_scene.handle, W, H, _addr(radiance), C.byref(g), _addr(variance),
                                      _addr(history_len), C.byref(p), _addr(out), _addr(variance_out),
                                      _addr(framebuffer), C.byref(st)))
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out
+
+    def upsample(self, d_scene: DeviceScene, radiance_low, aov_low, aov, *,
+                 sigma_normal: float = UPSAMPLE_DEFAULTS["sigma_normal"],
+                 sigma_depth: float = UPSAMPLE_DEFAULTS["sigma_depth"],
+                 demodulate: bool = UPSAMPLE_DEFAULTS["demodulate"], out=None, framebuffer=None, stats=None,
+                 low_size=None):
+        """Guided upsampling (tpt_upsample, DESIGN.md section 5 "Guided upsampling") of
+        `radiance_low` [hl, wl, 3], a render of this tracer's camera at a smaller size, to this
+        tracer's frame size: aov_low are the feature buffers at the low size, aov those at the
+        full size (renderAOV or renderAOVPath of a tracer of each size) -- normal, depth and
+        material, and albedo with demodulate.  The low size is radiance_low's shape; low_size =
+        (wl, hl) names it for a raw device pointer.  out: the full-size radiance's buffer (None:
+        a new numpy array); framebuffer: optional [H, W, 4] uint8 as doTrace writes it.  Buffers
+        are numpy arrays or torch CUDA tensors.  Returns `out`; stats: a dict that receives
+        kernel_ms and fallback (the pixels no tap of which holds their material: plain bilinear)."""
+        W, H = self.m_width, self.m_height
+        if low_size is None:
+            shape = tuple(getattr(radiance_low, "shape", ()))
+            if len(shape) != 3 or shape[2] != 3:
+                raise ValueError(f"radiance_low: need [hl, wl, 3] (or low_size=(wl, hl)), got shape {shape}")
+            low_size = (shape[1], shape[0])
+        wl, hl = int(low_size[0]), int(low_size[1])
+        if not (1 <= wl <= W and 1 <= hl <= H):
+            raise ValueError(f"the low size {wl} x {hl} must be within 1 x 1 .. {W} x {H}")
+        _check_plane("radiance", radiance_low, wl, hl)
+        keys = (("albedo",) if demodulate else ()) + ("normal", "depth", "material")
+        gl = _take_guides(aov_low, keys, wl, hl)
+        g = _take_guides(aov, keys, W, H)
+        if out is None:
+            out = np.zeros((H, W, 3), np.float32)
+        _check_plane("radiance", out, W, H)
+        if framebuffer is not None:
+            _check_plane("framebuffer", framebuffer, W, H)
+        p = _lib.UpsampleParams(float(sigma_normal), float(sigma_depth),
+                                _lib.UPSAMPLE_DEMODULATE if demodulate else 0)
+        st = _lib.UpsampleStats()
+        check(lib().tpt_upsample(d_scene.handle, wl, hl, _addr(radiance_low), C.byref(gl), W, H, C.byref(g),
+                                 C.byref(p), _addr(out), _addr(framebuffer), C.byref(st)))
         if stats is not None:
             stats.update(st.as_dict())
         return out

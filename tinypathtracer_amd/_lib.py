@@ -29,6 +29,7 @@ TEMPORAL_TILES = 0x2
 MOTION_TRACKED, MOTION_IDENTITY, MOTION_UNTRACKED = 0, 1, 2   # tpt_motion_matrices' flags
 SVGF_DEMODULATE = 0x1
 SVGF_DIRECT = 0x2
+UPSAMPLE_DEMODULATE = 0x1
 
 
 class Material(C.Structure):
@@ -174,6 +175,17 @@ class ClipStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class UpsampleParams(C.Structure):
+    _fields_ = [("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_int32)]
+
+
+class UpsampleStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("fallback", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # (name, restype, argtypes) -- every symbol include/tpt.h declares
 SIGNATURES = [
     ("tpt_version", C.c_char_p, []),
@@ -235,6 +247,9 @@ SIGNATURES = [
     ("tpt_denoise_svgf", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Aov), C.c_void_p,
                                    C.c_void_p, C.POINTER(SvgfParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(SvgfStats)]),
+    ("tpt_upsample", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Aov), C.c_int32, C.c_int32,
+                               C.POINTER(Aov), C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p,
+                               C.POINTER(UpsampleStats)]),
     ("tpt_scene_read_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_scene_read_world", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_debug_rng_init", C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),
@@ -300,7 +315,8 @@ def lib():
         # predates the newest debug entry points, tpt_render_adaptive or the refit entry points
         # (an A/B against the build before them); the product library must export all
         older = bool(os.environ.get("TPT_LIB"))
-        _NEWEST = ("tpt_render_adaptive", "tpt_scene_refit", "tpt_scene_read_wide", "tpt_wide_tree_levels")
+        _NEWEST = ("tpt_render_adaptive", "tpt_scene_refit", "tpt_scene_read_wide", "tpt_wide_tree_levels",
+                   "tpt_upsample")
         for name, res, args in SIGNATURES:
             if older and (name.startswith("tpt_debug_") or name in _NEWEST) and not hasattr(L, name):
                 continue

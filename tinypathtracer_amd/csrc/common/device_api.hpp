@@ -529,6 +529,31 @@ hipError_t launch_svgf_estimate(const SvgfArgs& a, hipStream_t s);
 hipError_t launch_svgf_filter(const SvgfFilterArgs& a, bool use_lds, hipStream_t s);
 hipError_t launch_svgf_resolve(const SvgfArgs& a, hipStream_t s);
 
+// post.hip: guided upsampling (tpt_upsample; DESIGN.md section 5 "Guided upsampling"): the low-size
+// frame and its guides are gathered (four taps per full-size pixel), the full-size guides read and
+// the outputs written at the lane's own pixel.  Device pointers, row 0 = bottom.
+struct UpsampleArgs {
+    const float* radiance_low;           // wl*hl*3
+    const float* albedo_low;             // wl*hl*3 (read when demodulate)
+    const float* normal_low;             // wl*hl*3
+    const float* depth_low;              // wl*hl
+    const int32_t* material_low;         // wl*hl
+    const float* albedo;                 // W*H*3 (read when demodulate)
+    const float* normal;                 // W*H*3
+    const float* depth;                  // W*H
+    const int32_t* material;             // W*H
+    float* radiance_out;                 // nullable, W*H*3
+    uint8_t* bgra;                       // nullable, W*H*4, row 0 = top, alpha untouched
+    unsigned long long* fallback;        // kTemporalSlots counters, kTemporalSlotStride words apart (zeroed by the
+                                         //   caller): their sum = pixels without an accepted tap
+    int32_t low_width, low_height;       // 1 <= wl <= W, 1 <= hl <= H
+    int32_t width, height;
+    int32_t demodulate;
+    float inv_sn2;                       // 1 / sigma_n^2
+    float sz2;                           // sigma_z^2
+};
+hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t s);
+
 }  // namespace tpt
 
 // The tolerance-mode build of trace.hip (TPT_FLAG_FAST; Makefile trace_fast.hip.o):

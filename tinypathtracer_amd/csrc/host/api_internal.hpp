@@ -430,6 +430,12 @@ struct tpt_scene {
     DevBuf<int32_t> ap_bounces;
     SpreadCounters ap_count;
     DevBuf<float> ap_points;                // tpt_render_aov_path_points: the staging of the terminal points
+    // tpt_upsample: no plane of its own.  Host buffers are staged in tpt_denoise's buffers (the
+    // full-size guides and outputs, the material in aov_i[1]) and tpt_render_aov's (the low-size
+    // guides); of its own the staging of the low-size radiance and the counters of
+    // UpsampleArgs::fallback
+    DevBuf<float> up_rad;
+    SpreadCounters up_count;
     // tpt_render_adaptive (adaptive.hip): the sums' snapshot at half a tile's samples (3 planes, 12 B
     // per pixel), the active tiles' list, the tiles' error estimates and sample counts, with pinned
     // host copies.  Kept between calls.

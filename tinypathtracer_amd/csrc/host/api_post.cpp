@@ -1,6 +1,6 @@
 // api_post.cpp -- the post-pass entry points of the C-ABI (post.hip): tpt_render_aov, tpt_render_aov_path,
 // tpt_render_aov_path_points, tpt_denoise, tpt_history_* (tpt_history_set_clip too), tpt_temporal, tpt_temporal_motion, tpt_temporal_path,
-// tpt_temporal_deform and tpt_denoise_svgf.  Each takes its buffers from either
+// tpt_temporal_deform, tpt_denoise_svgf and tpt_upsample.  Each takes its buffers from either
 // side: host buffers go through the device staging the scene / history keeps
 // (api_internal.hpp Staging).
 #include <cmath>
@@ -658,6 +658,73 @@ tpt_status tpt_denoise_svgf(tpt_scene* s, int32_t W, int32_t H, const float* rad
         HIP_OR_FAIL(elapsed_ms(s->ev[2], s->ev[3], &stats->filter_ms));
         HIP_OR_FAIL(elapsed_ms(s->ev[3], s->ev[4], &stats->resolve_ms));
         stats->estimated = s->sv_count.sum(0);
+    }
+    return TPT_OK;
+}
+
+// Guided upsampling (post.hip k_upsample; DESIGN.md section 5 "Guided upsampling"): one launch,
+// no scratch plane.  Host buffers are staged in the scene's buffers: the full-size guides and the
+// outputs in tpt_denoise's (the material in aov_i[1]), the low-size guides in tpt_render_aov's,
+// the low-size radiance in up_rad.
+tpt_status tpt_upsample(tpt_scene* s, int32_t wl, int32_t hl, const float* radiance_low, const tpt_aov* guides_low,
+                        int32_t W, int32_t H, const tpt_aov* guides, const tpt_upsample_params* p,
+                        float* radiance_out, uint8_t* bgra_out, tpt_upsample_stats* stats) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (!radiance_low) return fail(TPT_ERR_INVALID_ARG, "null radiance_low");
+    if (!guides_low || !guides) return fail(TPT_ERR_INVALID_ARG, "null guides");
+    if (!p) return fail(TPT_ERR_INVALID_ARG, "null params");
+    if (p->flags & ~TPT_UPSAMPLE_DEMODULATE) return fail(TPT_ERR_INVALID_ARG, "unknown upsample flags");
+    const bool demod = (p->flags & TPT_UPSAMPLE_DEMODULATE) != 0;
+    for (const tpt_aov* g : {guides_low, guides}) {
+        if (!g->normal || !g->depth || !g->material)
+            return fail(TPT_ERR_INVALID_ARG, "upsampling needs the normal, depth and material guides at both sizes");
+        if (demod && !g->albedo)
+            return fail(TPT_ERR_INVALID_ARG, "TPT_UPSAMPLE_DEMODULATE needs the albedo guides at both sizes");
+    }
+    constexpr int32_t kMaxSide = 1048576;   // tpt_render_adaptive's
+    if (wl <= 0 || hl <= 0 || W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size: every side must be > 0");
+    if (W > kMaxSide || H > kMaxSide) return fail(TPT_ERR_INVALID_ARG, "bad frame size: a side above 1048576");
+    if (wl > W || hl > H) return fail(TPT_ERR_INVALID_ARG, "the low size is larger than the full size");
+    if (!(p->sigma_normal > 0.0f) || !(p->sigma_depth > 0.0f))
+        return fail(TPT_ERR_INVALID_ARG, "sigma_normal and sigma_depth must be > 0");
+    if (!radiance_out && !bgra_out) return fail(TPT_ERR_INVALID_ARG, "no output buffer: radiance_out and bgra_out are null");
+    DeviceGuard g(s->device);
+    hipStream_t st = s->stream;
+    const size_t npl = (size_t)wl * (size_t)hl, npix = (size_t)W * (size_t)H;
+    HIP_OR_FAIL(s->up_count.alloc(1));
+    const FilterConsts fc = filter_consts(p->sigma_normal, p->sigma_depth, false);
+    tpt::UpsampleArgs a{};
+    a.low_width = wl;
+    a.low_height = hl;
+    a.width = W;
+    a.height = H;
+    a.demodulate = demod ? 1 : 0;
+    a.inv_sn2 = fc.inv_sn2;
+    a.sz2 = fc.sz2;
+    a.fallback = s->up_count.set(0);
+    Staging sg(st);
+    HIP_OR_FAIL(sg.in(s->up_rad, radiance_low, 3 * npl, &a.radiance_low));
+    HIP_OR_FAIL(sg.in(s->aov_f3[0], demod ? guides_low->albedo : nullptr, 3 * npl, &a.albedo_low));
+    HIP_OR_FAIL(sg.in(s->aov_f3[1], guides_low->normal, 3 * npl, &a.normal_low));
+    HIP_OR_FAIL(sg.in(s->aov_depth, guides_low->depth, npl, &a.depth_low));
+    HIP_OR_FAIL(sg.in(s->aov_i[0], guides_low->material, npl, &a.material_low));
+    HIP_OR_FAIL(sg.in(s->dn_f3[0], demod ? guides->albedo : nullptr, 3 * npix, &a.albedo));
+    HIP_OR_FAIL(sg.in(s->dn_f3[1], guides->normal, 3 * npix, &a.normal));
+    HIP_OR_FAIL(sg.in(s->dn_depth, guides->depth, npix, &a.depth));
+    HIP_OR_FAIL(sg.in(s->aov_i[1], guides->material, npix, &a.material));
+    HIP_OR_FAIL(sg.out(s->dn_rad, radiance_out, 3 * npix, &a.radiance_out));
+    // alpha is untouched: the caller's bytes go up first
+    HIP_OR_FAIL(sg.inout(s->dn_bgra, bgra_out, 4 * npix, &a.bgra));
+    HIP_OR_FAIL(s->up_count.zero(st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
+    HIP_OR_FAIL(tpt::launch_upsample(a, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
+    HIP_OR_FAIL(sg.finish());
+    HIP_OR_FAIL(s->up_count.fetch(st));
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    if (stats) {
+        HIP_OR_FAIL(elapsed_ms(s->ev[0], s->ev[1], &stats->kernel_ms));
+        stats->fallback = s->up_count.sum(0);
     }
     return TPT_OK;
 }

@@ -29,6 +29,8 @@
 //  * k_svgf_pack / k_svgf_estimate / k_svgf_atrous / k_svgf_atrous_lds /
 //    k_svgf_resolve: the variance-guided filter (tpt_denoise_svgf) on the same two
 //    planes, the variance in the colour plane's fourth component.
+//  * k_upsample: guided upsampling (tpt_upsample) of a low-size frame to the full size by the
+//    feature buffers of both sizes, one launch, no scratch plane.
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"   // trace_dev.hpp's env helpers, unused here
 #include "trace_dev.hpp"
 
@@ -873,5 +875,108 @@ hipError_t launch_svgf_filter(const SvgfFilterArgs& a, bool use_lds, hipStream_t
     return launch_filter_step(k_svgf_atrous_lds<1>, k_svgf_atrous_lds<2>, k_svgf_atrous, a, use_lds, s);
 }
 hipError_t launch_svgf_resolve(const SvgfArgs& a, hipStream_t s) { return launch_pixels(k_svgf_resolve, a, s); }
+
+// ---- guided upsampling (tpt_upsample; DESIGN.md section 5 "Guided upsampling" holds the definition) ----
+
+// One axis of a full-size pixel's footprint in the low frame, in integers: n = (2 x + 1) lo - full,
+// q0 = floor(n / 2 full), r = n - 2 full q0, f = r / 2 full.  n + 2 full > 0, so the floor is an
+// unsigned division of that.  q[0], q[1]: the two taps' coordinates, clamped; r == 0: the second
+// has the weight 0 and is no tap.
+struct UpAxis {
+    int q[2];
+    float f;
+    bool two;
+};
+__device__ __forceinline__ UpAxis up_axis(int x, int lo, int full) {
+    const unsigned long long d = 2ull * (unsigned long long)full;
+    const unsigned long long n = (2ull * (unsigned long long)x + 1ull) * (unsigned long long)lo + (unsigned long long)full;
+    const int q0 = (int)(n / d) - 1;   // -1 .. lo - 1
+    const unsigned long long r = n % d;
+    UpAxis ax;
+    ax.q[0] = q0 < 0 ? 0 : q0;
+    ax.q[1] = q0 + 1 > lo - 1 ? lo - 1 : q0 + 1;
+    ax.f = (float)r / (float)d;
+    ax.two = r != 0;
+    return ax;
+}
+
+// One lane per full-size pixel, a wave a 64-pixel row segment (block (64, 4)): its reads of the
+// full-size guides and its 12-B writes are contiguous.  The four taps' low-size planes are read
+// as they are (no pack step: at scale s each low pixel is a tap of about 4 s^2 lanes, nearly all
+// of them in the same or the neighbouring wave, so the gathers are L1 / L2 hits), every load of
+// a tap issued before the first is used, a tap of weight 0 included (its address is a clamped
+// neighbour's).  No LDS, no floating-point atomics.
+__global__ __launch_bounds__(256) void k_upsample(UpsampleArgs a) {
+    const int tid = (int)threadIdx.y * 64 + (int)threadIdx.x;
+    const int x = (int)blockIdx.x * 64 + (int)threadIdx.x, y = (int)blockIdx.y * 4 + (int)threadIdx.y;
+    bool fallback = false;
+    if (x < a.width && y < a.height) {
+        const size_t p = (size_t)y * (size_t)a.width + (size_t)x;
+        const UpAxis ax = up_axis(x, a.low_width, a.width), ay = up_axis(y, a.low_height, a.height);
+        const int mp = a.material[p];
+        const float4 gp = make_float4(a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2], a.depth[p]);
+        V3 albp = v3(1.0f, 1.0f, 1.0f);
+        if (a.demodulate) albp = v3(a.albedo[3 * p], a.albedo[3 * p + 1], a.albedo[3 * p + 2]);
+        V3 c[4], alb[4];
+        float4 g[4];
+        int m[4];
+        float b[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {   // (0,0), (1,0), (0,1), (1,1)
+            const int i = k & 1, j = k >> 1;
+            const size_t q = (size_t)ay.q[j] * (size_t)a.low_width + (size_t)ax.q[i];
+            c[k] = v3(a.radiance_low[3 * q], a.radiance_low[3 * q + 1], a.radiance_low[3 * q + 2]);
+            g[k] = make_float4(a.normal_low[3 * q], a.normal_low[3 * q + 1], a.normal_low[3 * q + 2], a.depth_low[q]);
+            m[k] = a.material_low[q];
+            alb[k] = v3(1.0f, 1.0f, 1.0f);
+            if (a.demodulate) alb[k] = v3(a.albedo_low[3 * q], a.albedo_low[3 * q + 1], a.albedo_low[3 * q + 2]);
+            // the bilinear weight; a tap of weight 0 is known from the integer remainder
+            const bool tap = (i == 0 || ax.two) && (j == 0 || ay.two);
+            b[k] = tap ? (i ? ax.f : 1.0f - ax.f) * (j ? ay.f : 1.0f - ay.f) : 0.0f;
+        }
+        const float kz = guide_kz(gp.w, a.sz2);
+        float e[4], emin = kRealMax;
+        bool ok[4], any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            ok[k] = b[k] > 0.0f && m[k] == mp;
+            e[k] = fminf(guide_arg(gp, g[k], a.inv_sn2, kz), kRealMax);
+            if (ok[k]) emin = fminf(emin, e[k]);
+            any = any || ok[k];
+        }
+        fallback = !any;
+        // accepted taps: the edge-weighted mean of the (demodulated) colours; none: the bilinear
+        // mean of the radiance as given.  Both as c_r + sum w (c_q - c_r) / sum w about the first
+        // tap that counts: a constant stays constant exactly.
+        const bool demod = a.demodulate && any;
+        V3 cr = v3(0.0f, 0.0f, 0.0f);
+        bool first = true;
+        float sw = 0.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool counts = any ? ok[k] : b[k] > 0.0f;
+            if (!counts) continue;
+            V3 cq = c[k];
+            if (demod) cq = v3(cq.x / albedo_floor(alb[k].x), cq.y / albedo_floor(alb[k].y), cq.z / albedo_floor(alb[k].z));
+            if (first) cr = cq;
+            first = false;
+            const float w = any ? b[k] * __expf(-(e[k] - emin)) : b[k];
+            sw += w;
+            ar += w * (cq.x - cr.x);
+            ag += w * (cq.y - cr.y);
+            ab += w * (cq.z - cr.z);
+        }
+        const float inv = 1.0f / sw;   // sw >= the weight b > 0 of the tap with e = emin, or of tap (0, 0)
+        V3 o = v3(cr.x + ar * inv, cr.y + ag * inv, cr.z + ab * inv);
+        if (demod) o = v3(o.x * albedo_floor(albp.x), o.y * albedo_floor(albp.y), o.z * albedo_floor(albp.z));
+        if (a.radiance_out) store3(a.radiance_out, p, o);
+        if (a.bgra) write_bgr(a.bgra, a.width, a.height, (size_t)x, (size_t)y, o);
+    }
+    spread_count(a.fallback, tid, fallback);   // the statistic
+}
+
+hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t s) {
+    return launch_tiles_or_rows(false, k_upsample, 0, k_upsample, a.width, a.height, s, a);
+}
 
 }  // namespace tpt

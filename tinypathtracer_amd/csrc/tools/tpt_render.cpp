@@ -9,7 +9,7 @@
 //              [--temporal] [--yaw DEG] [--svgf [iterations]] [--aov-path [bounces]]
 //              [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP] [--refit]
 //              [--adaptive TARGET [--min-spp N] [--max-spp N]]
-//              [--clip [GAMMA]] [--clip-radius R] [--clip-history N]
+//              [--clip [GAMMA]] [--clip-radius R] [--clip-history N] [--scale S]
 // --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
 // <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
 // a-trous filter of the written frame (tpt_denoise, the hosts' defaults; with
@@ -47,6 +47,12 @@
 // and its reflections stop lagging; --clip-radius R (1..3) and --clip-history N set the window and
 // the cap on a clipped pixel's history length.  Each frame prints its reprojected and clipped
 // pixel counts on stderr.
+// --scale S (2..4) traces every frame at ceil(W / S) x ceil(H / S) and makes the W x H frame of it
+// by guided upsampling (tpt_upsample, the hosts' defaults) on the feature buffers of both sizes:
+// everything after it -- --temporal*, --clip, --denoise, --svgf, the .pfm / .ppm outputs -- sees the
+// full-size frame.  <out>_low.pfm holds the traced frame, and each frame prints its fallback pixel
+// count on stderr.  With --aov-path both guide sets are the path buffers and the colours are
+// demodulated.  Not with --adaptive or --progressive.
 // --refit (with --move / --spin / --wave): the frames after the first refit the BVH
 // (tpt_scene_refit) instead of rebuilding it, and each prints its tree cost against the built
 // one and the refit's device time on stderr.
@@ -111,7 +117,7 @@ const char* kUsage =
     "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]] "
     "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP] [--refit] [--truck DX DY DZ] "
     "[--temporal-path [bounces]] [--adaptive TARGET [--min-spp N] [--max-spp N]] "
-    "[--clip [GAMMA]] [--clip-radius R] [--clip-history N]\n";
+    "[--clip [GAMMA]] [--clip-radius R] [--clip-history N] [--scale S]\n";
 
 // The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
 tpt::Camera yawed(const tpt::Camera& base, double deg) {
@@ -239,6 +245,7 @@ int main(int argc, char** argv) {
     bool refit = false;                  // --refit: frames after the first refit instead of rebuilding
     bool clip = false, clip_opts = false;   // --clip; --clip-radius or --clip-history given
     tpt_clip_params clip_params = tpt::defaultClip();
+    int scale = 1;                       // --scale: frames are traced at 1 / scale of the size and upsampled
     auto motion_of = [&](uint32_t object) -> ObjectMotion& {
         for (auto& om : motions)
             if (om.object == object) return om;
@@ -298,6 +305,13 @@ int main(int argc, char** argv) {
             waves.back().amp = std::stod(next());
         }
         else if (a == "--refit") refit = true;
+        else if (a == "--scale") {
+            scale = std::stoi(next());
+            if (scale < 2 || scale > 4) {
+                std::fprintf(stderr, "--scale S: S must be 2..4\n");
+                return 2;
+            }
+        }
         else if (a == "--clip") {
             clip = true;   // an optional gamma follows
             if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.'))
@@ -357,6 +371,10 @@ int main(int argc, char** argv) {
                              "or --truck\n");
         return 2;
     }
+    if (scale > 1 && (adaptive || progressive)) {   // both accumulate samples in a full-size frame
+        std::fprintf(stderr, "--scale cannot be combined with --adaptive or --progressive\n");
+        return 2;
+    }
     if (ad_range && !adaptive) {
         std::fprintf(stderr, "--min-spp and --max-spp need --adaptive TARGET\n");
         return 2;
@@ -388,6 +406,29 @@ int main(int argc, char** argv) {
         f.bgra.assign((size_t)W * H * 4, 255);
         f.radiance.assign((size_t)W * H * 3, 0.0f);
         tpt::Camera cam = scene.m_camera;
+        // One frame into f: traced at the full size, or (--scale) at the low size and upsampled by
+        // the feature buffers of both sizes, so that everything after it sees a W x H frame
+        const tpt::Size lo = tpt::lowSize(W, H, scale);
+        tpt::PathTracer ptl(env, lo.width, lo.height, device);
+        std::vector<float> low_rad;
+        std::vector<uint8_t> low_bgra;
+        auto trace = [&](const tpt::Camera& c, uint64_t sd, bool accumulate) {
+            if (scale == 1) {
+                f.stats = pt.doTrace(d, c, f.bgra.data(), spp, sd, depth, f.radiance.data(), 1, 0, accumulate);
+                return;
+            }
+            low_rad.resize((size_t)lo.width * lo.height * 3);
+            low_bgra.assign((size_t)lo.width * lo.height * 4, 255);
+            f.stats = ptl.doTrace(d, c, low_bgra.data(), spp, sd, depth, low_rad.data());
+            tpt::AOV gl = aov_path ? ptl.renderAOVPath(d, c, path_bounces) : ptl.renderAOV(d, c);
+            tpt::AOV gf = aov_path ? pt.renderAOVPath(d, c, path_bounces) : pt.renderAOV(d, c);
+            tpt_upsample_params up = tpt::defaultUpsample();
+            if (aov_path) up.flags |= TPT_UPSAMPLE_DEMODULATE;
+            const tpt_upsample_stats us = pt.upsample(d, lo.width, lo.height, low_rad.data(), gl.view(), gf.view(),
+                                                      f.radiance.data(), f.bgra.data(), up);
+            std::fprintf(stderr, "upsampled %d x %d to %d x %d: %llu fallback pixels, %.3f ms\n", lo.width, lo.height, W,
+                         H, (unsigned long long)us.fallback, us.kernel_ms);
+        };
         std::vector<float> acc;       // --temporal: the accumulated frame,
         std::vector<float> var, len;  //   its luminance variance and history length
         tpt::AOV g;
@@ -427,7 +468,7 @@ int main(int argc, char** argv) {
                                  rs.cost_built > 0.0 ? rs.cost / rs.cost_built : 0.0, rs.ms);
                 }
                 if (!d.built()) d.build();
-                f.stats = pt.doTrace(d, cam, f.bgra.data(), spp, base + (uint64_t)i, depth, f.radiance.data());
+                trace(cam, base + (uint64_t)i, false);
                 if (temporal_path) {   // the path buffers with their terminal points, every frame
                     std::vector<int32_t> bounces;
                     std::vector<float> points;
@@ -463,12 +504,12 @@ int main(int argc, char** argv) {
             for (int i = 0; i < frames; ++i) {
                 if (yaw != 0.0 || truck[0] != 0.0 || truck[1] != 0.0 || truck[2] != 0.0)
                     cam = trucked(yawed(scene.m_camera, yaw * i), truck, i);
-                f.stats = pt.doTrace(d, cam, f.bgra.data(), spp, seed, depth, f.radiance.data(), 1, 0,
-                                     progressive && i > 0);
+                trace(cam, seed, progressive && i > 0);
             }
         }
         write_ppm(out + ".ppm", f.bgra, W, H);
         write_pfm(out + ".pfm", f.radiance, W, H, 3);
+        if (scale > 1) write_pfm(out + "_low.pfm", low_rad, lo.width, lo.height, 3);
         if (aov || aov_path || denoise || svgf) {
             if (aov_path) {   // the filters' guides follow the mirrors (the temporal pass above did not)
                 std::vector<int32_t> bounces;
