@@ -65,10 +65,10 @@ def chain():
 
 
 def reference(cams, frames, params, clip, _without=None):
-    """The chain of clipped tpt_temporal calls through clip_ref; one result per frame."""
+    """The chain of clipped tpt_temporal calls through temporal_ref; one result per frame."""
     refs, state = [], None
     for cam, (rad, aov) in zip(cams, frames):
-        refs.append(CR.temporal_clip_ref(state, cam, rad, aov, clip, _without=_without, **params))
+        refs.append(TR.temporal_ref(state, cam, rad, aov, clip=clip, _without=_without, **params))
         state = refs[-1]["state"]
     return refs
 

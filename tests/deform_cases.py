@@ -76,10 +76,16 @@ def sequence(spec, w=W, h=H):
 
 
 def reference(seq, params, **kw):
+    """One result per frame.  A frame with deform False is a tpt_temporal call (the face guide is not
+    read, and kw, the deform reference's knock-out, does not apply); it reports no motion: zero."""
     idx = DS.rest()[0]
+    plain = {k: v for k, v in params.items() if k != "normal_margin"}
     refs, state = [], None
     for cam, wv, wn, rad, aov, deform in seq:
-        refs.append(DR.temporal_deform_ref(state, cam, rad, aov, idx, wv, wn, deform=deform, **params, **kw))
+        if deform:
+            refs.append(DR.temporal_deform_ref(state, cam, rad, aov, idx, wv, wn, **params, **kw))
+        else:
+            refs.append(dict(TR.temporal_ref(state, cam, rad, aov, **plain), motion=np.zeros(rad.shape[:2] + (2,))))
         state = refs[-1]["state"]
     return refs
 

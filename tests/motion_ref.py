@@ -4,11 +4,12 @@ tpt_temporal_motion as DESIGN.md section 5 "Moving objects" defines it, of
 tpt_motion_matrices, and temporal_ref's three synthetic patches bound to objects of a
 scene and moved with them.
 
-temporal_motion_ref is temporal_ref.temporal_ref with the numbered changes of the
-definition; where every object stands still it performs temporal_ref's operations in
-temporal_ref's order, so the two agree array for array (test_motion_api.py).  It carries
-the same `decidable` mask: pixels within 1e-3 of a threshold are left out of comparisons.
-MARGIN is that 1e-3 less one part in 10^9: a turned normal against normal_min 0.999 gives
+The definition itself lives in temporal_ref.temporal_core.  temporal_motion_ref adds what
+tpt_temporal_motion adds: where each lane's surface was in the previous frame (its object's
+D and G applied to X and n, and whether the object is tracked), the reported motion, and
+the matrices carried in the state.  Where every object stands still that is X and n
+themselves, so it agrees with temporal_ref array for array (test_motion_api.py).  Its
+`decidable` mask leaves out pixels within MARGIN of a threshold: 1e-3 less one part in 10^9: a turned normal against normal_min 0.999 gives
 n' . n_e = 1 - 1e-16, which float64 places 1e-3 - 1e-16 from the threshold, and what the mask
 guards against -- a float32 evaluation on the other side -- is six orders of magnitude wider."""
 import numpy as np
@@ -161,34 +162,19 @@ def synthetic_guides(cam, W, H, carrier, poses=None, materials=(0, 1, 2)):
 
 
 def temporal_motion_ref(state, cam, radiance, aov, carrier, vert_trans, alpha, depth_tol, normal_min, max_history,
-                        demodulate, _without=None):
+                        demodulate, clip=None, _without=None):
     """One call of the definition.  carrier: the scene's lut (Carrier); vert_trans: its
     objects' matrices at this call ([n, 16] float32); state: None or what a previous call
-    returned under `state` (it holds that call's matrices).  Returns temporal_ref's dict and
+    returned under `state` (it holds that call's matrices).  Returns temporal_core's dict with
     `motion` [H, W, 2].
 
     _without (tests/test_motion_ref_teeth.py only) evaluates a wrong definition, one rule
     knocked out: "D" reprojects X instead of X' (the static assumption), "G" compares the
-    unrotated normal, "dist" measures the expected depth from X instead of X'."""
-    assert _without in (None, "D", "G", "dist")
-    n = np.asarray(aov["normal"], np.float64)
-    z = np.asarray(aov["depth"], np.float64)
-    m = np.asarray(aov["material"], np.int64)
+    unrotated normal, "dist" (temporal_core's) measures the expected depth from X instead of X'."""
     f = np.asarray(aov["face"], np.int64)
-    H, W = z.shape
-    a = np.maximum(np.asarray(aov["albedo"], np.float64), TR.ALBEDO_FLOOR) if demodulate else 1.0
-    c = np.asarray(radiance, np.float64) / a
-    L = c @ TR.LUMA
-    hit = m >= 0
-    reproj = np.zeros((H, W), bool)
-    decidable = np.ones((H, W), bool)
-    motion = np.zeros((H, W, 2))
-    hC, hN, hM1, hM2 = np.zeros((H, W, 3)), np.zeros((H, W)), np.zeros((H, W)), np.zeros((H, W))
     vert_trans = np.asarray(vert_trans, F).reshape(-1, 16).copy()
-    if state is not None:
-        o32, d32 = R.pixel_centre_rays(cam["c2w"], cam["vfov"], cam["aspect"], W, H)
-        o, d = o32.astype(np.float64), d32.astype(np.float64)
-        X = o + z[..., None] * d
+
+    def source(state, X, n, hit, o, d32):
         # changes 1 - 3 and 5: the object, its D and G, X' and the previous frame's normal
         D, G, flags = motion_matrices_ref(state["vert_trans"], vert_trans)
         in_range = (f >= 0) & (f < carrier.n_faces)
@@ -204,68 +190,8 @@ def temporal_motion_ref(state, cam, radiance, aov, carrier, vert_trans, alpha, d
                 gn = gn / np.linalg.norm(gn, axis=-1, keepdims=True)
             Xm = np.where(moved[..., None], Xd, X)
             ne = np.where(moved[..., None], gn, n)
-        Xp = X if _without == "D" else Xm
-        if _without == "G":
-            ne = n
-        pc = state["cam"]
-        pm = np.asarray(pc["c2w"], F).astype(np.float64).reshape(4, 4).T
-        inv = np.linalg.inv(pm).astype(F).astype(np.float64)          # double, rounded to float32
-        po = pm[:3, 3]
-        local = np.where(hit[..., None], Xp @ inv[:3, :3].T + inv[:3, 3], d @ inv[:3, :3].T)
-        dist = np.linalg.norm((X if _without == "dist" else Xp) - po, axis=-1)
-        front = (local[..., 2] < 0) & tracked
-        sw, sh, hsw, hsh = (np.float64(v) for v in TR.sensor(pc["vfov"], pc["aspect"]))
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            s = -1.0 / local[..., 2]
-            fx = (local[..., 0] * s + hsw) / sw * W - 0.5
-            fy = (local[..., 1] * s + hsh) / sh * H - 0.5
-        finite = front & np.isfinite(fx) & np.isfinite(fy)
-        with np.errstate(invalid="ignore"):                             # change 8: after the snap, unclipped
-            sx = np.where(np.abs(fx - np.round(fx)) < TR.SNAP, np.round(fx), fx)
-            sy = np.where(np.abs(fy - np.round(fy)) < TR.SNAP, np.round(fy), fy)
-        xs = np.arange(W, dtype=np.float64)[None, :]
-        ys = np.arange(H, dtype=np.float64)[:, None]
-        motion[..., 0] = np.where(finite, sx - xs, 0.0)
-        motion[..., 1] = np.where(finite, sy - ys, 0.0)
-        fx = np.where(front & np.isfinite(fx), fx, -10.0)               # behind: no tap; kept finite
-        fy = np.where(front & np.isfinite(fy), fy, -10.0)
-        fx, fy = np.clip(fx, -10.0, W + 10.0), np.clip(fy, -10.0, H + 10.0)
-        for g in (fx, fy):
-            off = np.abs(g - np.round(g))
-            decidable &= ~(front & (np.abs(off - TR.SNAP) < 1e-4))
-        fx = np.where(np.abs(fx - np.round(fx)) < TR.SNAP, np.round(fx), fx)
-        fy = np.where(np.abs(fy - np.round(fy)) < TR.SNAP, np.round(fy), fy)
-        x0, y0 = np.floor(fx), np.floor(fy)
-        tx, ty = fx - x0, fy - y0
-        wsum = np.zeros((H, W))
-        for j in (0, 1):
-            for i in (0, 1):
-                w = (tx if i else 1.0 - tx) * (ty if j else 1.0 - ty)
-                qx, qy = (x0 + i).astype(np.int64), (y0 + j).astype(np.int64)
-                inside = (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
-                qxc, qyc = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
-                match = front & (w > 0) & inside & (state["m"][qyc, qxc] == m)
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    rel = np.abs(state["z"][qyc, qxc] - dist) / dist
-                ndot = (state["n"][qyc, qxc] * ne).sum(-1)
-                surf = match & hit
-                decidable &= ~(surf & ((np.abs(rel - depth_tol) < MARGIN) | (np.abs(ndot - normal_min) < MARGIN)))
-                valid = match & (~hit | ((rel <= depth_tol) & (ndot >= normal_min)))
-                wv = np.where(valid, w, 0.0)
-                wsum += wv
-                hC += wv[..., None] * state["C"][qyc, qxc]
-                hN += wv * state["N"][qyc, qxc]
-                hM1 += wv * state["M1"][qyc, qxc]
-                hM2 += wv * state["M2"][qyc, qxc]
-        decidable &= ~(np.abs(wsum - TR.MIN_WSUM) < MARGIN)
-        reproj = wsum >= TR.MIN_WSUM
-        ws = np.where(reproj, wsum, 1.0)
-        hC, hN, hM1, hM2 = hC / ws[..., None], hN / ws, hM1 / ws, hM2 / ws
-    N = np.where(reproj, np.minimum(hN + 1.0, float(max_history)), 1.0)
-    k = np.maximum(alpha, 1.0 / N)
-    C = np.where(reproj[..., None], hC + k[..., None] * (c - hC), c)
-    M1 = np.where(reproj, hM1 + k * (L - hM1), L)
-    M2 = np.where(reproj, hM2 + k * (L * L - hM2), L * L)
-    new = {"cam": cam, "C": C, "N": N, "M1": M1, "M2": M2, "n": n, "z": z, "m": m, "vert_trans": vert_trans}
-    return {"out": C * a, "variance": np.maximum(M2 - M1 * M1, 0.0), "history_len": N, "reprojected": reproj,
-            "decidable": decidable, "motion": motion, "state": new}
+        return X if _without == "D" else Xm, n if _without == "G" else ne, tracked
+
+    return TR.temporal_core(state, cam, radiance, aov, alpha, depth_tol, normal_min, max_history, demodulate, clip=clip,
+                            source=source, motion=True, extra_state={"vert_trans": vert_trans}, margin=MARGIN,
+                            knocks=("D", "G"), _without=_without)

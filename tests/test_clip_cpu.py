@@ -38,7 +38,7 @@ def test_case_exposes_rule(rule):
     cams, frames, params, clip, _ = _sequence(case)
     ref = K.reference(cams, frames, params, clip)[k]
     state = K.reference(cams[:k], frames[:k], params, clip)[-1]["state"]
-    wrong = CR.temporal_clip_ref(state, cams[k], *frames[k], clip, _without=rule, **params)
+    wrong = TR.temporal_ref(state, cams[k], *frames[k], clip=clip, _without=rule, **params)
     dec = ref["decidable"] & wrong["decidable"]
     delta = max(float(np.abs(ref[f] - wrong[f])[dec].max() / np.abs(ref[f]).max())
                 for f in ("out", "variance", "history_len"))
@@ -73,9 +73,8 @@ def test_motion_case_premises():
     """test_gpu_motion's both_move, as test_gpu_clip.motion_frames builds it."""
     M, cams, vts, frames = GC.motion_frames(True)
     params = dict(K.PARAMS, demodulate=True)
-    first = CR.clipped_ref(M.MR.temporal_motion_ref, None, cams[0], *frames[0], M.CARRIER, vts[0], clip=K.CLIP, **params)
-    second = CR.clipped_ref(M.MR.temporal_motion_ref, first["state"], cams[1], *frames[1], M.CARRIER, vts[1], clip=K.CLIP,
-                            **params)
+    first = M.MR.temporal_motion_ref(None, cams[0], *frames[0], M.CARRIER, vts[0], clip=K.CLIP, **params)
+    second = M.MR.temporal_motion_ref(first["state"], cams[1], *frames[1], M.CARRIER, vts[1], clip=K.CLIP, **params)
     K.premises("both_move", second, G.W, G.H)
 
 
@@ -88,8 +87,7 @@ def test_deform_case_premises():
     params = dict(DC.PARAMS, **extra, demodulate=True)
     state = None
     for cam, wv, wn, rad, aov, deform in DC.sequence(spec):
-        ref = CR.clipped_ref(DR.temporal_deform_ref, state, cam, rad, CR.speck(aov), DS.rest()[0], wv, wn, clip=K.CLIP,
-                             deform=deform, **params)
+        ref = DR.temporal_deform_ref(state, cam, rad, CR.speck(aov), DS.rest()[0], wv, wn, clip=K.CLIP, **params)
         state = ref["state"]
     K.premises("camera_bulge", ref, DC.W, DC.H)
 
@@ -102,8 +100,8 @@ def test_path_case_premises():
     state = None
     for i, cam in enumerate(PK.case_cameras("hall_two")):
         aov = CR.speck(PK.walk(name, w, h, cap, cam))
-        ref = CR.clipped_ref(TP.temporal_path_ref, state, cam, PK.radiance(101 + 101 * i, aov), aov, clip=K.CLIP,
-                             point_tol=PK.POINT_TOL, **dict(PK.PARAMS, demodulate=True))
+        ref = TP.temporal_path_ref(state, cam, PK.radiance(101 + 101 * i, aov), aov, clip=K.CLIP,
+                                   point_tol=PK.POINT_TOL, **dict(PK.PARAMS, demodulate=True))
         state = ref["state"]
     assert (aov["bounces"] > 0).sum() >= 100
     K.premises("hall_two", ref, w, h)
@@ -152,7 +150,7 @@ def test_clip_shortens_the_lag():
         now = level * np.where(region[..., None] & (k >= 6), 0.3, 1.0)
         rad = (now * rng.gamma(4.0, 0.25, (h, w, 3))).astype(np.float32)       # relative standard deviation 0.5
         for on in (False, True):
-            r = CR.temporal_clip_ref(states[on], cam, rad, aov, K.CLIP if on else None, **params)
+            r = TR.temporal_ref(states[on], cam, rad, aov, clip=K.CLIP if on else None, **params)
             states[on] = r["state"]
             if k == 8:
                 truth, outs[on] = now, r["out"]

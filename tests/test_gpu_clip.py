@@ -204,7 +204,7 @@ def test_motion_case_matches_numpy_reference(ctx):
     params = dict(K.PARAMS, demodulate=True)
     refs, state = [], None
     for cam, vt, (rad, aov) in zip(cams, vts, frames):
-        refs.append(CR.clipped_ref(M.MR.temporal_motion_ref, state, cam, rad, aov, M.CARRIER, vt, clip=K.CLIP, **params))
+        refs.append(M.MR.temporal_motion_ref(state, cam, rad, aov, M.CARRIER, vt, clip=K.CLIP, **params))
         state = refs[-1]["state"]
     got = play(ctx, cams, frames, params, K.CLIP, entry="motion", before=lambda k: ctx.set_transforms(0, vts[k]))
     K.premises("both_move", refs[1], G.W, G.H)
@@ -230,8 +230,7 @@ def test_deform_case_matches_numpy_reference(gpu_available):
         wv, wn = d.read_world()
         rad, _ = DC.colours(aov, seed)
         got.append(call(pt, hist, cam, rad, aov, "deform", **params))
-        refs.append(CR.clipped_ref(DR.temporal_deform_ref, state, cam, rad, aov, D.IDX, wv, wn, clip=K.CLIP, deform=True,
-                                   **params))
+        refs.append(DR.temporal_deform_ref(state, cam, rad, aov, D.IDX, wv, wn, clip=K.CLIP, **params))
         state = refs[-1]["state"]
     hist.close()
     d.close()
@@ -257,7 +256,7 @@ def test_path_case_matches_numpy_reference(gpu_available):
     params = dict(PK.PARAMS, demodulate=True)
     refs, state = [], None
     for cam, (rad, aov) in zip(cams, frames):
-        refs.append(CR.clipped_ref(TP.temporal_path_ref, state, cam, rad, aov, clip=K.CLIP, point_tol=PK.POINT_TOL, **params))
+        refs.append(TP.temporal_path_ref(state, cam, rad, aov, clip=K.CLIP, point_tol=PK.POINT_TOL, **params))
         state = refs[-1]["state"]
     got = play(d, cams, frames, params, K.CLIP, entry="path", point_tol=PK.POINT_TOL)
     d.close()

@@ -139,12 +139,8 @@ def play(d, spec, params, w=W, h=H, flags=0, unit_normals=False, edit=None):
     return frames, got
 
 
-def reference(frames, params, idx=IDX):
-    refs, state = [], None
-    for cam, wv, wn, rad, aov, deform in frames:
-        refs.append(DR.temporal_deform_ref(state, cam, rad, aov, idx, wv, wn, deform=deform, **params))
-        state = refs[-1]["state"]
-    return refs
+def reference(frames, params):
+    return DC.reference(frames, params)
 
 
 def check_motion(tag, mv, ref):

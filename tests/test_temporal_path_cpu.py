@@ -133,8 +133,8 @@ def test_cap_zero_buffers_are_first_hit_accumulation():
 def test_a_first_hit_call_disoccludes_the_mirror_pixels():
     """Rule 6 in the reference: after a tpt_temporal call every stored k' is 0."""
     cams, frames = frames_of("hall_two")
-    r1 = K.run_reference(frames[:1], cams[:1], False)[0]
-    r2 = TP.temporal_path_ref(TP.first_hit_state(r1["state"]), cams[1], *frames[1], demodulate=False,
+    r1 = TR.temporal_ref(None, cams[0], *frames[0], demodulate=False, **K.PARAMS)
+    r2 = TP.temporal_path_ref(r1["state"], cams[1], *frames[1], demodulate=False,
                               point_tol=K.POINT_TOL, **K.PARAMS)
     followed = frames[1][1]["bounces"] > 0
     assert followed.sum() > 300

@@ -31,7 +31,6 @@ sys.path.insert(0, ROOT)
 
 import tinypathtracer_amd as T  # noqa: E402
 from oracle import oracle as O  # noqa: E402
-from tests import clip_ref as CR  # noqa: E402
 from tests import motion_ref as MR  # noqa: E402
 from tests import path_ref as P  # noqa: E402
 from tests import svgf_ref as SR  # noqa: E402
@@ -89,7 +88,7 @@ def main():
     def accumulate(clip):
         state = None
         for m, rad, aov in frames:
-            r = CR.clipped_ref(MR.temporal_motion_ref, state, cam, rad, aov, carrier, m, clip=clip, **params)
+            r = MR.temporal_motion_ref(state, cam, rad, aov, carrier, m, clip=clip, **params)
             state = r["state"]
         return r
 
