@@ -8,9 +8,14 @@
  *   (src/path_tracer.cu:296-299).  Plain pointers and sizes only; no
  * exceptions cross this boundary (errors: tpt_status + tpt_last_error()).
  *
- * Handles own device memory; caller buffers are borrowed.  One tpt_scene per
- * HIP device; calls on different scenes may run concurrently from different
- * host threads, calls on one scene must be serialised by the caller.
+ * Handles own device memory; caller buffers are borrowed.  A tpt_scene lives
+ * on one HIP device (a device may hold any number of scenes); calls on
+ * different scenes may run concurrently from different host threads, calls on
+ * one scene -- and on the histories made from it -- must be serialised by the
+ * caller.  A const tpt_env* is read-only after its creation and may be shared
+ * by concurrent renders of different scenes; destroy it once they have
+ * returned.  tpt_last_error() is per thread: it returns the message of the
+ * calling thread's last failed call, valid until that thread's next one.
  */
 #ifndef TPT_H
 #define TPT_H

@@ -13,21 +13,31 @@
 //                                  (trace_lds_layout) first (variant_case below); one JSON object per case
 //   host_check variant-sweep N SEED   plan-sweep's cases and more: every plan's lane mode and workgroup rows
 //                                  are those of the variant launch_trace selects for the plan's requests
+//   host_check jumps N        N threads make the process's first host_jumps() calls together (host/rng_host.cpp):
+//                             each must see the table xorwow_jump_matrices builds serially; "ok", or
+//                             "differs <thread> ..." per thread that saw another one and exit status 1
+//   host_check parse-threads N [--gltf FILE...] [--image FILE...] [--plan CASE...] [--variant CASE...]
+//                             N threads load the scenes and images and run the plan and variant cases at once,
+//                             each on its own objects; each must get the serial run's bytes
 //
 // Prints one line per input: "ok", or "error: <message>" for a parse error
 // (the library's exception, which tpt_gltf_load / tpt_env_load turn into a
 // status).  Any memory error or undefined behaviour aborts with the
 // sanitizer's report instead.
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <random>
+#include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
+#include "../common/rng.hpp"
 #include "launch_plan.hpp"
 #include "tpt_internal.hpp"
 
@@ -93,35 +103,35 @@ static bool plan_case(const std::string& text, PlanCase& c) {
 }
 
 template <class It, class F>
-static void print_list(const char* name, It b, It e, F item) {
-    std::printf(",\"%s\":[", name);
+static void print_list(FILE* f, const char* name, It b, It e, F item) {
+    std::fprintf(f, ",\"%s\":[", name);
     for (It i = b; i != e; ++i) {
-        if (i != b) std::printf(",");
+        if (i != b) std::fprintf(f, ",");
         item(*i);
     }
-    std::printf("]");
+    std::fprintf(f, "]");
 }
 
-static void print_plan(const PlanCase& c, const tpt::LaunchPlan& pl) {
+static void print_plan(const PlanCase& c, const tpt::LaunchPlan& pl, FILE* f = stdout) {
     if (pl.status != TPT_OK) {
-        std::printf("{\"status\":%d,\"message\":\"%s\"}\n", (int)pl.status, pl.message);
+        std::fprintf(f, "{\"status\":%d,\"message\":\"%s\"}\n", (int)pl.status, pl.message);
         return;
     }
-    std::printf("{\"status\":0,\"bh\":%d,\"pair\":%d,\"pair_kernel\":%d,\"quad\":%d,\"drained\":%d,\"refill\":%d,"
+    std::fprintf(f, "{\"status\":0,\"bh\":%d,\"pair\":%d,\"pair_kernel\":%d,\"quad\":%d,\"drained\":%d,\"refill\":%d,"
                 "\"leaf_kb\":%d,\"xcd_run\":%d,\"wg_rows\":%d,\"nset\":%d,\"chunk\":%d",
                 c.in.bh, pl.pair, pl.pair_kernel, pl.quad, pl.drained, pl.refill, pl.leaf_kb, pl.xcd_run, pl.wg_rows,
                 pl.nset, pl.chunk);
-    print_list("launches", pl.launches.begin(), pl.launches.end(),
-               [](const tpt::PlanLaunch& l) { std::printf("[%d,%d]", l.set, l.samples); });
-    print_list("order", pl.order.begin(), pl.order.end(), [](size_t j) { std::printf("%zu", j); });
-    print_list("set_rows", pl.set_rows, pl.set_rows + pl.nset, [](int32_t r) { std::printf("%d", r); });
-    print_list("set_off", pl.set_off, pl.set_off + pl.nset, [](size_t o) { std::printf("%zu", o); });
-    print_list("set_list", pl.set_list, pl.set_list + pl.nset, [](const std::vector<int32_t>& l) {
-        std::printf("[");
-        for (size_t i = 0; i < l.size(); ++i) std::printf(i ? ",%d" : "%d", l[i]);
-        std::printf("]");
+    print_list(f, "launches", pl.launches.begin(), pl.launches.end(),
+               [f](const tpt::PlanLaunch& l) { std::fprintf(f, "[%d,%d]", l.set, l.samples); });
+    print_list(f, "order", pl.order.begin(), pl.order.end(), [f](size_t j) { std::fprintf(f, "%zu", j); });
+    print_list(f, "set_rows", pl.set_rows, pl.set_rows + pl.nset, [f](int32_t r) { std::fprintf(f, "%d", r); });
+    print_list(f, "set_off", pl.set_off, pl.set_off + pl.nset, [f](size_t o) { std::fprintf(f, "%zu", o); });
+    print_list(f, "set_list", pl.set_list, pl.set_list + pl.nset, [f](const std::vector<int32_t>& l) {
+        std::fprintf(f, "[");
+        for (size_t i = 0; i < l.size(); ++i) std::fprintf(f, i ? ",%d" : "%d", l[i]);
+        std::fprintf(f, "]");
     });
-    std::printf("}\n");
+    std::fprintf(f, "}\n");
 }
 
 // The invariants every plan keeps; returns what is broken (null: nothing).
@@ -235,9 +245,9 @@ static int check_plan_sweep(int n, unsigned seed) {
 
 static const char* const kFamilyName[tpt::kTraceFamilies] = {"lane", "drain", "pair", "is", "quad", "ref", "is_pair", "ref_is"};
 
-static void print_key(const tpt::TraceKey& k) {
+static void print_key(const tpt::TraceKey& k, FILE* to) {
     const tpt::TraceFamilyInfo& f = tpt::kTraceFamily[k.family];
-    std::printf("\"family\":\"%s\",\"env_is\":%d,\"lanes\":%d,\"deep\":%d,\"lights\":%d,\"mtl_lds\":%d,\"wide_ids\":%d,"
+    std::fprintf(to, "\"family\":\"%s\",\"env_is\":%d,\"lanes\":%d,\"deep\":%d,\"lights\":%d,\"mtl_lds\":%d,\"wide_ids\":%d,"
                 "\"noemit\":%d,\"legal\":%d,\"packed\":%u",
                 kFamilyName[k.family], f.env_is, f.lanes, k.deep, k.lights, k.mtl_lds, k.wide_ids, k.noemit,
                 tpt::trace_key_legal(k), tpt::trace_key_pack(k));
@@ -247,12 +257,12 @@ static void print_key(const tpt::TraceKey& k) {
 //   select=1, ref env_is pair quad drained lights mtls faces depth emitter  (what launch_trace sees; default: box-like,
 //             no lights, 5 materials, 1,932 faces, depth 8, an emitter)
 //   layout=1, family (a name above) lights mtl_lds wide_ids wgw (0: the family's) stack depth mtls max_slots max_levels
-static bool variant_case(const std::string& text) {
+static bool variant_case(const std::string& text, FILE* to = stdout) {
     if (text == "table") {
-        std::printf("{\"families\":[");
+        std::fprintf(to, "{\"families\":[");
         for (int f = 0; f < tpt::kTraceFamilies; ++f) {
             const tpt::TraceFamilyInfo& r = tpt::kTraceFamily[f];
-            std::printf("%s[\"%s\",%d,%d,%d,%d,%d,%d,%d,%d]", f ? "," : "", kFamilyName[f], r.wgw, r.waves, r.lds_waves, r.lanes,
+            std::fprintf(to, "%s[\"%s\",%d,%d,%d,%d,%d,%d,%d,%d]", f ? "," : "", kFamilyName[f], r.wgw, r.waves, r.lds_waves, r.lanes,
                         r.tile_w, r.tile_rows, r.env_is, r.ordered);
         }
         int legal = 0, round_trip = 0;
@@ -260,7 +270,7 @@ static bool variant_case(const std::string& text) {
             legal += tpt::trace_key_legal(tpt::trace_key_unpack(p));
             round_trip += tpt::trace_key_pack(tpt::trace_key_unpack(p)) == p;
         }
-        std::printf("],\"public\":%d,\"legal_keys\":%d,\"round_trip\":%d}\n", tpt::kTracePublicFamilies, legal, round_trip);
+        std::fprintf(to, "],\"public\":%d,\"legal_keys\":%d,\"round_trip\":%d}\n", tpt::kTracePublicFamilies, legal, round_trip);
         return true;
     }
     tpt::TraceSelectIn in{false, false, false, false, false, 0, 5, 1932, 8, true};
@@ -303,18 +313,18 @@ static bool variant_case(const std::string& text) {
     if (mode == 1) {
         const tpt::TraceSelection s = tpt::select_trace_variant(in);
         if (s.error) {
-            std::printf("{\"error\":\"%s\"}\n", s.error);
+            std::fprintf(to, "{\"error\":\"%s\"}\n", s.error);
             return true;
         }
-        std::printf("{");
-        print_key(s.key);
-        std::printf("}\n");
+        std::fprintf(to, "{");
+        print_key(s.key, to);
+        std::fprintf(to, "}\n");
         return true;
     }
     if (mode != 2) return false;
     const tpt::TraceLds l = tpt::trace_lds_layout(k, wgw > 0 ? (int)wgw : tpt::kTraceFamily[k.family].wgw, (int)stack, (int)depth,
                                                   (int)mtls, (size_t)max_slots, (size_t)max_levels);
-    std::printf("{\"bytes\":%zu,\"mtl_offset\":%d,\"stack_offset\":%d,\"rec_offset\":%d,\"stack_slots\":%d,\"rec_levels\":%d}\n",
+    std::fprintf(to, "{\"bytes\":%zu,\"mtl_offset\":%d,\"stack_offset\":%d,\"rec_offset\":%d,\"stack_slots\":%d,\"rec_levels\":%d}\n",
                 l.bytes, l.mtl_offset, l.stack_offset, l.rec_offset, l.stack_slots, l.rec_levels);
     return true;
 }
@@ -422,13 +432,161 @@ static int check_wide(int n, unsigned seed, int threads) {
     return 0;
 }
 
+// n threads, released together by one flag, each run work(thread); returns once all are joined.
+template <class F>
+static void run_together(int n, F work) {
+    std::atomic<int> ready{0};
+    std::atomic<bool> go{false};
+    std::vector<std::thread> th;
+    for (int i = 0; i < n; ++i)
+        th.emplace_back([&, i] {
+            ready.fetch_add(1);
+            while (!go.load(std::memory_order_acquire)) {
+            }
+            work(i);
+        });
+    while (ready.load() < n) std::this_thread::yield();
+    go.store(true, std::memory_order_release);
+    for (std::thread& t : th) t.join();
+}
+
+// The process's first host_jumps() calls, made by n threads at once: what each thread sees at
+// the moment the call returns must be the finished table.
+static int check_jumps(int n) {
+    const size_t words = (size_t)tpt::kRngJumps * tpt::kJumpWords;
+    std::vector<uint32_t> ref(words);
+    tpt::xorwow_jump_matrices(tpt::kRngJumps, ref.data());
+    std::vector<std::vector<uint32_t>> seen((size_t)n);
+    run_together(n, [&](int i) {
+        const auto& j = tpt::host::host_jumps();
+        seen[(size_t)i].assign(j.begin(), j.end());
+    });
+    int bad = 0;
+    for (int i = 0; i < n; ++i) {
+        const std::vector<uint32_t>& s = seen[(size_t)i];
+        size_t wrong = 0, first = words;
+        for (size_t k = 0; k < std::min(words, s.size()); ++k)
+            if (s[k] != ref[k]) {
+                ++wrong;
+                first = std::min(first, k);
+            }
+        if (s.size() != words || wrong) {
+            std::printf("differs %d: %zu of %zu words, %zu wrong, the first at %zu\n", i, s.size(), words, wrong, first);
+            ++bad;
+        }
+    }
+    if (bad) return 1;
+    std::printf("ok jumps: %d threads saw the serial table (%zu words)\n", n, words);
+    return 0;
+}
+
+// What one thread of parse-threads does, on objects of its own: every scene and image loaded,
+// every plan and variant case run; the results as one string of bytes.  Throws what the loaders throw.
+struct ParseWork {
+    std::vector<std::string> gltf, image, plan, variant;
+};
+static std::string parse_work(const ParseWork& w) {
+    std::string out;
+    auto put = [&out](const void* p, size_t bytes) {
+        const uint64_t n = bytes;
+        out.append((const char*)&n, sizeof n);
+        out.append((const char*)p, bytes);
+    };
+    for (const std::string& path : w.gltf) {
+        tpt::HostScene hs;
+        tpt::load_gltf(path, hs);
+        put(hs.indices.data(), hs.indices.size() * sizeof(uint32_t));
+        put(hs.vertices.data(), hs.vertices.size() * sizeof(float));
+        put(hs.normals.data(), hs.normals.size() * sizeof(float));
+        put(hs.lut.data(), hs.lut.size() * sizeof(tpt_interval));
+        put(hs.vert_trans.data(), hs.vert_trans.size() * sizeof(float));
+        put(hs.normal_trans.data(), hs.normal_trans.size() * sizeof(float));
+        put(hs.materials.data(), hs.materials.size() * sizeof(tpt_material));
+        put(hs.lights.data(), hs.lights.size() * sizeof(tpt_light));
+        put(&hs.camera, sizeof hs.camera);
+        out.push_back(hs.missing_material ? '1' : '0');
+    }
+    for (const std::string& path : w.image) {
+        std::vector<uint8_t> rgba;
+        int32_t wh[2] = {0, 0};
+        tpt::load_image(path, rgba, wh[0], wh[1]);
+        put(wh, sizeof wh);
+        put(rgba.data(), rgba.size());
+    }
+    char* text = nullptr;
+    size_t len = 0;
+    FILE* f = open_memstream(&text, &len);
+    if (!f) throw std::runtime_error("open_memstream failed");
+    bool good = true;
+    for (const std::string& c : w.plan) {
+        PlanCase pc;
+        good = good && plan_case(c, pc);
+        if (good) print_plan(pc, tpt::plan_launches(pc.in), f);
+    }
+    for (const std::string& c : w.variant) good = good && variant_case(c, f);
+    std::fclose(f);
+    out.append(text, len);
+    std::free(text);
+    if (!good) throw std::runtime_error("bad plan or variant case");
+    return out;
+}
+
+// parse-threads N [--gltf FILE...] [--image FILE...] [--plan CASE...] [--variant CASE...]: the loaders,
+// the planner and the variant selection keep no state between calls, so n threads doing the same work at
+// once each get the bytes the serial run got.
+static int check_parse_threads(int n, int argc, char** argv) {
+    ParseWork w;
+    std::vector<std::string>* into = nullptr;
+    for (int i = 0; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--gltf") into = &w.gltf;
+        else if (a == "--image") into = &w.image;
+        else if (a == "--plan") into = &w.plan;
+        else if (a == "--variant") into = &w.variant;
+        else if (into) into->push_back(a);
+        else return 2;
+    }
+    std::string serial;
+    try {
+        serial = parse_work(w);
+    } catch (const std::exception& ex) {
+        std::printf("error: serial run: %s\n", ex.what());
+        return 1;
+    }
+    std::vector<std::string> got((size_t)n), err((size_t)n);
+    run_together(n, [&](int i) {
+        const ParseWork mine = w;
+        try {
+            got[(size_t)i] = parse_work(mine);
+        } catch (const std::exception& ex) {
+            err[(size_t)i] = std::string("error: ") + ex.what();
+        }
+    });
+    int bad = 0;
+    for (int i = 0; i < n; ++i) {
+        if (err[(size_t)i].empty() && got[(size_t)i] == serial) continue;
+        size_t k = 0;
+        while (k < std::min(serial.size(), got[(size_t)i].size()) && serial[k] == got[(size_t)i][k]) ++k;
+        std::printf("differs %d: %zu bytes against %zu, the first at %zu %s\n", i, got[(size_t)i].size(), serial.size(), k,
+                    err[(size_t)i].c_str());
+        ++bad;
+    }
+    if (bad) return 1;
+    std::printf("ok parse-threads: %d threads, %zu scenes, %zu images, %zu plans, %zu variant cases, %zu bytes each\n", n,
+                w.gltf.size(), w.image.size(), w.plan.size(), w.variant.size(), serial.size());
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: host_check gltf|image FILE... | wide N SEED [THREADS] | plan CASE... | "
-                             "plan-sweep N SEED | variant CASE... | variant-sweep N SEED\n");
+                             "plan-sweep N SEED | variant CASE... | variant-sweep N SEED | jumps N | "
+                             "parse-threads N [--gltf FILE...] [--image FILE...] [--plan CASE...] [--variant CASE...]\n");
         return 2;
     }
     const std::string mode = argv[1];
+    if (mode == "jumps") return check_jumps(std::max(std::atoi(argv[2]), 1));
+    if (mode == "parse-threads") return check_parse_threads(std::max(std::atoi(argv[2]), 1), argc - 3, argv + 3);
     if (mode == "plan-sweep") return check_plan_sweep(std::atoi(argv[2]), argc > 3 ? (unsigned)std::atoi(argv[3]) : 1u);
     if (mode == "variant-sweep")
         return check_variant_sweep(std::atoi(argv[2]), argc > 3 ? (unsigned)std::atoi(argv[3]) : 1u);

@@ -39,8 +39,6 @@ struct DevLight {
 };
 
 constexpr int kMaxLights = 16;
-constexpr int kRngJumps = 16;            // base-4 digits: up to 4^16 = 2^32 pixels
-constexpr int kJumpWords = 160 * 5;      // one 160x160 GF(2) matrix
 
 struct TraceArgs {
     // scene

@@ -42,7 +42,11 @@ TPT_HD float xorwow_uniform(uint32_t st[6]) {
     return (float)xorwow_next(st) * 2.3283064e-10f + (2.3283064e-10f / 2.0f);
 }
 
+constexpr int kRngJumps = 16;            // base-4 digits: up to 4^16 = 2^32 pixels
+constexpr int kJumpWords = 160 * 5;      // one 160x160 GF(2) matrix
+
 // Jump matrices J_k = A^(2^67 * 4^k), k < n: row b (input bit b) = 5 words (host).
+// The library's own table of kRngJumps matrices is host_jumps() (host/tpt_internal.hpp).
 void xorwow_jump_matrices(int n, uint32_t* out);
 
 }  // namespace tpt

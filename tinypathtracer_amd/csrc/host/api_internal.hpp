@@ -287,8 +287,6 @@ struct HostTrees {
     bool emit_ok() const { return ne4 > 0 && (size_t)(base() + ne4) <= n - 1 && eneed <= 150; }
 };
 
-// the RNG's jump matrices, built once (api_scene.cpp)
-std::vector<uint32_t>& host_jumps();
 // Joins an asynchronous build's host half and uploads its trees (a no-op
 // without one).  Every entry point that reads the traversal trees calls it
 // (api_scene.cpp).

@@ -14,15 +14,6 @@
 #include "../common/tri_rec.hpp"
 #include "api_internal.hpp"
 
-std::vector<uint32_t>& tpt::host::host_jumps() {
-    static std::vector<uint32_t> j;
-    if (j.empty()) {
-        j.resize((size_t)tpt::kRngJumps * tpt::kJumpWords);
-        tpt::xorwow_jump_matrices(tpt::kRngJumps, j.data());
-    }
-    return j;
-}
-
 namespace {
 
 constexpr float kInfF = __builtin_huge_valf();

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../common/rng.hpp"
+#include "tpt_internal.hpp"
 
 namespace tpt {
 namespace {
@@ -46,6 +47,17 @@ void xorwow_jump_matrices(int count, uint32_t* out) {
         compose(a.data(), a.data(), t.data());
         compose(t.data(), t.data(), a.data());
     }
+}
+
+// A function-local static is initialised exactly once, and a thread that arrives while
+// another builds it waits for the finished table; nobody sees it empty or half filled.
+const std::vector<uint32_t>& host::host_jumps() {
+    static const std::vector<uint32_t> table = [] {
+        std::vector<uint32_t> j((size_t)kRngJumps * kJumpWords);
+        xorwow_jump_matrices(kRngJumps, j.data());
+        return j;
+    }();
+    return table;
 }
 
 }  // namespace tpt

@@ -97,6 +97,13 @@ int build_wide_sah(const std::vector<int>& pos, const float* leaf_box, const uin
 // the level ranges of its breadth-first numbering (wide_bvh.cpp; tpt_wide_tree_levels)
 int wide_tree_levels(const float* nodes, int n_nodes, int id_base, std::vector<int32_t>& begin);
 
+namespace host __attribute__((visibility("hidden"))) {
+// The RNG's kRngJumps jump matrices (common/rng.hpp), shared by every scene of the process:
+// built once by the first caller, whichever thread that is; later and concurrent callers get
+// the finished table (rng_host.cpp).
+const std::vector<uint32_t>& host_jumps();
+}  // namespace host
+
 }  // namespace tpt
 
 struct tpt_gltf {
