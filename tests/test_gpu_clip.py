@@ -164,15 +164,16 @@ def still_inputs(ctx):
                   "path": (flat, dict(point_tol=1.0))}
 
 
+@pytest.mark.parametrize("flags", [0, _lib.TEMPORAL_TILES], ids=["rows", "tiles"])
 @pytest.mark.parametrize("entry", ["temporal", "motion", "deform", "path"])
-def test_loose_box_is_the_unclipped_call(ctx, entry):
+def test_loose_box_is_the_unclipped_call(ctx, entry, flags):
     """gamma = 1e30 on random colours: the box never bites, and every entry point gives the bits of
     the same call with the clip off -- the next frame's too, which proves the state."""
     cams, inputs = still_inputs(ctx)
     frames, kw = inputs[entry]
     params = dict(K.PARAMS, demodulate=True)
-    off = play(ctx, cams, frames, params, None, entry=entry, **kw)
-    loose = play(ctx, cams, frames, params, dict(radius=2, gamma=1e30, max_history=1), entry=entry, **kw)
+    off = play(ctx, cams, frames, params, None, flags, entry=entry, **kw)
+    loose = play(ctx, cams, frames, params, dict(radius=2, gamma=1e30, max_history=1), flags, entry=entry, **kw)
     for k in range(3):
         for a, b in zip(off[k][:3], loose[k][:3]):
             assert np.array_equal(_bits(a), _bits(b)), (entry, k)
@@ -184,11 +185,12 @@ def test_loose_box_is_the_unclipped_call(ctx, entry):
     assert (off[2][2] == 3.0).any()
 
 
-def test_still_scene_is_clipped_tpt_temporal(ctx):
+@pytest.mark.parametrize("flags", [0, _lib.TEMPORAL_TILES], ids=["rows", "tiles"])
+def test_still_scene_is_clipped_tpt_temporal(ctx, flags):
     """Nothing moved, nothing deformed, no mirror: the three other entry points give clipped tpt_temporal's bits."""
     cams, inputs = still_inputs(ctx)
     params = dict(K.PARAMS, demodulate=True)
-    got = {e: play(ctx, cams, frames, params, K.CLIP, entry=e, **kw) for e, (frames, kw) in inputs.items()}
+    got = {e: play(ctx, cams, frames, params, K.CLIP, flags, entry=e, **kw) for e, (frames, kw) in inputs.items()}
     assert got["temporal"][2][3]["clipped"] >= 20
     for e in ("motion", "deform", "path"):
         for k in range(3):

@@ -402,7 +402,6 @@ struct TemporalArgs {
 };
 constexpr int kTemporalSlots = 256;
 constexpr int kTemporalSlotStride = 16;  // 128 B: one counter per cache line
-hipError_t launch_temporal(const TemporalArgs& a, hipStream_t s);
 
 // post.hip: what the motion-aware variant (tpt_temporal_motion) reads and writes on top of
 // TemporalArgs.  A record is tpt_motion_matrices' 24 floats, read as six float4:
@@ -417,11 +416,10 @@ struct MotionArgs {
 };
 constexpr int kMotionRecordFloats = 24;
 constexpr int32_t kMotionTracked = 0, kMotionIdentity = 1, kMotionUntracked = 2;
-hipError_t launch_temporal_motion(const TemporalArgs& a, const MotionArgs& mo, hipStream_t s);
 
 // post.hip: what the pass on mirror-path guides (tpt_temporal_path) reads and writes on top of
 // TemporalArgs, whose guides are then tpt_render_aov_path's.  The bounce count k is kept as its
-// integer bits in the fourth word of state plane 2 (k_temporal and k_temporal_motion write 0.0f
+// integer bits in the fourth word of state plane 2 (every other variant of k_temporal writes 0.0f
 // there: k = 0); the terminal points are a fourth state plane per set, (P.xyz, 0), written and
 // gathered by k > 0 lanes only.
 struct TemporalPathArgs {
@@ -431,7 +429,6 @@ struct TemporalPathArgs {
     float4* next_points;                 // the new state's plane 3 (written where k > 0)
     float point_tol;                     // > 0, in pixel footprints
 };
-hipError_t launch_temporal_path(const TemporalArgs& a, const TemporalPathArgs& pa, hipStream_t s);
 
 // post.hip: what the variant that follows deforming meshes (tpt_temporal_deform) reads and writes
 // on top of TemporalArgs: the scene's topology and world buffers as they are now, and the
@@ -447,7 +444,6 @@ struct DeformArgs {
     int32_t n_faces;
     int32_t snap_valid;                  // 0: the snapshot is not the previous call's: hit pixels are disoccluded
 };
-hipError_t launch_temporal_deform(const TemporalArgs& a, const DeformArgs& de, hipStream_t s);
 
 // post.hip: history clipping (tpt_history_set_clip; DESIGN.md section 5 "History clipping").
 // k_clip_box writes, per pixel, the box of the colours the temporal kernel accumulates over the
@@ -471,19 +467,19 @@ struct ClipBoxArgs {
 };
 hipError_t launch_clip_box(const ClipBoxArgs& a, hipStream_t s);
 
-// What the clipped compilations of the temporal kernels (k_temporal_clip, ...) take on top of
-// their twins' arguments: the two planes, the cap on a clipped pixel's history length and the
-// counter of the pixels whose history the clip moved.
+// What the clipped temporal kernels take on top of their twins' arguments: the two planes, the
+// cap on a clipped pixel's history length and the counter of the pixels whose history the clip
+// moved.
 struct ClipArgs {
     const float4* lo;
     const float4* hi;
     float clip_history;
     unsigned long long* clipped;         // kTemporalSlots counters, as TemporalArgs::reprojected
 };
-hipError_t launch_temporal_clip(const TemporalArgs& a, const ClipArgs& cl, hipStream_t s);
-hipError_t launch_temporal_motion_clip(const TemporalArgs& a, const MotionArgs& mo, const ClipArgs& cl, hipStream_t s);
-hipError_t launch_temporal_path_clip(const TemporalArgs& a, const TemporalPathArgs& pa, const ClipArgs& cl, hipStream_t s);
-hipError_t launch_temporal_deform_clip(const TemporalArgs& a, const DeformArgs& de, const ClipArgs& cl, hipStream_t s);
+// The temporal kernel that takes the arguments given: at most one of mo, pa and de
+// (hipErrorInvalidValue otherwise; none: tpt_temporal's), and cl where the history is clipped.
+hipError_t launch_temporal(const TemporalArgs& a, const MotionArgs* mo, const TemporalPathArgs* pa, const DeformArgs* de,
+                           const ClipArgs* cl, hipStream_t s);
 
 // post.hip: the variance-guided a-trous filter (tpt_denoise_svgf; DESIGN.md section 5
 // "Post-pass").  tpt_denoise's planes, the colour plane's fourth component carrying the

@@ -490,9 +490,12 @@ struct tpt_scene {
     }
 };
 
-// The temporal entry points' state (post.hip k_temporal, k_temporal_motion, k_temporal_path,
-// k_temporal_deform): two sets of three float4 planes that ping-pong, the previous call's camera
-// and object transforms, device staging of host buffers.
+// Which of the four temporal entry points a call is: tpt_temporal, tpt_temporal_motion,
+// tpt_temporal_path, tpt_temporal_deform.
+enum class TemporalKind { Plain, Motion, Path, Deform };
+
+// The temporal entry points' state (post.hip k_temporal): two sets of three float4 planes that
+// ping-pong, the previous call's camera and object transforms, device staging of host buffers.
 struct tpt_history {
     tpt_scene* scene = nullptr;             // the stream; outlives the history's last tpt_temporal
     int device = 0;

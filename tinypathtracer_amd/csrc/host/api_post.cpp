@@ -290,7 +290,7 @@ tpt_status tpt_history_reset(tpt_history* h) {
 
 void tpt_history_destroy(tpt_history* h) { delete h; }
 
-// History clipping (post.hip k_clip_box and the k_temporal*_clip kernels; DESIGN.md section 5
+// History clipping (post.hip k_clip_box and k_temporal with ClipArgs; DESIGN.md section 5
 // "History clipping"): a setting of the history that every temporal entry point obeys.
 tpt_status tpt_history_set_clip(tpt_history* h, const tpt_clip_params* p) {
     if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
@@ -322,14 +322,13 @@ struct PathInputs {
     float point_tol;
 };
 
-// tpt_temporal (motion false: face guide and motion_out unused), tpt_temporal_motion,
-// tpt_temporal_path (path not null; never with motion) and tpt_temporal_deform (deform; never
-// with motion or path)
+// The four temporal entry points.  Plain and Path: face guide and motion_out unused; path: not null
+// for Path alone.
 static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const float* radiance_in,
                                 const tpt_aov* guides, const tpt_temporal_params* p, float* radiance_out,
                                 float* variance_out, float* history_len_out, float* motion_out, uint8_t* bgra_out,
-                                tpt_temporal_stats* stats, bool motion, const PathInputs* path = nullptr,
-                                bool deform = false) {
+                                tpt_temporal_stats* stats, TemporalKind kind, const PathInputs* path = nullptr) {
+    const bool motion = kind == TemporalKind::Motion, deform = kind == TemporalKind::Deform;
     if (!h) return fail(TPT_ERR_INVALID_ARG, "null history");
     if (!cam) return fail(TPT_ERR_INVALID_ARG, "null camera");
     if (!radiance_in) return fail(TPT_ERR_INVALID_ARG, "null radiance_in");
@@ -485,16 +484,8 @@ static tpt_status temporal_pass(tpt_history* h, const tpt_camera* cam, const flo
         HIP_OR_FAIL(hipEventRecord(h->clip_ev[1], st));
     }
     HIP_OR_FAIL(hipEventRecord(h->ev[0], st));
-    if (clip)
-        HIP_OR_FAIL(path     ? tpt::launch_temporal_path_clip(a, pa, cl, st)
-                    : motion ? tpt::launch_temporal_motion_clip(a, mo, cl, st)
-                    : deform ? tpt::launch_temporal_deform_clip(a, de, cl, st)
-                             : tpt::launch_temporal_clip(a, cl, st));
-    else
-        HIP_OR_FAIL(path     ? tpt::launch_temporal_path(a, pa, st)
-                    : motion ? tpt::launch_temporal_motion(a, mo, st)
-                    : deform ? tpt::launch_temporal_deform(a, de, st)
-                             : tpt::launch_temporal(a, st));
+    HIP_OR_FAIL(tpt::launch_temporal(a, motion ? &mo : nullptr, path ? &pa : nullptr, deform ? &de : nullptr,
+                                     clip ? &cl : nullptr, st));
     HIP_OR_FAIL(hipEventRecord(h->ev[1], st));
     if (deform) {   // the world buffers as this call saw them, for the next one
         HIP_OR_FAIL(hipMemcpyAsync(h->snap_verts.p, s->wverts.p, nv3 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -528,7 +519,7 @@ tpt_status tpt_temporal(tpt_history* h, const tpt_camera* cam, const float* radi
                         const tpt_temporal_params* p, float* radiance_out, float* variance_out,
                         float* history_len_out, uint8_t* bgra_out, tpt_temporal_stats* stats) {
     return temporal_pass(h, cam, radiance_in, guides, p, radiance_out, variance_out, history_len_out, nullptr, bgra_out,
-                         stats, false);
+                         stats, TemporalKind::Plain);
 }
 
 tpt_status tpt_temporal_motion(tpt_history* h, const tpt_camera* cam, const float* radiance_in, const tpt_aov* guides,
@@ -536,21 +527,21 @@ tpt_status tpt_temporal_motion(tpt_history* h, const tpt_camera* cam, const floa
                                float* history_len_out, float* motion_out, uint8_t* bgra_out,
                                tpt_temporal_stats* stats) {
     return temporal_pass(h, cam, radiance_in, guides, p, radiance_out, variance_out, history_len_out, motion_out,
-                         bgra_out, stats, true);
+                         bgra_out, stats, TemporalKind::Motion);
 }
 
-// tpt_temporal for a scene whose vertices moved (post.hip k_temporal_deform; DESIGN.md section 5
-// "Deforming meshes").
+// tpt_temporal for a scene whose vertices moved (post.hip k_temporal with DeformArgs; DESIGN.md
+// section 5 "Deforming meshes").
 tpt_status tpt_temporal_deform(tpt_history* h, const tpt_camera* cam, const float* radiance_in, const tpt_aov* guides,
                                const tpt_temporal_params* p, float* radiance_out, float* variance_out,
                                float* history_len_out, float* motion_out, uint8_t* bgra_out,
                                tpt_temporal_stats* stats) {
     return temporal_pass(h, cam, radiance_in, guides, p, radiance_out, variance_out, history_len_out, motion_out,
-                         bgra_out, stats, false, nullptr, true);
+                         bgra_out, stats, TemporalKind::Deform);
 }
 
-// tpt_temporal on mirror-path guides (post.hip k_temporal_path; DESIGN.md section 5 "Temporal
-// accumulation through mirrors").
+// tpt_temporal on mirror-path guides (post.hip k_temporal with TemporalPathArgs; DESIGN.md
+// section 5 "Temporal accumulation through mirrors").
 tpt_status tpt_temporal_path(tpt_history* h, const tpt_camera* cam, const float* radiance_in, const tpt_aov* path_guides,
                              const int32_t* bounces, const float* points, const tpt_temporal_path_params* p,
                              float* radiance_out, float* variance_out, float* history_len_out, uint8_t* bgra_out,
@@ -559,7 +550,7 @@ tpt_status tpt_temporal_path(tpt_history* h, const tpt_camera* cam, const float*
     const tpt_temporal_params tp{p->alpha, p->depth_tol, p->normal_min, p->max_history, p->flags};
     const PathInputs path{bounces, points, p->point_tol};
     return temporal_pass(h, cam, radiance_in, path_guides, &tp, radiance_out, variance_out, history_len_out, nullptr,
-                         bgra_out, stats, false, &path);
+                         bgra_out, stats, TemporalKind::Path, &path);
 }
 
 // The variance-guided a-trous filter (post.hip k_svgf_*; DESIGN.md section 5

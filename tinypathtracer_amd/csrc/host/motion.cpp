@@ -1,4 +1,4 @@
-// motion.cpp -- tpt_motion_matrices: what k_temporal_motion (post.hip) needs to follow an
+// motion.cpp -- tpt_motion_matrices: what k_temporal with MotionArgs (post.hip) needs to follow an
 // object from this frame's world into the previous frame's (DESIGN.md section 5 "Moving
 // objects").  Host only, no HIP: double arithmetic, each entry rounded to float once.
 #include <cmath>

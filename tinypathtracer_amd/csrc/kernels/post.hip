@@ -19,19 +19,22 @@
 //    between two colour planes, no atomics.  Each tap is two 16-B loads per lane;
 //    a wave of the direct kernel is a 64-pixel row segment, so its lanes read
 //    1 KiB of contiguous addresses per plane at every step size.
-//  * k_temporal / k_temporal_motion / k_temporal_path / k_temporal_deform (temporal_kernel.hpp):
-//    reprojection and accumulation across frames (tpt_temporal; tpt_temporal_motion, which follows
-//    objects that moved; tpt_temporal_path, which follows reflections in mirrors;
-//    tpt_temporal_deform, which follows meshes whose vertices moved).
-//  * k_clip_box and the four k_temporal*_clip: history clipping (tpt_history_set_clip): the box
-//    of the current frame's colours around each pixel, LDS-staged, and the temporal kernels
-//    compiled once more with the clamp to it.
+//  * k_temporal<TILES, Ex...> (temporal_kernel.hpp), a template over the argument structs a variant
+//    takes: reprojection and accumulation across frames (tpt_temporal; with MotionArgs
+//    tpt_temporal_motion, which follows objects that moved; with TemporalPathArgs tpt_temporal_path,
+//    which follows reflections in mirrors; with DeformArgs tpt_temporal_deform, which follows
+//    meshes whose vertices moved).
+//  * k_clip_box and k_temporal<..., ClipArgs>: history clipping (tpt_history_set_clip): the box
+//    of the current frame's colours around each pixel, LDS-staged, and each of the four temporal
+//    kernels again with the clamp to it.
 //  * k_svgf_pack / k_svgf_estimate / k_svgf_atrous / k_svgf_atrous_lds /
 //    k_svgf_resolve: the variance-guided filter (tpt_denoise_svgf) on the same two
 //    planes, the variance in the colour plane's fourth component.
 //  * k_upsample: guided upsampling (tpt_upsample) of a low-size frame to the full size by the
 //    feature buffers of both sizes, one launch, no scratch plane.
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"   // trace_dev.hpp's env helpers, unused here
+#include <type_traits>
+
 #include "trace_dev.hpp"
 
 namespace tpt {
@@ -224,8 +227,8 @@ __global__ __launch_bounds__(256) void k_aov(TraceArgs a, AovArgs o) {
 
 // The mirror-path kernel's text is aov_path_kernel.hpp, compiled twice: as k_aov_path, and with
 // TPT_AOV_PATH_POINTS as k_aov_path_points (tpt_render_aov_path_points), which also writes where
-// each path ended.  Two compilations of one text, as the temporal kernel below and for its reason:
-// k_aov_path's instructions stay what they were (tools/kernel_diff.py).
+// each path ended.  Two compilations of one text, so that k_aov_path's instructions stay what they
+// were (tools/kernel_diff.py).
 #define TPT_AOV_PATH_POINTS 0
 #include "aov_path_kernel.hpp"
 #undef TPT_AOV_PATH_POINTS
@@ -379,65 +382,16 @@ hipError_t launch_denoise_resolve(const DenoiseArgs& a, hipStream_t s) { return 
 constexpr float kSnap = 1.0f / 1024.0f;      // a reprojected coordinate this close to a pixel centre is that centre
 constexpr float kMinWsum = 1.0f / 16.0f;     // least sum of valid bilinear weights that counts as history
 
-// The temporal kernel's text is temporal_kernel.hpp, compiled twice: as k_temporal, and with
-// TPT_TEMPORAL_MOTION as k_temporal_motion (tpt_temporal_motion), whose additions are the
-// #if blocks there.  Two compilations of one text and not a template parameter: with the
-// parameter, k_temporal's instructions came out in another order and in other registers
-// (tools/kernel_diff.py), and the post-pass's recorded times belong to the code as it was.
-// Its lane's pixel, ray, albedo floor, framebuffer write and counter are the shared steps above,
-// which leave all four instantiations' instructions as they were.
-// A third compilation, with TPT_TEMPORAL_PATH, is k_temporal_path (tpt_temporal_path): the
-// pass on mirror-path guides, which compares bounce counts and terminal points as well.
-// A fourth, with TPT_TEMPORAL_DEFORM, is k_temporal_deform (tpt_temporal_deform): the pass
-// that follows deforming meshes through the previous frame's vertices.
-#define TPT_TEMPORAL_CLIP 0
-#define TPT_TEMPORAL_DEFORM 0
-#define TPT_TEMPORAL_PATH 0
-#define TPT_TEMPORAL_MOTION 0
+// k_temporal<TILES, Ex...> (temporal_kernel.hpp) is one template for the eight temporal kernels: the
+// pack Ex holds the argument structs a variant takes on top of TemporalArgs, so each instantiation
+// has the parameter list and the kernarg layout of the kernel it replaces, and its additions are the
+// `if constexpr` blocks there.  Its lane's pixel, ray, albedo floor, framebuffer write and counter are
+// the shared steps above.  The kernels used to be eight compilations of that text under four macros,
+// because a bool template parameter had reordered k_temporal's instructions.  What allowed the
+// template (tools/kernel_diff.py @tools/kernel_diff_temporal.args, device-only builds of this file at
+// the commit before and here): "identical: 37; different: 0", the sixteen temporal kernels among
+// them, with the registers, scratch and occupancy they had (make resource-usage-post).
 #include "temporal_kernel.hpp"
-#undef TPT_TEMPORAL_MOTION
-#define TPT_TEMPORAL_MOTION 1
-#include "temporal_kernel.hpp"
-#undef TPT_TEMPORAL_MOTION
-#undef TPT_TEMPORAL_PATH
-#define TPT_TEMPORAL_MOTION 0
-#define TPT_TEMPORAL_PATH 1
-#include "temporal_kernel.hpp"
-#undef TPT_TEMPORAL_PATH
-#undef TPT_TEMPORAL_DEFORM
-#define TPT_TEMPORAL_PATH 0
-#define TPT_TEMPORAL_DEFORM 1
-#include "temporal_kernel.hpp"
-#undef TPT_TEMPORAL_DEFORM
-#undef TPT_TEMPORAL_PATH
-#undef TPT_TEMPORAL_MOTION
-#undef TPT_TEMPORAL_CLIP
-// Four more, with TPT_TEMPORAL_CLIP: k_temporal_clip, k_temporal_motion_clip, k_temporal_path_clip
-// and k_temporal_deform_clip, the same four with history clipping (tpt_history_set_clip).  A
-// macro again and for the same reason: the four above stay what they were, instruction for
-// instruction (tools/kernel_diff.py against the commit before).
-#define TPT_TEMPORAL_CLIP 1
-#define TPT_TEMPORAL_DEFORM 0
-#define TPT_TEMPORAL_PATH 0
-#define TPT_TEMPORAL_MOTION 0
-#include "temporal_kernel.hpp"
-#undef TPT_TEMPORAL_MOTION
-#define TPT_TEMPORAL_MOTION 1
-#include "temporal_kernel.hpp"
-#undef TPT_TEMPORAL_MOTION
-#undef TPT_TEMPORAL_PATH
-#define TPT_TEMPORAL_MOTION 0
-#define TPT_TEMPORAL_PATH 1
-#include "temporal_kernel.hpp"
-#undef TPT_TEMPORAL_PATH
-#undef TPT_TEMPORAL_DEFORM
-#define TPT_TEMPORAL_PATH 0
-#define TPT_TEMPORAL_DEFORM 1
-#include "temporal_kernel.hpp"
-#undef TPT_TEMPORAL_DEFORM
-#undef TPT_TEMPORAL_PATH
-#undef TPT_TEMPORAL_MOTION
-#undef TPT_TEMPORAL_CLIP
 
 // The box of history clipping (DESIGN.md section 5 "History clipping" holds the definition):
 // 16x16 tiles; per pixel, the first two moments of the colour the temporal kernel accumulates
@@ -568,33 +522,17 @@ hipError_t launch_clip_box(const ClipBoxArgs& a, hipStream_t s) {
     }
 }
 
-hipError_t launch_temporal_clip(const TemporalArgs& a, const ClipArgs& cl, hipStream_t s) {
-    return launch_tiles_or_rows(a.tiles != 0, k_temporal_clip<true>, 0, k_temporal_clip<false>, a.width, a.height, s, a, cl);
+template <class... Ex>
+static hipError_t launch_temporal_as(const TemporalArgs& a, hipStream_t s, const Ex&... ex) {
+    return launch_tiles_or_rows(a.tiles != 0, k_temporal<true, Ex...>, 0, k_temporal<false, Ex...>, a.width, a.height, s, a, ex...);
 }
-hipError_t launch_temporal_motion_clip(const TemporalArgs& a, const MotionArgs& mo, const ClipArgs& cl, hipStream_t s) {
-    return launch_tiles_or_rows(a.tiles != 0, k_temporal_motion_clip<true>, 0, k_temporal_motion_clip<false>, a.width, a.height,
-                                s, a, mo, cl);
-}
-hipError_t launch_temporal_path_clip(const TemporalArgs& a, const TemporalPathArgs& pa, const ClipArgs& cl, hipStream_t s) {
-    return launch_tiles_or_rows(a.tiles != 0, k_temporal_path_clip<true>, 0, k_temporal_path_clip<false>, a.width, a.height, s,
-                                a, pa, cl);
-}
-hipError_t launch_temporal_deform_clip(const TemporalArgs& a, const DeformArgs& de, const ClipArgs& cl, hipStream_t s) {
-    return launch_tiles_or_rows(a.tiles != 0, k_temporal_deform_clip<true>, 0, k_temporal_deform_clip<false>, a.width, a.height,
-                                s, a, de, cl);
-}
-
-hipError_t launch_temporal_motion(const TemporalArgs& a, const MotionArgs& mo, hipStream_t s) {
-    return launch_tiles_or_rows(a.tiles != 0, k_temporal_motion<true>, 0, k_temporal_motion<false>, a.width, a.height, s, a, mo);
-}
-hipError_t launch_temporal(const TemporalArgs& a, hipStream_t s) {
-    return launch_tiles_or_rows(a.tiles != 0, k_temporal<true>, 0, k_temporal<false>, a.width, a.height, s, a);
-}
-hipError_t launch_temporal_path(const TemporalArgs& a, const TemporalPathArgs& pa, hipStream_t s) {
-    return launch_tiles_or_rows(a.tiles != 0, k_temporal_path<true>, 0, k_temporal_path<false>, a.width, a.height, s, a, pa);
-}
-hipError_t launch_temporal_deform(const TemporalArgs& a, const DeformArgs& de, hipStream_t s) {
-    return launch_tiles_or_rows(a.tiles != 0, k_temporal_deform<true>, 0, k_temporal_deform<false>, a.width, a.height, s, a, de);
+hipError_t launch_temporal(const TemporalArgs& a, const MotionArgs* mo, const TemporalPathArgs* pa, const DeformArgs* de,
+                           const ClipArgs* cl, hipStream_t s) {
+    if ((mo != nullptr) + (pa != nullptr) + (de != nullptr) > 1) return hipErrorInvalidValue;
+    const auto clip_or_not = [&](const auto&... kind) {
+        return cl ? launch_temporal_as(a, s, kind..., *cl) : launch_temporal_as(a, s, kind...);
+    };
+    return mo ? clip_or_not(*mo) : pa ? clip_or_not(*pa) : de ? clip_or_not(*de) : clip_or_not();
 }
 
 // ---- the variance-guided a-trous filter (Schied et al. 2017; DESIGN.md section 5 "Post-pass" holds the definition) ----
