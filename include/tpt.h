@@ -830,6 +830,80 @@ tpt_status tpt_upsample(tpt_scene* scene, int32_t low_width, int32_t low_height,
                         const tpt_upsample_params* params,
                         float* radiance_out, uint8_t* bgra_out, tpt_upsample_stats* stats);
 
+/* Tone mapping: exposure, tone curve and display encoding (DESIGN.md section 5 "Tone mapping",
+ * which holds the definition in full).  The display stage behind the post-pass: every other
+ * bgra_out of this header is linear radiance times 255, clamped and truncated (the reference's
+ * toUChar); this one is exposed, tone-mapped, encoded and rounded.
+ *
+ * tpt_exposure is the adapted exposure across frames.  It belongs to a scene (its device and
+ * stream), as a tpt_history does, and is destroyed before it.  It holds 2 KiB (the last
+ * measured histogram) and a few words on the device. */
+typedef struct tpt_exposure tpt_exposure;
+tpt_status tpt_exposure_create(tpt_scene* scene, tpt_exposure** out);
+/* Forget the adapted value: the next TPT_TONEMAP_AUTO call starts at its target. */
+tpt_status tpt_exposure_reset(tpt_exposure* exposure);
+void       tpt_exposure_destroy(tpt_exposure* exposure);
+/* The 256 bin counts of the last TPT_TONEMAP_AUTO call on the handle (zeros before the first);
+ * for tests and tools. */
+tpt_status tpt_exposure_histogram(const tpt_exposure* exposure, uint64_t* bins256);
+/* The duration of that call's measurement kernel (HIP events; 0 before the first); for tools. */
+tpt_status tpt_exposure_measure_ms(const tpt_exposure* exposure, double* ms);
+
+#define TPT_TONEMAP_AUTO    0x1    /* measure the frame's exposure (below); else scale = 2^ev */
+#define TPT_TONEMAP_DITHER  0x2    /* ordered 4x4 dither before the bytes are rounded */
+#define TPT_TONEMAP_LINEAR   0     /* op: y = min(x, 1) */
+#define TPT_TONEMAP_REINHARD 1     /* op: extended Reinhard on luminance */
+#define TPT_TONEMAP_ACES     2     /* op: ACES fit (Narkowicz 2015), per channel */
+#define TPT_TRANSFER_NONE    0
+#define TPT_TRANSFER_SRGB    1     /* piecewise sRGB OETF */
+#define TPT_TRANSFER_GAMMA   2     /* y^(1 / gamma) */
+
+typedef struct {
+    int32_t op, transfer, flags;
+    float ev;               /* stops, finite; fixed exposure, and added to the measured one under AUTO */
+    float white;            /* > 0: Reinhard's white point, in exposed luminance */
+    float gamma;            /* > 0: transfer 2 */
+    float key;              /* > 0: AUTO brings the trimmed log-average luminance to this */
+    float p_low, p_high;    /* 0 <= p_low < p_high <= 1: the share of counted pixels, by luminance, that is averaged */
+    float min_ev, max_ev;   /* min_ev <= max_ev: clamp of the measured log2 scale */
+    float rate;             /* (0, 1]: how far the state moves to its target per call; 1 = no adaptation */
+} tpt_tonemap_params;
+
+typedef struct {
+    double   hist_ms, map_ms;             /* HIP events; hist_ms 0 without AUTO */
+    float    log2_scale, scale;           /* what the map kernel used */
+    float    log2_avg;                    /* the trimmed log-average, AUTO */
+    uint64_t counted, dark, nonfinite;    /* AUTO; counted + dark + nonfinite == width * height */
+} tpt_tonemap_stats;
+
+/* One frame through exposure, tone curve, transfer function and rounding to bytes.
+ *   Luminance L = (0.2126 r + 0.7152 g) + 0.0722 b in float, uncontracted.
+ *   AUTO: a histogram of L over the frame, 256 bins of 1/8 octave over [2^-16, 2^16) taken from
+ *     the float's exponent and top three mantissa bits (L < 2^-16 is `dark`, NaN `nonfinite`,
+ *     L >= 2^16 bin 255); log2_avg is the mean of the bins' log2 centres over the pixels between
+ *     the shares p_low and p_high of the counted ones; target = clamp(log2(key) - log2_avg,
+ *     min_ev, max_ev); with an adapted `exposure` s = s' + rate (target - s'), else s = target; a
+ *     frame without a counted pixel keeps s' (0 without one).  log2_scale = s + ev.
+ *   Without AUTO: log2_scale = ev; `exposure` is neither read nor written.
+ *   Per channel x = min(max(c 2^log2_scale, 0), 65504), NaN to 0; the op; the transfer: y in [0, 1].
+ *   Bytes: floor(clamp(255 y + 0.5 + d, 0, 255)), d the 4x4 Bayer offset under DITHER, else 0.
+ *   radiance_in: width*height*3 floats, row 0 = bottom.  radiance_out: nullable, the same shape,
+ *     receives y; it may be radiance_in.  bgra_out: nullable, as tpt_denoise's (row 0 = top; B, G,
+ *     R written, alpha untouched).  At least one of the two.
+ *   exposure: nullable; with AUTO and none, the frame is measured and mapped without adaptation.
+ * Pointers are host or device memory (detected per pointer; tpt_render's stream rule for device
+ * memory); host buffers are staged in the buffers tpt_denoise stages its radiance and bytes in;
+ * all work is complete when the call returns.  `scene` supplies the device, the stream and the
+ * scratch (512 KiB of partial histograms under AUTO); it need not be built.  Deterministic: the
+ * counts are integers, and the scale goes from the measurement to the map kernel in device memory.
+ * TPT_ERR_INVALID_ARG (nothing is written, the exposure is left as it was): null scene /
+ * radiance_in / params, both outputs null, an exposure of another scene, a size <= 0, a side
+ * above 1,048,576, more than 2^31 pixels, an unknown op, transfer or flag, a parameter outside
+ * the ranges of tpt_tonemap_params or NaN. */
+tpt_status tpt_tonemap(tpt_scene* scene, tpt_exposure* exposure, int32_t width, int32_t height,
+                       const float* radiance_in, const tpt_tonemap_params* params,
+                       float* radiance_out, uint8_t* bgra_out, tpt_tonemap_stats* stats);
+
 /* Introspection for tests: copy back the built BVH in the reference node
  * layout (bvh.cuh:52-58, 36 B/node, 2F-1 nodes) and the sorted Morton keys. */
 tpt_status tpt_scene_read_bvh(tpt_scene* scene, void* nodes36, int64_t* keys);

@@ -292,6 +292,49 @@ private:
     std::unique_ptr<tpt_history, Free> h_;
 };
 
+// The hosts' defaults of tone mapping (PathTracer::tonemap).  Conventions -- Reinhard's white point
+// of 4, the sRGB curve, the photographic key of 0.18 and a 10 % / 95 % trim -- not the result of a sweep.
+inline tpt_tonemap_params defaultTonemap() {
+    tpt_tonemap_params p{};
+    p.op = TPT_TONEMAP_REINHARD;
+    p.transfer = TPT_TRANSFER_SRGB;
+    p.flags = 0;
+    p.ev = 0.0f;
+    p.white = 4.0f;
+    p.gamma = 2.2f;
+    p.key = 0.18f;
+    p.p_low = 0.10f;
+    p.p_high = 0.95f;
+    p.min_ev = -16.0f;
+    p.max_ev = 16.0f;
+    p.rate = 1.0f;
+    return p;
+}
+
+// tpt_tonemap's adapted exposure across frames (tpt_exposure).  Declared after the DeviceScene it
+// was created from, so that it is destroyed first.
+class Exposure {
+public:
+    explicit Exposure(DeviceScene& scene) {
+        tpt_exposure* x = nullptr;
+        check(tpt_exposure_create(scene.handle(), &x));
+        x_.reset(x);
+    }
+    void reset() { check(tpt_exposure_reset(x_.get())); }   // the next auto-exposed tonemap() starts at its target
+    std::vector<uint64_t> histogram() const {               // of the last auto-exposed call
+        std::vector<uint64_t> bins(256);
+        check(tpt_exposure_histogram(x_.get(), bins.data()));
+        return bins;
+    }
+    tpt_exposure* handle() const { return x_.get(); }
+
+private:
+    struct Free {
+        void operator()(tpt_exposure* x) const { tpt_exposure_destroy(x); }
+    };
+    std::unique_ptr<tpt_exposure, Free> x_;
+};
+
 class PathTracer {
 public:
     PathTracer() : PathTracer(1920, 1080) {}   // VkEngine default extent (vkEngine.h:24)
@@ -523,6 +566,19 @@ public:
         tpt_upsample_stats st{};
         check(tpt_upsample(scene.handle(), low_width, low_height, radiance_low, &guides_low, m_width, m_height, &guides,
                            &params, radiance_out, framebuffer, &st));
+        return st;
+    }
+
+    // The display stage (tpt_tonemap): exposure, tone curve, transfer function and rounding to
+    // bytes.  exposure: nullable, carries the adapted value across TPT_TONEMAP_AUTO frames.
+    // radiance_out (the mapped colours in [0, 1]; it may be radiance_in) and framebuffer are
+    // nullable, not both.  Pointers are host or device memory.
+    tpt_tonemap_stats tonemap(DeviceScene& scene, const float* radiance_in, float* radiance_out,
+                              uint8_t* framebuffer = nullptr, const tpt_tonemap_params& params = defaultTonemap(),
+                              Exposure* exposure = nullptr) {
+        tpt_tonemap_stats st{};
+        check(tpt_tonemap(scene.handle(), exposure ? exposure->handle() : nullptr, m_width, m_height, radiance_in, &params,
+                          radiance_out, framebuffer, &st));
         return st;
     }
 

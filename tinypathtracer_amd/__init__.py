@@ -25,7 +25,7 @@ from ._lib import TPTError, build_identity, check, lib
 __all__ = ["Camera", "Scene", "DeviceScene", "BVH", "EnvLight", "PathTracer", "Frame", "TPTError",
            "procedural_sky", "version", "device_count", "build_identity", "NODE_DTYPE", "DENOISE_DEFAULTS",
            "History", "TEMPORAL_DEFAULTS", "TEMPORAL_PATH_DEFAULTS", "CLIP_DEFAULTS", "motion_matrices", "ADAPTIVE_DEFAULTS",
-           "UPSAMPLE_DEFAULTS", "low_size"]
+           "UPSAMPLE_DEFAULTS", "low_size", "Exposure", "TONEMAP_DEFAULTS"]
 
 # BVHNode (include/bvh.cuh:52-58): parent, info{left,right | fid,placeHolder}, box
 NODE_DTYPE = np.dtype([("parent", "<u4"), ("a", "<i4"), ("b", "<i4"), ("bmin", "<f4", 3), ("bmax", "<f4", 3)])
@@ -672,6 +672,69 @@ class History:
             pass
 
 
+# Tone mapping (PathTracer.tonemap; tpt.hpp defaultTonemap): conventions -- Reinhard's white point of
+# 4, the sRGB curve, the photographic key of 0.18 and a 10 % / 95 % trim -- not the result of a sweep
+TONEMAP_DEFAULTS = {"op": "reinhard", "transfer": "srgb", "auto": False, "dither": False, "ev": 0.0, "white": 4.0,
+                    "gamma": 2.2, "key": 0.18, "p_low": 0.10, "p_high": 0.95, "min_ev": -16.0, "max_ev": 16.0,
+                    "rate": 1.0}
+
+
+class Exposure:
+    """tpt_tonemap's adapted exposure across frames (tpt_exposure): the log2 scale the last
+    auto-exposed frames settled on and the last measured histogram.  d_scene supplies the device
+    and the stream; close the exposure before it."""
+
+    def __init__(self, d_scene: DeviceScene):
+        self.handle = C.c_void_p()
+        check(lib().tpt_exposure_create(d_scene.handle, C.byref(self.handle)))
+        self._scene = d_scene                   # kept alive: the exposure is destroyed first
+
+    def reset(self):
+        """The next auto-exposed tonemap() starts at its target."""
+        check(lib().tpt_exposure_reset(self.handle))
+        return self
+
+    def histogram(self):
+        """The 256 bin counts (uint64) of the last auto-exposed tonemap() on this exposure."""
+        bins = np.zeros(256, np.uint64)
+        check(lib().tpt_exposure_histogram(self.handle, bins.ctypes.data))
+        return bins
+
+    def measure_ms(self) -> float:
+        """The duration of that call's measurement kernel."""
+        ms = C.c_double()
+        check(lib().tpt_exposure_measure_ms(self.handle, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self.handle:
+            lib().tpt_exposure_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _tonemap_params(given: dict):
+    """TONEMAP_DEFAULTS overridden by `given` as a tpt_tonemap_params: names are checked here, the
+    values' ranges by the library."""
+    unknown = sorted(set(given) - set(TONEMAP_DEFAULTS))
+    if unknown:
+        raise TypeError(f"tonemap: unknown parameter {', '.join(unknown)}; there are {', '.join(TONEMAP_DEFAULTS)}")
+    v = dict(TONEMAP_DEFAULTS, **given)
+    if v["op"] not in _lib.TONEMAP_OPS:
+        raise ValueError(f"tonemap: op must be one of {', '.join(_lib.TONEMAP_OPS)}, got {v['op']!r}")
+    if v["transfer"] not in _lib.TONEMAP_TRANSFERS:
+        raise ValueError(f"tonemap: transfer must be one of {', '.join(_lib.TONEMAP_TRANSFERS)}, got {v['transfer']!r}")
+    flags = (_lib.TONEMAP_AUTO if v["auto"] else 0) | (_lib.TONEMAP_DITHER if v["dither"] else 0)
+    return _lib.TonemapParams(_lib.TONEMAP_OPS[v["op"]], _lib.TONEMAP_TRANSFERS[v["transfer"]], flags, float(v["ev"]),
+                              float(v["white"]), float(v["gamma"]), float(v["key"]), float(v["p_low"]),
+                              float(v["p_high"]), float(v["min_ev"]), float(v["max_ev"]), float(v["rate"]))
+
+
 class PathTracer:
     """PathTracer (include/path_tracer.h:16-35), headless.
 
@@ -1069,6 +1132,36 @@ class PathTracer:
         if stats is not None:
             stats.update(st.as_dict())
         return out
+
+    def tonemap(self, d_scene: DeviceScene, radiance, *, exposure=None, out=None, bgra=None, stats=None, **params):
+        """The display stage (tpt_tonemap, DESIGN.md section 5 "Tone mapping") of `radiance`
+        [H, W, 3]: exposure, tone curve, transfer function, and rounding to bytes.  params override
+        TONEMAP_DEFAULTS: op "linear" | "reinhard" | "aces", transfer "none" | "srgb" | "gamma",
+        auto (measure the frame's exposure; else the scale is 2^ev), dither, ev, white, gamma, key,
+        p_low, p_high, min_ev, max_ev, rate.  exposure: an Exposure that carries the adapted value
+        across auto-exposed frames (None: each frame stands alone).  out: the buffer of the
+        mapped colours in [0, 1], [H, W, 3] float32; it may be `radiance` itself.  bgra: [H, W, 4]
+        uint8 as doTrace writes it, alpha untouched.  With neither, a new numpy array is `out`.
+        Buffers are numpy arrays or torch CUDA tensors.  Returns `out`, or `bgra` where only that
+        was given; stats: a dict that receives hist_ms, map_ms, log2_scale, scale, log2_avg,
+        counted, dark and nonfinite."""
+        W, H = self.m_width, self.m_height
+        p = _tonemap_params(params)
+        if exposure is not None and not isinstance(exposure, Exposure):
+            raise TypeError(f"exposure: need an Exposure or None, got {type(exposure).__name__}")
+        _check_plane("radiance", radiance, W, H)
+        if out is None and bgra is None:
+            out = np.zeros((H, W, 3), np.float32)
+        if out is not None:
+            _check_plane("radiance", out, W, H)
+        if bgra is not None:
+            _check_plane("framebuffer", bgra, W, H)
+        st = _lib.TonemapStats()
+        check(lib().tpt_tonemap(d_scene.handle, exposure.handle if exposure is not None else None, W, H,
+                                _addr(radiance), C.byref(p), _addr(out), _addr(bgra), C.byref(st)))
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out if out is not None else bgra
 
     def render(self, meshFile: str, nSamplesPerPixel: int = 64, seed=None, max_depth: int = 8, frames: int = 1):
         scene = Scene(meshFile, "gltf")

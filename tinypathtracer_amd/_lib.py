@@ -30,6 +30,10 @@ MOTION_TRACKED, MOTION_IDENTITY, MOTION_UNTRACKED = 0, 1, 2   # tpt_motion_matri
 SVGF_DEMODULATE = 0x1
 SVGF_DIRECT = 0x2
 UPSAMPLE_DEMODULATE = 0x1
+TONEMAP_AUTO = 0x1
+TONEMAP_DITHER = 0x2
+TONEMAP_OPS = {"linear": 0, "reinhard": 1, "aces": 2}
+TONEMAP_TRANSFERS = {"none": 0, "srgb": 1, "gamma": 2}
 
 
 class Material(C.Structure):
@@ -186,6 +190,20 @@ class UpsampleStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TonemapParams(C.Structure):
+    _fields_ = [("op", C.c_int32), ("transfer", C.c_int32), ("flags", C.c_int32), ("ev", C.c_float),
+                ("white", C.c_float), ("gamma", C.c_float), ("key", C.c_float), ("p_low", C.c_float),
+                ("p_high", C.c_float), ("min_ev", C.c_float), ("max_ev", C.c_float), ("rate", C.c_float)]
+
+
+class TonemapStats(C.Structure):
+    _fields_ = [("hist_ms", C.c_double), ("map_ms", C.c_double), ("log2_scale", C.c_float), ("scale", C.c_float),
+                ("log2_avg", C.c_float), ("counted", C.c_uint64), ("dark", C.c_uint64), ("nonfinite", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # (name, restype, argtypes) -- every symbol include/tpt.h declares
 SIGNATURES = [
     ("tpt_version", C.c_char_p, []),
@@ -250,6 +268,13 @@ SIGNATURES = [
     ("tpt_upsample", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Aov), C.c_int32, C.c_int32,
                                C.POINTER(Aov), C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p,
                                C.POINTER(UpsampleStats)]),
+    ("tpt_exposure_create", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("tpt_exposure_reset", C.c_int, [C.c_void_p]),
+    ("tpt_exposure_destroy", None, [C.c_void_p]),
+    ("tpt_exposure_histogram", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("tpt_exposure_measure_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("tpt_tonemap", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(TonemapParams),
+                              C.c_void_p, C.c_void_p, C.POINTER(TonemapStats)]),
     ("tpt_scene_read_bvh", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_scene_read_world", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tpt_debug_rng_init", C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),
@@ -316,7 +341,8 @@ def lib():
         # (an A/B against the build before them); the product library must export all
         older = bool(os.environ.get("TPT_LIB"))
         _NEWEST = ("tpt_render_adaptive", "tpt_scene_refit", "tpt_scene_read_wide", "tpt_wide_tree_levels",
-                   "tpt_upsample")
+                   "tpt_upsample", "tpt_exposure_create", "tpt_exposure_reset", "tpt_exposure_destroy",
+                   "tpt_exposure_histogram", "tpt_exposure_measure_ms", "tpt_tonemap")
         for name, res, args in SIGNATURES:
             if older and (name.startswith("tpt_debug_") or name in _NEWEST) and not hasattr(L, name):
                 continue

@@ -548,6 +548,49 @@ struct UpsampleArgs {
 };
 hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t s);
 
+// tonemap.hip: exposure, tone curve and display encoding (tpt_tonemap; DESIGN.md section 5 "Tone
+// mapping").  The exposure lives in device memory between the measuring kernels and the map kernel.
+struct ExposureBlock {                   // a tpt_exposure's device state, or the scene's for a call without one
+    double s;                            // the adapted log2 scale (meaningful where the host says so)
+    float log2_scale, scale;             // what the last AUTO call's map kernel used
+    float log2_avg;
+    float pad;
+    unsigned long long counted, dark, nonfinite;
+    unsigned long long hist[256];        // the last AUTO call's histogram
+};
+constexpr int kHistMaxBlocks = 512;      // the cap of the histogram kernel's grid: 2 workgroups of 256 lanes per CU
+constexpr int kHistRowWords = 256;       // a workgroup's row of the partials; the rows are followed by one
+                                         //   word per workgroup, its NaN count
+struct HistArgs {
+    const float* radiance;               // W*H*3
+    size_t npix;
+    uint32_t* partials;                  // kHistMaxBlocks * kHistRowWords + kHistMaxBlocks words
+    int32_t blocks;                      // the grid: min(kHistMaxBlocks, ceil(npix / 256))
+};
+struct MeasureArgs {
+    const uint32_t* partials;
+    int32_t blocks;
+    size_t npix;
+    ExposureBlock* block;
+    int32_t has_state;                   // block->s is the state s'
+    double p_low, p_high, key, min_ev, max_ev, rate, ev;   // tpt_tonemap_params', widened
+};
+struct TonemapArgs {
+    const float* radiance_in;            // W*H*3, row 0 = bottom
+    float* radiance_out;                 // nullable, W*H*3; may be radiance_in
+    uint8_t* bgra;                       // nullable, W*H*4, row 0 = top, alpha untouched
+    const ExposureBlock* block;          // AUTO: the scale is block->scale; null: `scale`
+    float scale;
+    int32_t width, height;
+    int32_t op, transfer, dither;
+    float white2;                        // white^2
+    float inv_gamma;                     // 1 / gamma
+};
+int hist_blocks(size_t npix);
+hipError_t launch_histogram(const HistArgs& a, hipStream_t s);
+hipError_t launch_measure(const MeasureArgs& a, hipStream_t s);
+hipError_t launch_tonemap(const TonemapArgs& a, hipStream_t s);
+
 }  // namespace tpt
 
 // The tolerance-mode build of trace.hip (TPT_FLAG_FAST; Makefile trace_fast.hip.o):

@@ -434,6 +434,12 @@ struct tpt_scene {
     // UpsampleArgs::fallback
     DevBuf<float> up_rad;
     SpreadCounters up_count;
+    // tpt_tonemap: no plane of its own.  Host buffers are staged in tpt_denoise's dn_rad (in and out
+    // share it) and dn_bgra; of its own the histogram kernel's partials, the exposure block of a
+    // call without a tpt_exposure and the pinned copy of a call's figures
+    DevBuf<uint32_t> tm_partials;
+    DevBuf<tpt::ExposureBlock> tm_block;
+    HostPinned<tpt::ExposureBlock> tm_fetch;
     // tpt_render_adaptive (adaptive.hip): the sums' snapshot at half a tile's samples (3 planes, 12 B
     // per pixel), the active tiles' list, the tiles' error estimates and sample counts, with pinned
     // host copies.  Kept between calls.
@@ -488,6 +494,16 @@ struct tpt_scene {
         }
         return e;
     }
+};
+
+// tpt_tonemap's exposure across frames (tonemap.hip k_tm_measure): the adapted log2 scale, the last
+// measured histogram and the last call's figures, on the device.
+struct tpt_exposure {
+    tpt_scene* scene = nullptr;             // the device and the stream; outlives the exposure
+    int device = 0;
+    DevBuf<tpt::ExposureBlock> block;
+    bool valid = false;                     // false after create / reset: block.s is not a state
+    double measure_ms = 0.0;                // the last AUTO call's measurement kernel
 };
 
 // Which of the four temporal entry points a call is: tpt_temporal, tpt_temporal_motion,

@@ -1,6 +1,7 @@
 // api_post.cpp -- the post-pass entry points of the C-ABI (post.hip): tpt_render_aov, tpt_render_aov_path,
 // tpt_render_aov_path_points, tpt_denoise, tpt_history_* (tpt_history_set_clip too), tpt_temporal, tpt_temporal_motion, tpt_temporal_path,
-// tpt_temporal_deform, tpt_denoise_svgf and tpt_upsample.  Each takes its buffers from either
+// tpt_temporal_deform, tpt_denoise_svgf and tpt_upsample, and of tonemap.hip: tpt_exposure_* and
+// tpt_tonemap.  Each takes its buffers from either
 // side: host buffers go through the device staging the scene / history keeps
 // (api_internal.hpp Staging).
 #include <cmath>
@@ -717,6 +718,159 @@ tpt_status tpt_upsample(tpt_scene* s, int32_t wl, int32_t hl, const float* radia
         HIP_OR_FAIL(elapsed_ms(s->ev[0], s->ev[1], &stats->kernel_ms));
         stats->fallback = s->up_count.sum(0);
     }
+    return TPT_OK;
+}
+
+// Tone mapping (tonemap.hip; DESIGN.md section 5 "Tone mapping").  The exposure handle keeps one
+// ExposureBlock on the device; whether its `s` is a state is known here.
+tpt_status tpt_exposure_create(tpt_scene* s, tpt_exposure** out) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (!out) return fail(TPT_ERR_INVALID_ARG, "null out");
+    DeviceGuard g(s->device);
+    std::unique_ptr<tpt_exposure> x(new tpt_exposure);
+    x->scene = s;
+    x->device = s->device;
+    HIP_OR_FAIL(x->block.alloc(1));
+    HIP_OR_FAIL(hipMemsetAsync(x->block.p, 0, sizeof(tpt::ExposureBlock), s->stream));
+    HIP_OR_FAIL(hipStreamSynchronize(s->stream));
+    *out = x.release();
+    return TPT_OK;
+}
+
+tpt_status tpt_exposure_reset(tpt_exposure* x) {
+    if (!x) return fail(TPT_ERR_INVALID_ARG, "null exposure");
+    x->valid = false;
+    return TPT_OK;
+}
+
+void tpt_exposure_destroy(tpt_exposure* x) {
+    if (!x) return;
+    DeviceGuard g(x->device);
+    delete x;
+}
+
+tpt_status tpt_exposure_histogram(const tpt_exposure* x, uint64_t* bins256) {
+    if (!x) return fail(TPT_ERR_INVALID_ARG, "null exposure");
+    if (!bins256) return fail(TPT_ERR_INVALID_ARG, "null bins256");
+    DeviceGuard g(x->device);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the bins are copied as they are");
+    HIP_OR_FAIL(hipMemcpyAsync(bins256, x->block.p->hist, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, x->scene->stream));
+    HIP_OR_FAIL(hipStreamSynchronize(x->scene->stream));
+    return TPT_OK;
+}
+
+tpt_status tpt_exposure_measure_ms(const tpt_exposure* x, double* ms) {
+    if (!x) return fail(TPT_ERR_INVALID_ARG, "null exposure");
+    if (!ms) return fail(TPT_ERR_INVALID_ARG, "null ms");
+    *ms = x->measure_ms;
+    return TPT_OK;
+}
+
+// Under AUTO: histogram, measurement, map; the scale stays on the device between them and comes
+// back with the figures once the map kernel is enqueued.  Otherwise the map kernel alone.
+tpt_status tpt_tonemap(tpt_scene* s, tpt_exposure* x, int32_t W, int32_t H, const float* radiance_in,
+                       const tpt_tonemap_params* p, float* radiance_out, uint8_t* bgra_out, tpt_tonemap_stats* stats) {
+    if (!s) return fail(TPT_ERR_INVALID_ARG, "null scene");
+    if (!radiance_in) return fail(TPT_ERR_INVALID_ARG, "null radiance_in");
+    if (!p) return fail(TPT_ERR_INVALID_ARG, "null params");
+    if (!radiance_out && !bgra_out) return fail(TPT_ERR_INVALID_ARG, "no output buffer: radiance_out and bgra_out are null");
+    if (x && x->scene != s) return fail(TPT_ERR_INVALID_ARG, "the exposure belongs to another scene");
+    constexpr int32_t kMaxSide = 1048576;   // tpt_upsample's
+    if (W <= 0 || H <= 0) return fail(TPT_ERR_INVALID_ARG, "bad frame size: width and height must be > 0");
+    if (W > kMaxSide || H > kMaxSide) return fail(TPT_ERR_INVALID_ARG, "bad frame size: a side above 1048576");
+    const size_t npix = (size_t)W * (size_t)H;
+    if (npix > ((size_t)1 << 31)) return fail(TPT_ERR_INVALID_ARG, "bad frame size: more than 2^31 pixels");
+    if (p->op < TPT_TONEMAP_LINEAR || p->op > TPT_TONEMAP_ACES) return fail(TPT_ERR_INVALID_ARG, "unknown tone map op");
+    if (p->transfer < TPT_TRANSFER_NONE || p->transfer > TPT_TRANSFER_GAMMA)
+        return fail(TPT_ERR_INVALID_ARG, "unknown transfer function");
+    if (p->flags & ~(TPT_TONEMAP_AUTO | TPT_TONEMAP_DITHER)) return fail(TPT_ERR_INVALID_ARG, "unknown tonemap flags");
+    // (every comparison is false for a NaN)
+    if (!std::isfinite(p->ev)) return fail(TPT_ERR_INVALID_ARG, "ev must be finite");
+    if (!(p->white > 0.0f && std::isfinite(p->white))) return fail(TPT_ERR_INVALID_ARG, "white must be finite and > 0");
+    if (!(p->gamma > 0.0f && std::isfinite(p->gamma))) return fail(TPT_ERR_INVALID_ARG, "gamma must be finite and > 0");
+    if (!(p->key > 0.0f && std::isfinite(p->key))) return fail(TPT_ERR_INVALID_ARG, "key must be finite and > 0");
+    if (!(p->p_low >= 0.0f && p->p_low < p->p_high && p->p_high <= 1.0f))
+        return fail(TPT_ERR_INVALID_ARG, "p_low and p_high must be 0 <= p_low < p_high <= 1");
+    if (!(p->min_ev <= p->max_ev && std::isfinite(p->min_ev) && std::isfinite(p->max_ev)))
+        return fail(TPT_ERR_INVALID_ARG, "min_ev and max_ev must be finite, min_ev <= max_ev");
+    if (!(p->rate > 0.0f && p->rate <= 1.0f)) return fail(TPT_ERR_INVALID_ARG, "rate must be in (0, 1]");
+    const bool autoexp = (p->flags & TPT_TONEMAP_AUTO) != 0;
+    DeviceGuard g(s->device);
+    hipStream_t st = s->stream;
+    tpt::TonemapArgs a{};
+    a.width = W;
+    a.height = H;
+    a.op = p->op;
+    a.transfer = p->transfer;
+    a.dither = (p->flags & TPT_TONEMAP_DITHER) ? 1 : 0;
+    a.white2 = p->white * p->white;
+    a.inv_gamma = 1.0f / p->gamma;
+    a.scale = std::exp2(p->ev);
+    tpt::ExposureBlock* block = nullptr;
+    if (autoexp) {
+        HIP_OR_FAIL(s->tm_partials.alloc((size_t)tpt::kHistMaxBlocks * (tpt::kHistRowWords + 1)));
+        HIP_OR_FAIL(s->tm_fetch.alloc(1));
+        if (!x) HIP_OR_FAIL(s->tm_block.alloc(1));
+        block = x ? x->block.p : s->tm_block.p;
+    }
+    Staging sg(st);
+    HIP_OR_FAIL(sg.in(s->dn_rad, radiance_in, 3 * npix, &a.radiance_in));
+    // radiance in and out share dn_rad: the histogram has read it, and a lane of the map kernel
+    // reads its pixel before it writes it
+    HIP_OR_FAIL(sg.out(s->dn_rad, radiance_out, 3 * npix, &a.radiance_out));
+    // alpha is untouched: the caller's bytes go up first
+    HIP_OR_FAIL(sg.inout(s->dn_bgra, bgra_out, 4 * npix, &a.bgra));
+    if (autoexp) {
+        tpt::HistArgs h{};
+        h.radiance = a.radiance_in;
+        h.npix = npix;
+        h.partials = s->tm_partials.p;
+        h.blocks = tpt::hist_blocks(npix);
+        tpt::MeasureArgs m{};
+        m.partials = h.partials;
+        m.blocks = h.blocks;
+        m.npix = npix;
+        m.block = block;
+        m.has_state = x && x->valid ? 1 : 0;
+        m.p_low = p->p_low;
+        m.p_high = p->p_high;
+        m.key = p->key;
+        m.min_ev = p->min_ev;
+        m.max_ev = p->max_ev;
+        m.rate = p->rate;
+        m.ev = p->ev;
+        a.block = block;
+        HIP_OR_FAIL(hipEventRecord(s->ev[0], st));
+        HIP_OR_FAIL(tpt::launch_histogram(h, st));
+        HIP_OR_FAIL(hipEventRecord(s->ev[1], st));
+        HIP_OR_FAIL(tpt::launch_measure(m, st));
+    }
+    HIP_OR_FAIL(hipEventRecord(s->ev[2], st));
+    HIP_OR_FAIL(tpt::launch_tonemap(a, st));
+    HIP_OR_FAIL(hipEventRecord(s->ev[3], st));
+    if (autoexp)   // the figures: the block without its histogram
+        HIP_OR_FAIL(hipMemcpyAsync(s->tm_fetch.p, block, offsetof(tpt::ExposureBlock, hist), hipMemcpyDeviceToHost, st));
+    HIP_OR_FAIL(sg.finish());
+    HIP_OR_FAIL(hipStreamSynchronize(st));
+    tpt_tonemap_stats r{};
+    r.log2_scale = p->ev;
+    r.scale = a.scale;
+    if (autoexp) {
+        const tpt::ExposureBlock& f = *s->tm_fetch.p;
+        r.log2_scale = f.log2_scale;
+        r.scale = f.scale;
+        r.log2_avg = f.log2_avg;
+        r.counted = f.counted;
+        r.dark = f.dark;
+        r.nonfinite = f.nonfinite;
+        HIP_OR_FAIL(elapsed_ms(s->ev[0], s->ev[1], &r.hist_ms));
+        if (x) {
+            if (f.counted > 0) x->valid = true;   // a frame without a counted pixel keeps what there was
+            HIP_OR_FAIL(elapsed_ms(s->ev[1], s->ev[2], &x->measure_ms));
+        }
+    }
+    HIP_OR_FAIL(elapsed_ms(s->ev[2], s->ev[3], &r.map_ms));
+    if (stats) *stats = r;
     return TPT_OK;
 }
 

@@ -10,6 +10,8 @@
 //              [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP] [--refit]
 //              [--adaptive TARGET [--min-spp N] [--max-spp N]]
 //              [--clip [GAMMA]] [--clip-radius R] [--clip-history N] [--scale S]
+//              [--tonemap [linear|reinhard|aces]] [--ev STOPS] [--auto-exposure [KEY]] [--adapt RATE]
+//              [--srgb | --gamma G] [--dither]
 // --aov writes the first-hit feature buffers <out>_albedo.pfm, <out>_normal.pfm and
 // <out>_depth.pfm (tpt_render_aov); --denoise writes <out>_denoised.pfm / .ppm, the
 // a-trous filter of the written frame (tpt_denoise, the hosts' defaults; with
@@ -53,6 +55,16 @@
 // full-size frame.  <out>_low.pfm holds the traced frame, and each frame prints its fallback pixel
 // count on stderr.  With --aov-path both guide sets are the path buffers and the colours are
 // demodulated.  Not with --adaptive or --progressive.
+// --tonemap [linear|reinhard|aces] (default reinhard) writes <out>_display.ppm, the display stage
+// (tpt_tonemap, the hosts' defaults but no transfer function unless --srgb or --gamma G is given) of
+// the last frame the chain produced: the render (upsampled under --scale), or the output of
+// --temporal*, --denoise or --svgf (of --svgf where both are given).  --ev STOPS is the fixed
+// exposure (added to the measured one under --auto-exposure); --auto-exposure [KEY] measures each
+// frame's exposure (key 0.18 unless given); --adapt RATE moves the exposure that far towards each
+// frame's target; --dither adds the ordered dither.  With --frames F and --temporal* every frame's
+// accumulated output goes through one tpt_exposure and prints its scale on stderr; the file holds
+// the last frame, and a --denoise / --svgf output is mapped at the scale that frame got.  Every
+// other file is written as without these options; all of them but --tonemap are refused without it.
 // --refit (with --move / --spin / --wave): the frames after the first refit the BVH
 // (tpt_scene_refit) instead of rebuilding it, and each prints its tree cost against the built
 // one and the refit's device time on stderr.
@@ -117,7 +129,9 @@ const char* kUsage =
     "[--aov] [--denoise [iterations]] [--temporal] [--yaw DEG] [--svgf [iterations]] "
     "[--aov-path [bounces]] [--move OBJ DX DY DZ] [--spin OBJ DEG] [--wave OBJ AMP] [--refit] [--truck DX DY DZ] "
     "[--temporal-path [bounces]] [--adaptive TARGET [--min-spp N] [--max-spp N]] "
-    "[--clip [GAMMA]] [--clip-radius R] [--clip-history N] [--scale S]\n";
+    "[--clip [GAMMA]] [--clip-radius R] [--clip-history N] [--scale S] "
+    "[--tonemap [linear|reinhard|aces]] [--ev STOPS] [--auto-exposure [KEY]] [--adapt RATE] "
+    "[--srgb | --gamma G] [--dither]\n";
 
 // The scene's camera turned by `deg` degrees about its own origin and up axis: c2w * R_y
 tpt::Camera yawed(const tpt::Camera& base, double deg) {
@@ -246,6 +260,11 @@ int main(int argc, char** argv) {
     bool clip = false, clip_opts = false;   // --clip; --clip-radius or --clip-history given
     tpt_clip_params clip_params = tpt::defaultClip();
     int scale = 1;                       // --scale: frames are traced at 1 / scale of the size and upsampled
+    bool tonemap = false;                // --tonemap: <out>_display.ppm
+    const char* tm_opt = nullptr;        // the first of --ev, --auto-exposure, --adapt, --srgb, --gamma, --dither given
+    bool tm_adapt = false, tm_srgb = false, tm_gamma = false;
+    tpt_tonemap_params tm = tpt::defaultTonemap();
+    tm.transfer = TPT_TRANSFER_NONE;
     auto motion_of = [&](uint32_t object) -> ObjectMotion& {
         for (auto& om : motions)
             if (om.object == object) return om;
@@ -312,6 +331,35 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (a == "--tonemap") {
+            tonemap = true;   // an optional operator follows
+            if (i + 1 < argc && argv[i + 1][0] != '-') {
+                const std::string op = argv[++i];
+                if (op == "linear") tm.op = TPT_TONEMAP_LINEAR;
+                else if (op == "reinhard") tm.op = TPT_TONEMAP_REINHARD;
+                else if (op == "aces") tm.op = TPT_TONEMAP_ACES;
+                else {
+                    std::fprintf(stderr, "--tonemap: the operator must be linear, reinhard or aces\n");
+                    return 2;
+                }
+            }
+        }
+        else if (a == "--ev") { tm_opt = tm_opt ? tm_opt : "--ev"; tm.ev = std::stof(next()); }
+        else if (a == "--auto-exposure") {
+            tm_opt = tm_opt ? tm_opt : "--auto-exposure";
+            tm.flags |= TPT_TONEMAP_AUTO;   // an optional key follows
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.'))
+                tm.key = std::stof(argv[++i]);
+        }
+        else if (a == "--adapt") { tm_opt = tm_opt ? tm_opt : "--adapt"; tm_adapt = true; tm.rate = std::stof(next()); }
+        else if (a == "--srgb") { tm_opt = tm_opt ? tm_opt : "--srgb"; tm_srgb = true; tm.transfer = TPT_TRANSFER_SRGB; }
+        else if (a == "--gamma") {
+            tm_opt = tm_opt ? tm_opt : "--gamma";
+            tm_gamma = true;
+            tm.transfer = TPT_TRANSFER_GAMMA;
+            tm.gamma = std::stof(next());
+        }
+        else if (a == "--dither") { tm_opt = tm_opt ? tm_opt : "--dither"; tm.flags |= TPT_TONEMAP_DITHER; }
         else if (a == "--clip") {
             clip = true;   // an optional gamma follows
             if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.'))
@@ -379,6 +427,26 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--min-spp and --max-spp need --adaptive TARGET\n");
         return 2;
     }
+    if (tm_opt && !tonemap) {
+        std::fprintf(stderr, "%s needs --tonemap\n", tm_opt);
+        return 2;
+    }
+    if (tm_srgb && tm_gamma) {
+        std::fprintf(stderr, "--srgb cannot be combined with --gamma\n");
+        return 2;
+    }
+    if (tm_adapt && !(tm.flags & TPT_TONEMAP_AUTO)) {
+        std::fprintf(stderr, "--adapt needs --auto-exposure\n");
+        return 2;
+    }
+    if (!(tm.rate > 0.0f && tm.rate <= 1.0f)) {
+        std::fprintf(stderr, "--adapt RATE: RATE must be in (0, 1]\n");
+        return 2;
+    }
+    if (!(tm.gamma > 0.0f) || !(tm.key > 0.0f)) {
+        std::fprintf(stderr, "--gamma G and --auto-exposure KEY: the value must be > 0\n");
+        return 2;
+    }
     try {
         tpt::EnvLight env;
         if (!env_file.empty()) {
@@ -432,16 +500,30 @@ int main(int argc, char** argv) {
         std::vector<float> acc;       // --temporal: the accumulated frame,
         std::vector<float> var, len;  //   its luminance variance and history length
         tpt::AOV g;
+        // --tonemap: <out>_display.ppm from `rad`; the exposure lives as long as the frames do
+        std::vector<uint8_t> display;
+        std::unique_ptr<tpt::Exposure> exposure(tonemap ? new tpt::Exposure(d) : nullptr);
+        tpt_tonemap_stats tms{};
+        auto show = [&](const float* rad, const tpt_tonemap_params& prm) {
+            display.assign((size_t)W * H * 4, 255);
+            tms = pt.tonemap(d, rad, nullptr, display.data(), prm, exposure.get());
+        };
         if (temporal) {
             tpt::History hist(d, W, H);
             if (clip) hist.setClip(&clip_params);
             tpt_temporal_stats ts{};
-            auto report = [&](int i) {   // (the clip's figures, where it is on)
-                if (!clip) return;
-                const tpt_clip_stats cs = hist.clipStats();
-                std::fprintf(stderr, "frame %d: reprojected %llu, clipped %llu, boxed %llu, box %.3f ms\n", i,
-                             (unsigned long long)ts.reprojected, (unsigned long long)cs.clipped,
-                             (unsigned long long)cs.boxed, cs.box_ms);
+            auto report = [&](int i) {   // (the clip's figures and the display stage, where they are on)
+                if (clip) {
+                    const tpt_clip_stats cs = hist.clipStats();
+                    std::fprintf(stderr, "frame %d: reprojected %llu, clipped %llu, boxed %llu, box %.3f ms\n", i,
+                                 (unsigned long long)ts.reprojected, (unsigned long long)cs.clipped,
+                                 (unsigned long long)cs.boxed, cs.box_ms);
+                }
+                if (tonemap) {
+                    show(acc.data(), tm);
+                    std::fprintf(stderr, "frame %d: exposure scale %.9g (log2 %.9g)\n", i, (double)tms.scale,
+                                 (double)tms.log2_scale);
+                }
             };
             acc.resize((size_t)W * H * 3);
             var.resize((size_t)W * H);
@@ -510,6 +592,14 @@ int main(int argc, char** argv) {
         write_ppm(out + ".ppm", f.bgra, W, H);
         write_pfm(out + ".pfm", f.radiance, W, H, 3);
         if (scale > 1) write_pfm(out + "_low.pfm", low_rad, lo.width, lo.height, 3);
+        // --tonemap: the frame the display stage takes, unless a filter below replaces it.  After
+        // --temporal the last frame is mapped already; a filtered one is mapped at that frame's scale.
+        tpt_tonemap_params tm_last = tm;
+        if (tonemap && temporal) {
+            tm_last.flags &= ~TPT_TONEMAP_AUTO;
+            tm_last.ev = tms.log2_scale;
+        }
+        std::vector<float> shown;
         if (aov || aov_path || denoise || svgf) {
             if (aov_path) {   // the filters' guides follow the mirrors (the temporal pass above did not)
                 std::vector<int32_t> bounces;
@@ -530,6 +620,7 @@ int main(int argc, char** argv) {
                            tpt::defaultDenoise(dn_iterations));
                 write_pfm(out + "_denoised.pfm", clean, W, H, 3);
                 write_ppm(out + "_denoised.ppm", fb, W, H);
+                if (tonemap) shown = clean;
             }
             if (svgf) {   // of the temporal output, by its variance and history length, when there is one
                 std::vector<float> clean((size_t)W * H * 3);
@@ -539,7 +630,15 @@ int main(int argc, char** argv) {
                                tpt::defaultSVGF(sv_iterations));
                 write_pfm(out + "_svgf.pfm", clean, W, H, 3);
                 write_ppm(out + "_svgf.ppm", fb, W, H);
+                if (tonemap) shown = clean;
             }
+        }
+        if (tonemap) {
+            if (!shown.empty()) show(shown.data(), tm_last);
+            else if (!temporal) show(f.radiance.data(), tm);
+            if (!temporal)
+                std::fprintf(stderr, "exposure scale %.9g (log2 %.9g)\n", (double)tms.scale, (double)tms.log2_scale);
+            write_ppm(out + "_display.ppm", display, W, H);
         }
         if (adaptive) {
             std::printf("{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"target\": %g, \"min_spp\": %d, "
